@@ -21,6 +21,14 @@ last limb (rns_ntt.sharded).  `--shard batch` is SURVEY §8e's zero-collective
 comparison (each rank its own ciphertexts over all limbs, a full key
 replica); the line's config.parallelism names the layout that ran.
 
+A plain run sets up, warms up, times `--steps` steps and prints the line.
+`--full` adds what the headline figure does not need: the oracle parity
+spot check, the CPU baseline, the power/clock probe, the live rocprofv3
+--pmc passes and the stream-copy bandwidth (their fields are null without
+it).  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs); the inputs are seeded, so two runs with the
+same arguments work on identical operands.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -100,7 +108,17 @@ def parse():
     p.add_argument("--strong", action="store_true",
                    help="poly-mul: --batch is the fixed global batch split over the ranks (strong "
                         "scaling) instead of the per-GPU batch (weak, the default)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the oracle parity spot check, "
+                        "the CPU baseline, the power/clock probe, the live rocprofv3 --pmc passes and the "
+                        "stream-copy bandwidth (each still switched off by its own --no-* option)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step computed as DIR/<name>.npy "
+                        "(float64, a fixed seeded sample of the batch, at most 64 MB in all)")
+    args = p.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_power = args.no_live_pmc = True
+    return args
 
 
 def relaunch_with_torchrun(args) -> int:
@@ -266,6 +284,47 @@ def uniform(rng, mods, count, n):
     return rng.integers(0, 1 << 62, size=(count, len(mods), n), dtype=np.uint64) % q
 
 
+DUMP_BUDGET = 64 * 10 ** 6  # bytes of array data one --dump-outputs run may write
+
+
+def dump_outputs(args, rank, world, outputs, wide=False):
+    """--dump-outputs DIR: write the timed path's outputs of its last step.
+    `outputs` = [(name, count, get)]: get(i) returns item i of the batch of
+    `count` as an array (this rank's [L][N] residues of poly i, or a
+    plaintext's complex slots).  Each output gets an equal share of
+    DUMP_BUDGET: items 0 and count - 1, then items in the order of a fixed
+    seeded permutation until the share is full (leading rows only where one
+    item alone exceeds it).  All files are float64, which holds a 31-bit
+    residue exactly; `wide` (62-bit residues) splits an output into
+    <name>_hi (v >> 31) and <name>_lo (v mod 2^31), a complex one into
+    <name>_re and <name>_im.  At N > 1 ranks write <name>_rank<r>.npy."""
+    if not args.dump_outputs:
+        return
+    import numpy as np
+
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_BUDGET // len(outputs)
+    for name, count, get in outputs:
+        x0 = np.asarray(get(0))
+        parts = 2 if (wide or np.iscomplexobj(x0)) else 1
+        row_bytes = x0[0].size * 8 * parts
+        rows = min(x0.shape[0], max(1, share // row_bytes))
+        k = max(1, min(count, share // (rows * row_bytes)))
+        order = [0, count - 1] + [int(i) for i in np.random.default_rng(2024).permutation(count)]
+        idx = sorted(list(dict.fromkeys(order))[:k])
+        arr = np.stack([np.asarray(get(i))[:rows] for i in idx])
+        if np.iscomplexobj(arr):
+            files = [(name + "_re", arr.real), (name + "_im", arr.imag)]
+        elif wide:
+            files = [(name + "_hi", arr >> np.uint64(31)), (name + "_lo", arr & np.uint64((1 << 31) - 1))]
+        else:
+            files = [(name, arr)]
+        for fname, a in files:
+            if world > 1:
+                fname += f"_rank{rank}"
+            np.save(os.path.join(args.dump_outputs, fname + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def pmc_field(kernel, workload, batch, log_n, L, field):
     """Another per-launch field (e.g. SQ_INSTS_VALU) of the same committed
     pass as traffic_for; None when none of this shape is committed."""
@@ -419,6 +478,7 @@ def run_polymul(args, comm, world, rank, local_rank):
         if cnt:
             kernels[k] = {"launches": cnt, "avg_ms": ms / cnt, "total_ms": ms}
     B.profile_enable(False)
+    dump_outputs(args, rank, world, [("c", batch, lambda i: out.channels_of(i)[0])], wide=wb == 8)
     power = None
     if rank == 0 and not args.no_power:
         power = power_probe(lambda: rn.check(lib.rnt_mul(out.handle, a.handle, b.handle)), B.sync,
@@ -428,7 +488,7 @@ def run_polymul(args, comm, world, rank, local_rank):
     # (rnt_copy: a plain 16-byte-per-lane copy kernel, k_copy16, timed by its
     # HIP events)
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         dst = rn.RnsPoly(B, batch)
         rn.check(lib.rnt_copy(dst.handle, a.handle))
         B.sync()
@@ -445,9 +505,10 @@ def run_polymul(args, comm, world, rank, local_rank):
     value = global_batch * args.steps / elapsed  # whole-job poly-muls / s (slowest rank's time)
 
     # spot parity of the timed output (this rank's limbs of the first and the
-    # last pair) vs the oracle
-    parity_ok = True
-    if rank == 0:
+    # last pair) vs the oracle (--full)
+    parity_ok = None
+    if rank == 0 and args.full:
+        parity_ok = True
         orc = oracle()
         ob = orc.Basis(lmod, n)
         for pi in sorted({0, batch - 1}):
@@ -679,8 +740,10 @@ def run_ctmul_graph(args, comm, world, rank, local_rank):
          "ks_whole", "mf_tensor"))
     ms_per_step = elapsed / args.steps * 1e3
     value = B * args.steps * world / elapsed
+    dump_outputs(args, rank, world, [("c0", B, lambda i: r0.channels_of(i)[0]),
+                                     ("c1", B, lambda i: r1.channels_of(i)[0])], wide=wb == 8)
     parity_ok = None
-    if rank == 0:
+    if rank == 0 and args.full:
         orc = oracle()
         ob = orc.Basis(mod, n)
         parity_ok = True
@@ -805,6 +868,8 @@ def run_ctmul(args, comm, world, rank, local_rank):
         if cnt:
             kernels[k] = {"launches": cnt, "avg_ms": ms / cnt, "total_ms": ms}
     prof_basis.profile_enable(False)
+    dump_outputs(args, rank, world, [("c0", B, lambda i: pipe.download(r[0], first=i, count=1)[0]),
+                                     ("c1", B, lambda i: pipe.download(r[1], first=i, count=1)[0])], wide=wb == 8)
     power = None
     if rank == 0 and world == 1 and not args.no_power:
         power = power_probe(step, torch.cuda.synchronize, local_rank)
@@ -818,13 +883,14 @@ def run_ctmul(args, comm, world, rank, local_rank):
     # 0 over the gloo control plane, which assembles the full ciphertexts.
     # the first pair, the first of the second pipeline chunk (or, one chunk,
     # of the library's second key-switch chunk at N = 2^16: 256), the last
-    check_pairs = sorted({0, min(pipe.chunk, 256, B - 1), B - 1})
+    # (--full; none otherwise)
+    check_pairs = sorted({0, min(pipe.chunk, 256, B - 1), B - 1}) if args.full else []
     mine = {pi: pipe.download(r[0], first=pi, count=1)[0] for pi in check_pairs}
     if world > 1 and not batch_shard:
         parts = comm.gather((rank, pipe.limbs.start, mine))
     else:
         parts = [(0, 0, mine)]
-    if rank == 0:
+    if rank == 0 and args.full:
         orc = oracle()
         ob = orc.Basis(mod, n)
         threads = usable_threads()
@@ -988,6 +1054,8 @@ def run_rotate(args, comm, world, rank, local_rank):
         Bs.profile_enable(False)
         kms = sum(kv["total_ms"] for kv in kernels.values()) / args.steps
         graph_info = {"kernel_ms_per_step": kms, "device_busy": kms / (elapsed / args.steps * 1e3)}
+    dump_outputs(args, rank, world, [("c0", B, lambda i: out0.channels_of(i)[0]),
+                                     ("c1", B, lambda i: out1.channels_of(i)[0])], wide=wb == 8)
     power = None
     if rank == 0 and not args.no_power:
         power = power_probe(step, Bs.sync, local_rank)
@@ -1013,7 +1081,7 @@ def run_rotate(args, comm, world, rank, local_rank):
 
     parity_ok = None
     cpu = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # the last offset of the sweep, ciphertext 0 and the batch's last one,
         # against the oracle's rotate_ciphertext (channel-parallel)
         orc = oracle()
@@ -1110,6 +1178,7 @@ def run_encode(args, comm, world, rank, local_rank):
         if cnt:
             kernels[k] = {"launches": cnt, "avg_ms": ms / cnt, "total_ms": ms}
     Bs.profile_enable(False)
+    dump_outputs(args, rank, world, [("slots", B, lambda i: out[i])])
     err = float(np.max(np.abs(out - v)))
     # algorithmic bytes of one special-FFT launch (encode or decode of the
     # batch): the N/2 complex slots (16 B) and the N i64 coefficients (8 B)
@@ -1185,6 +1254,7 @@ def run_ntt(args, comm, world, rank, local_rank):
         if cnt:
             kernels[k] = {"launches": cnt, "avg_ms": ms / cnt, "total_ms": ms}
     B.profile_enable(False)
+    dump_outputs(args, rank, world, [("x", batch, lambda i: x.channels_of(i)[0])], wide=wb == 8)
     power = None
     if rank == 0 and not args.no_power:
         power = power_probe(step, B.sync, local_rank)
@@ -1193,7 +1263,7 @@ def run_ntt(args, comm, world, rank, local_rank):
     parity_ok = bool(np.array_equal(x.channels_of(0)[0], first)
                      and np.array_equal(x.channels_of(batch - 1)[0], last))
     cpu = None
-    if rank == 0:
+    if rank == 0 and args.full:
         orc = oracle()
         ob = orc.Basis(mod, n)
         x.to_ntt_domain()
@@ -1287,11 +1357,13 @@ def run_pointwise(args, comm, world, rank, local_rank):
     elapsed = comm.max(t1 - t0)
     cnt, ms = B.profile_read("elementwise")
     B.profile_enable(False)
+    dump_outputs(args, rank, world, [("c", batch, lambda i: out.channels_of(i)[0])], wide=wb == 8)
     power = None
     if rank == 0 and not args.no_power:
         power = power_probe(lambda: rn.check(lib.rnt_mul(out.handle, a.handle, b.handle)), B.sync, local_rank)
-    parity_ok = True
-    if rank == 0:
+    parity_ok = None
+    if rank == 0 and args.full:
+        parity_ok = True
         orc = oracle()
         ob = orc.Basis(mod, n)
         for pi in sorted({0, batch - 1}):
@@ -1362,6 +1434,7 @@ def run_copy(args, comm, world, rank, local_rank):
     elapsed = comm.max(t1 - t0)
     cnt, ms = B.profile_read("copy")
     B.profile_enable(False)
+    dump_outputs(args, rank, world, [("dst", args.batch, lambda i: dst.channels_of(i)[0])], wide=wb == 8)
     power = power_probe(step, B.sync, local_rank) if rank == 0 and not args.no_power else None
     alg = 2 * L * args.batch * n * wb
     achieved = alg / (ms / cnt * 1e-3) / 1e9
@@ -1436,14 +1509,18 @@ def run_rotate_sharded(args, comm, world, rank, local_rank, log_n, L, mod):
     elapsed = comm.max(t1 - t0)
     value = B * len(offsets) * args.steps / elapsed
     bfly = (L * L + 2 * L) * (n // 2) * log_n
+    dump_outputs(args, rank, world, [("c0", B, lambda i: pipe.download(out[0], first=i, count=1)[0]),
+                                     ("c1", B, lambda i: pipe.download(out[1], first=i, count=1)[0])],
+                 wide=max(mod) >= (1 << 31))
     # sampled parity of the last offset's output: ciphertext 0 and the last
     # one, every rank's limbs gathered to rank 0 over the gloo control plane
-    check = sorted({0, B - 1})
+    # (--full; none otherwise)
+    check = sorted({0, B - 1}) if args.full else []
     mine = {p: (pipe.download(out[0], first=p, count=1)[0], pipe.download(out[1], first=p, count=1)[0])
             for p in check}
     parts = comm.gather((pipe.limbs.start, mine))
     parity_ok = None
-    if rank == 0:
+    if rank == 0 and args.full:
         orc = oracle()
         ob = orc.Basis(mod, n)
         parts = sorted(parts, key=lambda t: t[0])

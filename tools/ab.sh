@@ -12,9 +12,10 @@ set -o pipefail
 mkdir -p gpurun_out
 REPS=$1; shift
 VARS=${@:-base}
-# AB_POWER=1 keeps the bench's power probe (3 s more per run)
-POWER_ARG=--no-power
-[ "${AB_POWER:-0}" = "1" ] && POWER_ARG=
+# --full: the summary prints each run's parity spot check; AB_POWER=1 also
+# keeps the bench's power probe (3 s more per run)
+POWER_ARG="--full --no-power"
+[ "${AB_POWER:-0}" = "1" ] && POWER_ARG=--full
 if [ -n "${AB_PYTEST:-}" ]; then
   for v in $VARS; do
     IFS='+' read -ra parts <<< "$v"

@@ -10,8 +10,8 @@ run() {  # run <name> <seconds> <bench args...>
   timeout -k 10 "$secs" python bench.py "$@" > gpurun_out/bench_$name.json 2> gpurun_out/bench_$name.err || exit $?
   echo "== $name $(head -c 160 gpurun_out/bench_$name.json)" >&2
 }
-run polymul 300 --steps 20 --warmup 3
-run ctmul 300 --workload ctmul --ct-batch 128 --steps 10 --warmup 2
-run rotate 300 --workload rotate --rot-batch 8 --steps 3 --warmup 1
-run rotate_b1 300 --workload rotate --rot-batch 1 --steps 5 --warmup 1
-run rotate_all 400 --workload rotate --rot-offsets all --rot-batch 1 --steps 1 --warmup 0
+run polymul 300 --full --steps 20 --warmup 3
+run ctmul 300 --full --workload ctmul --ct-batch 128 --steps 10 --warmup 2
+run rotate 300 --full --workload rotate --rot-batch 8 --steps 3 --warmup 1
+run rotate_b1 300 --full --workload rotate --rot-batch 1 --steps 5 --warmup 1
+run rotate_all 400 --full --workload rotate --rot-offsets all --rot-batch 1 --steps 1 --warmup 0

@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_configs.py -m gpu -x -v -k 
 tail -2 $O/pytest.log
 run() {  # run <name> <bench args...>
   local name=$1; shift
-  timeout -k 10 400 python3 bench.py "$@" > $O/$name.json 2> $O/$name.err || { echo "$name rc=$?"; tail -20 $O/$name.err; exit 1; }
+  timeout -k 10 400 python3 bench.py --full "$@" > $O/$name.json 2> $O/$name.err || { echo "$name rc=$?"; tail -20 $O/$name.err; exit 1; }
   head -c 240 $O/$name.json; echo
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$name -o run -- python3 bench.py --no-cpu-baseline --no-power "$@" > $O/trace_$name.json 2> $O/trace_$name.err || { echo "trace $name rc=$?"; tail -20 $O/trace_$name.err; exit 1; }
 }

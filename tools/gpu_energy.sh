@@ -13,7 +13,7 @@ run() {  # run <tag> <lib|-> <bench args...>
   local env=()
   [ "$lib" != "-" ] && env=(RNSNTT_LIB=$ROOT/toy-heaan-ckks_amd/lib/variants/librnsntt_$lib.so)
   echo "== $tag" >&2
-  env "${env[@]}" timeout -k 10 300 python3 bench.py --no-cpu-baseline "$@" > $OUT/$tag.json 2> $OUT/$tag.err
+  env "${env[@]}" timeout -k 10 300 python3 bench.py --full --no-cpu-baseline "$@" > $OUT/$tag.json 2> $OUT/$tag.err
   local rc=$?; echo "bench $tag rc=$rc" >&2; [ $rc -eq 0 ] || exit $rc
   for pass in "sq:SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAVES" \
               "fetch:FETCH_SIZE" "write:WRITE_SIZE"; do

@@ -13,7 +13,7 @@ tail -1 $O/pytest.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke rc=$?"; tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
 tools/gpu_headline.sh || exit 1
-run() { local name=$1; shift; timeout -k 10 400 python3 bench.py "$@" > $O/$name.json 2> $O/$name.err || { echo "$name rc=$?"; tail -5 $O/$name.err; exit 1; }; echo "$name $(head -c 120 $O/$name.json)"; }
+run() { local name=$1; shift; timeout -k 10 400 python3 bench.py --full "$@" > $O/$name.json 2> $O/$name.err || { echo "$name rc=$?"; tail -5 $O/$name.err; exit 1; }; echo "$name $(head -c 120 $O/$name.json)"; }
 run ctmul128 --workload ctmul --ct-batch 128 --steps 10 --warmup 2 --no-cpu-baseline
 run cfg4 --workload ctmul --ct-batch 1024 --steps 4 --warmup 1
 run cfg3 --workload ctmul --log-n 14 --limbs 8 --ct-batch 1024 --steps 10 --warmup 2

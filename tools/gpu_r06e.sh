@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r06e; mkdir -p $O
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest.log 2>&1 || { echo "pytest rc=$?"; tail -30 $O/pytest.log; exit 1; }
 tail -2 $O/pytest.log
-run() { local name=$1; shift; timeout -k 10 400 python3 bench.py "$@" > $O/$name.json 2> $O/$name.err || { echo "$name rc=$?"; tail -5 $O/$name.err; exit 1; }; echo "$name $(head -c 160 $O/$name.json)"; }
+run() { local name=$1; shift; timeout -k 10 400 python3 bench.py --full "$@" > $O/$name.json 2> $O/$name.err || { echo "$name rc=$?"; tail -5 $O/$name.err; exit 1; }; echo "$name $(head -c 160 $O/$name.json)"; }
 run ctmul128 --workload ctmul --ct-batch 128 --steps 10 --warmup 2 --no-cpu-baseline
 run cfg4 --workload ctmul --ct-batch 1024 --steps 4 --warmup 1
 run cfg3 --workload ctmul --log-n 14 --limbs 8 --ct-batch 1024 --steps 10 --warmup 2

@@ -8,7 +8,7 @@ LOG=gpurun_out/power_$TAG.log
 rocm-smi --showpowercap --showmaxpower > $LOG 2>&1
 echo "== idle" >> $LOG
 rocm-smi --showpower --showclocks >> $LOG 2>&1
-timeout -k 10 300 python3 bench.py --no-cpu-baseline "$@" > gpurun_out/power_$TAG.json 2> gpurun_out/power_$TAG.err &
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline "$@" > ${LOG%.log}.json 2> ${LOG%.log}.err &
 PID=$!
 sleep ${WAIT:-12}
 for i in $(seq 1 ${SAMPLES:-8}); do
