@@ -322,6 +322,26 @@ int rnt_ct_mul_relin_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0,
 int rnt_ct_rotate(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0,
                   const rnt_buf* c1, int32_t k, const rnt_buf* key_a,
                   const rnt_buf* key_b);
+/* The diagonal-method linear transform: for every ciphertext of the batch,
+ *   out = sum_t diag[t] * rotate_ciphertext((c0, c1), steps[t]; key t),
+ * word for word the composition rnt_ct_rotate -> coefficient-domain product
+ * with diag[t] -> rnt_add.  c0, c1: coefficient domain; out0/out1 coefficient
+ * domain on return (out0 == c0 and out1 == c1 allowed; any other aliasing of
+ * an output -> RNT_ERR_BAD_ARGUMENT).  diag: n_terms polys, NTT domain (an
+ * rnt_ntt_fwd result); poly t multiplies every ciphertext.  keys_a/keys_b:
+ * n_terms * L prepared polys, term t's gadget key at [t L, (t + 1) L).  A term
+ * with steps[t] == 0 is diag[t] * (c0, c1) without a key-switch (its key slot
+ * is ignored; the key buffers may be NULL when every step is 0).  Where the
+ * four-step key-switch runs the terms share its accumulators: one pair of
+ * inverse column passes per chunk, the plaintext applied in the NTT domain. */
+int rnt_ct_linear(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                  const int32_t* steps, size_t n_terms, const rnt_buf* diag,
+                  const rnt_buf* keys_a, const rnt_buf* keys_b);
+/* polys [src_first, src_first + count) of src -> [dst_first, ...) of dst (same
+ * context; dst takes src's domain, which must equal dst's unless the copy
+ * covers all of dst).  A range outside either batch -> RNT_ERR_BAD_ARGUMENT. */
+int rnt_copy_polys(rnt_buf* dst, size_t dst_first, const rnt_buf* src, size_t src_first,
+                   size_t count);
 /* rescale_ciphertext (engine.rs:263-282): both components onto the same
  * dropped basis. */
 int rnt_ct_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0,

@@ -2251,6 +2251,12 @@ extern "C" int rnt_ct_mul_relin_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_
   return rc;
 }
 
+// The rotation's body (arguments checked by the caller).  The keys are read
+// through their data pointer and limb stride only, so rnt_ct_linear passes one
+// term's slice of a packed key set as a view.
+static int ct_rotate_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                          int32_t kk, const rnt_buf* key_a, const rnt_buf* key_b);
+
 extern "C" int rnt_ct_rotate(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
                              int32_t kk, const rnt_buf* key_a, const rnt_buf* key_b) {
   const rnt_buf* all[4] = {out0, out1, c0, c1};
@@ -2260,6 +2266,11 @@ extern "C" int rnt_ct_rotate(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
     if (int rc = check_same(all[0], all[i], "rnt_ct_rotate")) return rc;
   if (int rc = check_key(c0, key_a, key_b)) return rc;
   if (out0 == out1) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_rotate: out0 aliases out1");
+  return ct_rotate_body(out0, out1, c0, c1, kk, key_a, key_b);
+}
+
+static int ct_rotate_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                          int32_t kk, const rnt_buf* key_a, const rnt_buf* key_b) {
   if (int rc = set_device(c0->ctx)) return rc;
   rnt::Launch k = launch_for(c0);
   const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
@@ -2317,6 +2328,304 @@ extern "C" int rnt_ct_rotate(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
   }
   sview.data = nullptr;
   out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// linear transform: out = sum_t diag_t * rotate_ciphertext(ct, steps[t])
+// ---------------------------------------------------------------------------
+namespace {
+
+// `rows` runs of `run_words` contiguous words, dst row r at dst + r dst_ls,
+// src row r at src + r src_ls (strides in words): the polys [first, first +
+// count) of every limb of a [L][B][N] buffer are one such run per limb.
+int copy_rows(const rnt::Launch& k, void* dst, uint64_t dst_ls, const void* src, uint64_t src_ls,
+              uint64_t run_words, size_t rows) {
+  const size_t wb = word_bytes(k.t);
+  if (dst_ls == run_words && src_ls == run_words) {  // contiguous on both sides: one copy
+    run_words *= rows;
+    rows = 1;
+  }
+  for (size_t r = 0; r < rows; ++r)
+    HIP_TRY(hipMemcpyAsync((char*)dst + r * dst_ls * wb, (const char*)src + r * src_ls * wb, run_words * wb,
+                           hipMemcpyDeviceToDevice, k.s),
+            "hipMemcpyAsync");
+  return RNT_OK;
+}
+
+// Forward / inverse transform in place of a raw [k.L][k.B][N] block at limb
+// stride ls: the launches of rnt_ntt_fwd / rnt_ntt_inv.
+int fwd_raw(const rnt::Launch& k, void* p, uint64_t ls) {
+  if (use_mf(k)) {
+    LAUNCH(k.t, rnt::K_MF_NTT_FWD, rnt::launch_mf_ntt(k, 0, p, ls), "MFMA forward transform");
+  } else if (rnt::whole_ok(k.t, 0)) {
+    LAUNCH(k.t, rnt::K_WHOLE_FWD, rnt::launch_whole(k, 0, p, p, nullptr, ls), "whole-plane forward");
+  } else {
+    LAUNCH(k.t, rnt::K_COL_FWD, rnt::launch_col_fwd(k, p, p, nullptr, nullptr, ls, ls), "column forward");
+    LAUNCH(k.t, rnt::K_ROW_FWD, rnt::launch_row(k, 0, p, nullptr, ls), "row forward");
+  }
+  return RNT_OK;
+}
+int inv_raw(const rnt::Launch& k, void* p, uint64_t ls) {
+  if (use_mf(k)) {
+    LAUNCH(k.t, rnt::K_MF_NTT_INV, rnt::launch_mf_ntt(k, 1, p, ls), "MFMA inverse transform");
+  } else if (rnt::whole_ok(k.t, 1)) {
+    LAUNCH(k.t, rnt::K_WHOLE_INV, rnt::launch_whole(k, 1, p, p, nullptr, ls), "whole-plane inverse");
+  } else {
+    LAUNCH(k.t, rnt::K_ROW_INV, rnt::launch_row(k, 1, p, nullptr, ls), "row inverse");
+    LAUNCH(k.t, rnt::K_COL_INV, rnt::launch_col_inv(k, p, ls, p, ls, 0, nullptr), "column inverse");
+  }
+  return RNT_OK;
+}
+
+// z (+)= x^ (.) m_t for one term: x^ a [k.L][k.B][N] NTT-domain block, m_t
+// plane t of the Montgomery-form plaintexts dm ([L][n_terms][N]).
+int lin_mac(const rnt::Launch& k, void* z, const void* x, const char* dm, size_t t, size_t n_terms, bool accum) {
+  const size_t n = k.t->n, wb = word_bytes(k.t);
+  LAUNCH(k.t, rnt::K_ELEMENTWISE,
+         rnt::launch_bcast_mul(k, 0, z, x, dm + t * n * wb, (uint64_t)n_terms * n, accum), "plaintext product");
+  return RNT_OK;
+}
+
+// The whole-plane rings (ks_whole_ok: no U0/U1 for the terms to share): the
+// composition itself -- every term's rotation through the whole-plane
+// key-switch, its product with the plaintext taken in the NTT domain and
+// summed there, one inverse of each sum.
+int ct_linear_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                       const int32_t* steps, size_t n_terms, const char* dm, const rnt_buf* keys_a,
+                       const rnt_buf* keys_b, void* ws) {
+  rnt::Launch k = launch_for(c0);
+  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
+  const size_t pw = L * B * n * wb;
+  const uint64_t ls = limb_stride(c0);
+  char* Z[2] = {(char*)ws, (char*)ws + pw};
+  char* R[2] = {(char*)ws + 2 * pw, (char*)ws + 3 * pw};
+  rnt_buf rv[2], kv[2];
+  for (int o = 0; o < 2; ++o) {
+    rv[o].ctx = c0->ctx;
+    rv[o].n_polys = B;
+    rv[o].data = R[o];
+    rv[o].owns = false;
+  }
+  const rnt_buf* src[2] = {c0, c1};
+  for (size_t t = 0; t < n_terms; ++t) {
+    if (steps[t] == 0) {
+      for (int o = 0; o < 2; ++o)
+        if (int rc = copy_rows(k, R[o], ls, src[o]->data, ls, ls, L)) return rc;
+    } else {
+      const rnt_buf* keys[2] = {keys_a, keys_b};
+      for (int o = 0; o < 2; ++o) {
+        kv[o].ctx = c0->ctx;
+        kv[o].n_polys = keys[o]->n_polys;  // (the packed set's limb stride)
+        kv[o].data = (char*)keys[o]->data + t * L * n * wb;
+        kv[o].in_ntt = 1;
+        kv[o].owns = false;
+      }
+      if (int rc = ct_rotate_body(&rv[0], &rv[1], c0, c1, steps[t], &kv[0], &kv[1])) return rc;
+    }
+    for (int o = 0; o < 2; ++o) {
+      if (int rc = fwd_raw(k, R[o], ls)) return rc;
+      if (int rc = lin_mac(k, Z[o], R[o], dm, t, n_terms, t != 0)) return rc;
+    }
+  }
+  rnt_buf* out[2] = {out0, out1};
+  for (int o = 0; o < 2; ++o) {
+    if (int rc = inv_raw(k, Z[o], ls)) return rc;
+    if (int rc = copy_rows(k, out[o]->data, ls, Z[o], ls, ls, L)) return rc;
+  }
+  return RNT_OK;
+}
+
+// The four-step key-switch: chunks outside, terms inside.  Per chunk the
+// workspace holds (chunk planes of L bc N words) X0 X1 (the chunk gathered,
+// more than one chunk only) | SIG1 | SEED | NT0 NT1 Z0 Z1 (a step-0 term only)
+// | S U0 U1.  Every nonzero term: sigma(c1) -> decomposition -> rows with the
+// seed NTT(sigma(c0)) 2^-w, the plaintext row and (after the first)
+// accumulation into U0/U1; the step-0 terms' products are summed in the NTT
+// domain, inverted and added by the chunk's two inverse column passes.
+int ct_linear_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                    const int32_t* steps, size_t n_terms, const char* dm, const rnt_buf* keys_a,
+                    const rnt_buf* keys_b, char* ws, size_t bc, bool any_zero, bool any_rot) {
+  rnt::Launch k = launch_for(c0);
+  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
+  const size_t pw = L * bc * n * wb;
+  const uint64_t full_ls = limb_stride(c0);
+  const bool multi = bc < B;
+  char* p = ws;
+  auto take = [&](bool on) {
+    char* r = on ? p : nullptr;
+    if (on) p += pw;
+    return r;
+  };
+  char* X[2] = {take(multi), take(multi)};
+  char* SIG1 = take(true);
+  char* SEED = take(true);
+  char* NT[2] = {take(any_zero), take(any_zero)};
+  char* Z[2] = {take(any_zero), take(any_zero)};
+  char* KS = p;
+  const rnt_buf* src[2] = {c0, c1};
+  rnt_buf* out[2] = {out0, out1};
+  const uint64_t two_n = 2 * (uint64_t)n;
+  for (size_t p0 = 0; p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    rnt::Launch kc = k;
+    kc.B = c;
+    const uint64_t cls = (uint64_t)c * n;
+    char* S = KS;
+    char* U[2] = {S + L * L * c * n * wb, S + (L * L + L) * c * n * wb};
+    const char* x[2];
+    for (int o = 0; o < 2; ++o) {
+      x[o] = (const char*)src[o]->data + p0 * n * wb;
+      if (multi) {
+        if (int rc = copy_rows(kc, X[o], cls, x[o], full_ls, cls, L)) return rc;
+        x[o] = X[o];
+      }
+    }
+    if (any_zero) {
+      bool first = true;
+      for (int o = 0; o < 2; ++o) {
+        if (int rc = copy_rows(kc, NT[o], cls, x[o], multi ? cls : full_ls, cls, L)) return rc;
+        if (int rc = fwd_raw(kc, NT[o], cls)) return rc;
+      }
+      for (size_t t = 0; t < n_terms; ++t) {
+        if (steps[t] != 0) continue;
+        for (int o = 0; o < 2; ++o)
+          if (int rc = lin_mac(kc, Z[o], NT[o], dm, t, n_terms, !first)) return rc;
+        first = false;
+      }
+      for (int o = 0; o < 2; ++o)
+        if (int rc = inv_raw(kc, Z[o], cls)) return rc;
+    }
+    bool first = true;
+    for (size_t t = 0; t < n_terms; ++t) {
+      if (steps[t] == 0) continue;
+      const uint64_t g = rotation_exponent(steps[t], two_n);
+      LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG1, x[1], g), "automorphism");
+      LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SEED, x[0], g), "automorphism");
+      if (int rc = fwd_raw(kc, SEED, cls)) return rc;
+      LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 0, SEED, SEED, nullptr, 0, false), "seed scale");
+      rnt::KsLin lin;
+      lin.mul = dm + t * n * wb;
+      lin.mul_ls = (uint64_t)n_terms * n;
+      lin.accum = first ? 0u : 1u;
+      const size_t koff = t * L * n * wb;
+      LAUNCH(kc.t, rnt::K_KS_DECOMPOSE, rnt::launch_ks_decompose(kc, S, SIG1, cls), "ks decompose");
+      LAUNCH(kc.t, rnt::K_KS_ROWS,
+             rnt::launch_ks_rows_lin(kc, U[0], U[1], cls, S, (const char*)keys_a->data + koff,
+                                     (const char*)keys_b->data + koff, limb_stride(keys_a), SEED, nullptr, cls,
+                                     lin),
+             "ks rows");
+      first = false;
+    }
+    for (int o = 0; o < 2; ++o) {
+      char* dst = (char*)out[o]->data + p0 * n * wb;
+      if (!any_rot) {
+        if (int rc = copy_rows(kc, dst, full_ls, Z[o], cls, cls, L)) return rc;
+      } else if (!multi) {
+        LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, dst, full_ls, U[o], cls, 1, any_zero ? Z[o] : nullptr),
+               "ks inverse");
+      } else {
+        // (the addend shares the output's limb stride: a chunk-local output)
+        char* tmp = o == 0 ? SEED : SIG1;
+        LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, tmp, cls, U[o], cls, 1, any_zero ? Z[o] : nullptr),
+               "ks inverse");
+        if (int rc = copy_rows(kc, dst, full_ls, tmp, cls, cls, L)) return rc;
+      }
+    }
+  }
+  return RNT_OK;
+}
+
+}  // namespace
+
+extern "C" int rnt_ct_linear(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                             const int32_t* steps, size_t n_terms, const rnt_buf* diag,
+                             const rnt_buf* keys_a, const rnt_buf* keys_b) {
+  const rnt_buf* all[4] = {out0, out1, c0, c1};
+  for (const rnt_buf* b : all)
+    if (int rc = check_buf(b, "rnt_ct_linear")) return rc;
+  if (int rc = check_buf(diag, "rnt_ct_linear")) return rc;
+  if (n_terms == 0) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_linear: no terms");
+  if (!steps) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_linear: null steps");
+  for (int i = 1; i < 4; ++i)
+    if (int rc = check_same(all[0], all[i], "rnt_ct_linear")) return rc;
+  if (diag->ctx != c0->ctx)
+    return fail(RNT_ERR_BASIS_MISMATCH, "rnt_ct_linear: the plaintexts belong to a different basis");
+  if (diag->n_polys != n_terms)
+    return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_linear: %zu plaintexts for %zu terms", diag->n_polys, n_terms);
+  bool any_rot = false, any_zero = false;
+  for (size_t t = 0; t < n_terms; ++t) (steps[t] == 0 ? any_zero : any_rot) = true;
+  const size_t L = c0->ctx->L;
+  if (any_rot || keys_a || keys_b) {
+    if (int rc = check_buf(keys_a, "rnt_ct_linear keys")) return rc;
+    if (int rc = check_buf(keys_b, "rnt_ct_linear keys")) return rc;
+    if (keys_a->ctx != c0->ctx || keys_b->ctx != c0->ctx)
+      return fail(RNT_ERR_BASIS_MISMATCH, "rnt_ct_linear: keys and ciphertext belong to different bases");
+    if (keys_a->n_polys != n_terms * L || keys_b->n_polys != n_terms * L)
+      return fail_fields(RNT_ERR_CHANNEL_COUNT, n_terms * L,
+                         keys_a->n_polys != n_terms * L ? keys_a->n_polys : keys_b->n_polys,
+                         "the key set must hold one poly per term and channel (%zu)", n_terms * L);
+    if (!keys_a->in_ntt || !keys_b->in_ntt)
+      return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_ct_linear: keys must be prepared (rnt_key_prepare)");
+  }
+  if (!diag->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_ct_linear: the plaintexts must be in the NTT domain");
+  if (c0->in_ntt || c1->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_ct_linear: the ciphertext must be in coefficient domain");
+  const rnt_buf* ins[5] = {c0, c1, diag, keys_a, keys_b};
+  if (out0 == out1) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_linear: out0 aliases out1");
+  for (int i = 0; i < 5; ++i) {
+    if ((out0 == ins[i] && i != 0) || (out1 == ins[i] && i != 1))
+      return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_linear: an output aliases an input other than its own component");
+  }
+  if (int rc = set_device(c0->ctx)) return rc;
+  rnt::Launch k = launch_for(c0);
+  const size_t n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
+  const bool composed = rnt::ks_whole_ok(k.t);
+  const size_t bc = composed ? B : ks_chunk(k.t, L, B);
+  const size_t planes = composed ? 4 : (bc < B ? 2 : 0) + 2 + (any_zero ? 4 : 0);
+  const size_t dm_bytes = L * n_terms * n * wb;
+  const size_t need = dm_bytes + planes * L * bc * n * wb + (composed ? 0 : ks_scratch_words(k.t, L, bc) * wb);
+  CallWs ws(out0);
+  if (int rc = ws.get(std::max<size_t>(need, 16))) return rc;
+  // the plaintexts in Montgomery form (m^ 2^w mod q), once per call: a
+  // Montgomery product with them is then the canonical product, and the
+  // key-switch sums keep their single factor 2^-w for the inverse to fold
+  char* dm = (char*)ws.p;
+  rnt::Launch kd = k;
+  kd.B = n_terms;
+  LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kd, 1, dm, diag->data, nullptr, 0, false),
+         "plaintexts to Montgomery form");
+  int rc;
+  if (composed)
+    rc = ct_linear_composed(out0, out1, c0, c1, steps, n_terms, dm, keys_a, keys_b, dm + dm_bytes);
+  else
+    rc = ct_linear_fused(out0, out1, c0, c1, steps, n_terms, dm, keys_a, keys_b, dm + dm_bytes, bc, any_zero,
+                         any_rot);
+  if (rc) return rc;
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
+extern "C" int rnt_copy_polys(rnt_buf* dst, size_t dst_first, const rnt_buf* src, size_t src_first,
+                              size_t count) {
+  if (int rc = check_buf(dst, "rnt_copy_polys")) return rc;
+  if (int rc = check_buf(src, "rnt_copy_polys")) return rc;
+  if (dst->ctx != src->ctx) return fail(RNT_ERR_BASIS_MISMATCH, "rnt_copy_polys: operands belong to different bases");
+  if (dst == src) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_copy_polys: dst aliases src");
+  if (count == 0 || dst_first > dst->n_polys || count > dst->n_polys - dst_first || src_first > src->n_polys ||
+      count > src->n_polys - src_first)
+    return fail(RNT_ERR_BAD_ARGUMENT, "rnt_copy_polys: range outside the batch (%zu+%zu of %zu -> %zu+%zu of %zu)",
+                src_first, count, src->n_polys, dst_first, count, dst->n_polys);
+  const bool whole = count == dst->n_polys;
+  if (!whole && dst->in_ntt != src->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_copy_polys: domain mismatch on a partial copy");
+  if (int rc = set_device(dst->ctx)) return rc;
+  rnt::Launch k = launch_for(dst);
+  const size_t n = k.t->n, wb = word_bytes(k.t);
+  if (int rc = copy_rows(k, (char*)dst->data + dst_first * n * wb, limb_stride(dst),
+                         (const char*)src->data + src_first * n * wb, limb_stride(src), (uint64_t)count * n, k.L))
+    return rc;
+  dst->in_ntt = src->in_ntt;
   return RNT_OK;
 }
 

@@ -305,6 +305,24 @@ hipError_t launch_ks_decompose(const Launch& k, void* S, const void* d, uint64_t
 hipError_t launch_ks_rows(const Launch& k, void* u0, void* u1, uint64_t u_ls, const void* S,
                           const void* key_a, const void* key_b, uint64_t key_ls,
                           const void* init0, const void* init1, uint64_t init_ls);
+// The same for one term of rnt_ct_linear (k_ks_rows<..., LIN>): both sums are
+// multiplied by the plaintext row `mul` (one [N] plane per limb at limb stride
+// mul_ls, Montgomery form m^ 2^w mod q, shared by every poly) before the
+// inverse rows, which are added to u0/u1 when `accum` is set (stored otherwise).
+struct KsLin {
+  const void* mul = nullptr;
+  uint64_t mul_ls = 0;
+  uint32_t accum = 0;
+};
+hipError_t launch_ks_rows_lin(const Launch& k, void* u0, void* u1, uint64_t u_ls, const void* S,
+                              const void* key_a, const void* key_b, uint64_t key_ls,
+                              const void* init0, const void* init1, uint64_t init_ls, const KsLin& lin);
+// Pointwise products over k.L x k.B x N contiguous words (k_bcast_mul).
+// kind 0: out = x (.) m 2^-w, m one [N] plane per limb at limb stride m_ls
+// broadcast over the batch (m null: out = x 2^-w), added to out with accum;
+// kind 1: out = x 2^w mod q (canonical -> Montgomery form).  out may be x.
+hipError_t launch_bcast_mul(const Launch& k, int kind, void* out, const void* x, const void* m,
+                            uint64_t m_ls, bool accum);
 // The whole-plane key-switch at 2^10 <= N <= 2^13 (k_ks_whole, one launch,
 // no S): out0 = INV(sum_i NTT(src_i mod q_j) (.) key_b[i][j] + init0) (+ add0),
 // out1 likewise with key_a; src is [k.src_limbs()][k.B][N] coefficient-domain

@@ -994,13 +994,33 @@ __device__ __forceinline__ uint32_t mac2_lazy(uint32_t acc, uint32_t x0, uint32_
 // slot, and the accumulate reads them back from LDS: one global round trip
 // per source limb instead of three (S, then key_b, then key_a), and 2 key
 // words per thread instead of 2E (A/B: profiles/r02_ab_ks_rows.txt).
-template <class W, int LOG_C, int NP>
+//
+// LIN (rnt_ct_linear's terms): before the inverse rows both accumulators are
+// multiplied by a plaintext's NTT row -- lin.mul points at the term's plane of
+// a [limb][..][N] array of Montgomery-form words (m^ 2^w mod q, limb stride
+// lin.mul_ls), the same row for every poly, so the product leaves the sum's
+// single factor 2^-w in place -- and with lin.accum (uniform) the inverse rows
+// are added to u0/u1 instead of stored: the terms of a sum share one pair of
+// accumulators and one pair of inverse column passes.  The row is read from
+// global memory once per accumulator (the second read hits cache; held across
+// the first inverse it would cost E more live registers).  Without LIN the
+// argument is an empty struct and the kernel the one it was before it.
+template <class W, bool LIN>
+struct KsLinArgs {};
+template <class W>
+struct KsLinArgs<W, true> {
+  const W* mul;
+  uint64_t mul_ls;
+  uint32_t accum;
+};
+template <class W, int LOG_C, int NP, bool LIN = false>
 __global__ void __launch_bounds__(RowGeo<LOG_C>::THREADS, (KsCfg<W, LOG_C, NP>::KREG ? RNT_KS_KREG_WAVES : sizeof(W) == 4 ? RNT_KS_ROWS_WAVES : 1))
 k_ks_rows(W* __restrict__ u0, W* __restrict__ u1, const W* __restrict__ S,
           const W* __restrict__ key_a, const W* __restrict__ key_b, uint64_t key_ls,
           const W* __restrict__ init0, const W* __restrict__ init1, uint64_t init_ls,
           TabPtrs<W> tp, uint32_t log_n, uint32_t L, uint32_t B, uint64_t ls, uint32_t pgroups,
-          uint32_t nblocks, const W* __restrict__ d2hat, uint64_t d2hat_ls) {
+          uint32_t nblocks, const W* __restrict__ d2hat, uint64_t d2hat_ls, KsLinArgs<W, LIN> lin) {
+  if constexpr (LIN) d2hat = nullptr;  // no ct-mul diagonal in a linear transform's term
   using G = RowGeo<LOG_C>;
   constexpr int E = G::E;
   constexpr int C = G::C;
@@ -1389,13 +1409,37 @@ k_ks_rows(W* __restrict__ u0, W* __restrict__ u1, const W* __restrict__ S,
   asm volatile("" : "+v"(xq.tau), "+v"(pq));
   const uint64_t oq = (uint64_t)j * ls + (uint64_t)pq * N + rowoff;
   const uint32_t b0q = G::base(xq.tau, G::BB0);
+  // (LIN lives inside this loop as discarded statements: written as a block
+  // of its own in front of it, the code of the existing instantiations -- and
+  // of k_row and k_tensor_rows -- moved.  The u64 LIN rows of 128 words and
+  // more outgrow the compiler's full-unroll limit here and keep their two
+  // accumulators in scratch, 272 bytes a lane written once and read once.)
 #pragma unroll
   for (int o = 0; o < 2; ++o) {
     W v[1][E];
 #pragma unroll
     for (int e = 0; e < E; ++e) v[0][e] = kLazy ? csub<W>(acc[o][e], lc.q) : acc[o][e];
+    if constexpr (LIN) {
+      // the plaintext's row at this thread's accumulator positions (the seed
+      // loads' pattern; no poly index: one row serves the batch)
+      const W* mr = lin.mul + (uint64_t)j * lin.mul_ls + rowoff;
+#pragma unroll
+      for (int e = 0; e < E; ++e)
+        v[0][e] = mont_mul<W>(v[0][e], mr[bl + ((uint32_t)e << G::BBL)], lc.q, lc.qinv);
+    }
     xf_inv<G, W, 1>(v, xq, lds, itw, mod_of(lc));
     W* uo = o == 0 ? u0 : u1;
+    if constexpr (LIN) {
+      // a later term of the sum: add the rows already there (accum is
+      // uniform; the loads are issued together, ahead of the adds)
+      if (rp.active && lin.accum) {
+        W old[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) old[e] = uo[oq + b0q + ((uint32_t)e << G::BB0)];
+#pragma unroll
+        for (int e = 0; e < E; ++e) v[0][e] = add_mod<W>(old[e], v[0][e], lc.q);
+      }
+    }
     if (rp.active) {
 #pragma unroll
       for (int e = 0; e < E; ++e) uo[oq + b0q + ((uint32_t)e << G::BB0)] = v[0][e];
@@ -1662,6 +1706,65 @@ k_elementwise(W* __restrict__ out, const W* __restrict__ a, const W* __restrict_
     *reinterpret_cast<uint4*>(out + g) = o;
   } else {
     out[g] = elementwise_op<W, OP>(a[g], OP == 2 ? (W)0 : b[g], lc);
+  }
+}
+
+// Pointwise products of rnt_ct_linear over a batch [L][B][N] (limb stride B N
+// words), grid as k_elementwise.  KIND 0: out = x (.) m 2^-w (Montgomery
+// product) with m one plane per limb (limb stride m_ls, the same plane for
+// every poly of the batch), or x 2^-w where m is null (the key-switch seed
+// scale); with `accum` (uniform) the product is added to out.  KIND 1:
+// out = x 2^w mod q (a canonical plaintext into Montgomery form, so that a
+// later Montgomery product with it is the canonical product).  out may be x.
+template <class W, int KIND, bool VEC>
+__global__ void __launch_bounds__(256)
+k_bcast_mul(W* out, const W* x, const W* __restrict__ m, TabPtrs<W> tp, uint32_t log_n,
+            uint64_t limb_words, uint64_t m_ls, uint32_t accum) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint32_t l = blockIdx.y;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= limb_words) return;
+  const LimbConst<W> lc = tp.lc[l];
+  const uint64_t g = (uint64_t)l * limb_words + i;
+  const uint64_t mi = (uint64_t)l * m_ls + (i & ((1ull << log_n) - 1));  // V divides N: one plane
+  W xv[V], mv[V], ov[V], r[V];
+  if constexpr (VEC) {
+    const uint4 xa = *reinterpret_cast<const uint4*>(x + g);
+    __builtin_memcpy(xv, &xa, 16);
+  } else {
+    xv[0] = x[g];
+  }
+#pragma unroll
+  for (int v = 0; v < V; ++v) mv[v] = (W)1;
+  if (KIND == 0 && m != nullptr) {
+    if constexpr (VEC) {
+      const uint4 ma = *reinterpret_cast<const uint4*>(m + mi);
+      __builtin_memcpy(mv, &ma, 16);
+    } else {
+      mv[0] = m[mi];
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    if constexpr (KIND == 0) r[v] = mont_mul<W>(xv[v], mv[v], lc.q, lc.qinv);
+    else r[v] = shoup_mul<W>(xv[v], lc.rmod, lc.rmod_p, lc.q);
+  }
+  if (KIND == 0 && accum) {
+    if constexpr (VEC) {
+      const uint4 oa = *reinterpret_cast<const uint4*>(out + g);
+      __builtin_memcpy(ov, &oa, 16);
+    } else {
+      ov[0] = out[g];
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) r[v] = add_mod<W>(ov[v], r[v], lc.q);
+  }
+  if constexpr (VEC) {
+    uint4 o;
+    __builtin_memcpy(&o, r, 16);
+    *reinterpret_cast<uint4*>(out + g) = o;
+  } else {
+    out[g] = r[0];
   }
 }
 
@@ -2072,6 +2175,31 @@ static hipError_t elementwise_t(const Launch& k, int op, void* out, const void* 
   return hipGetLastError();
 }
 
+template <class W>
+static hipError_t bcast_mul_t(const Launch& k, int kind, void* out, const void* x, const void* m,
+                              uint64_t m_ls, bool accum) {
+  const uint64_t N = 1ull << k.t->log_n;
+  const uint64_t limb_words = (uint64_t)k.B * N;
+  if (limb_words == 0 || k.L == 0) return hipSuccess;
+  constexpr int V = 16 / (int)sizeof(W);
+  // 16-byte accesses: whole vectors within a plane, every plane 16-byte aligned
+  const bool vec = N % V == 0 && m_ls % V == 0 && ((uintptr_t)out | (uintptr_t)x | (uintptr_t)m) % 16 == 0;
+  const uint64_t per = vec ? limb_words / V : limb_words;
+  const uint64_t bx = (per + 255) / 256;
+  if (bx > 0x7fffffffull || k.L > 65535) return hipErrorInvalidConfiguration;
+  const dim3 grid((unsigned)bx, (unsigned)k.L);
+#define RNT_BM(KIND, VEC)                                                                        \
+  hipLaunchKernelGGL((k_bcast_mul<W, KIND, VEC>), grid, dim3(256), 0, k.s, (W*)out, (const W*)x, \
+                     (const W*)m, tab_ptrs<W>(k.t), k.t->log_n, limb_words, m_ls, accum ? 1u : 0u)
+  if (kind == 0) {
+    if (vec) RNT_BM(0, true); else RNT_BM(0, false);
+  } else {
+    if (vec) RNT_BM(1, true); else RNT_BM(1, false);
+  }
+#undef RNT_BM
+  return hipGetLastError();
+}
+
 // Clone: 4 x 16 B per lane, all four loads issued before the stores.
 __global__ void __launch_bounds__(256)
 k_copy16(uint4* __restrict__ dst, const uint4* __restrict__ src, uint64_t n16) {
@@ -2249,7 +2377,8 @@ static hipError_t ks_decompose_t(const Launch& k, void* S, const void* d, uint64
 template <class W, int LOG_C, int NP>
 static hipError_t ks_rows_launch(const Launch& k, void* u0, void* u1, uint64_t ls, const void* S,
                                  const void* key_a, const void* key_b, uint64_t key_ls,
-                                 const void* init0, const void* init1, uint64_t init_ls) {
+                                 const void* init0, const void* init1, uint64_t init_ls,
+                                 const KsLin* lin) {
   using G = RowGeo<LOG_C>;
   constexpr int KROWS = G::RPW / NP;
   constexpr size_t KPADB = (size_t)ks_kpad_words<W>(G::C) * sizeof(W);
@@ -2268,13 +2397,27 @@ static hipError_t ks_rows_launch(const Launch& k, void* u0, void* u1, uint64_t l
   // (the kernel's KDOUBLE rule)
   const size_t lds = KsCfg<W, LOG_C, NP>::LDS_BYTES;
   static_assert(KsCfg<W, LOG_C, NP>::KPAD * sizeof(W) == KPADB, "key row pad");
+  if (lin != nullptr) {
+    // rnt_ct_linear's term: the same grid, the plaintext row and the
+    // accumulate flag in place of the ct-mul diagonal
+    if (k.d2hat != nullptr || lin->mul == nullptr) return hipErrorInvalidValue;
+    hipError_t e = allow_lds(k_ks_rows<W, LOG_C, NP, true>, lds);
+    if (e != hipSuccess) return e;
+    const KsLinArgs<W, true> la{(const W*)lin->mul, lin->mul_ls, lin->accum};
+    hipLaunchKernelGGL((k_ks_rows<W, LOG_C, NP, true>), dim3(launched), dim3(G::THREADS), lds, k.s,
+                       (W*)u0, (W*)u1, (const W*)S, (const W*)key_a, (const W*)key_b, key_ls,
+                       (const W*)init0, (const W*)init1, init_ls, tab_ptrs<W>(k.t), g.log_n,
+                       (uint32_t)k.src_limbs(), (uint32_t)k.B, ls, (uint32_t)pgroups,
+                       (uint32_t)blocks, (const W*)nullptr, (uint64_t)0, la);
+    return hipGetLastError();
+  }
   hipError_t e = allow_lds(k_ks_rows<W, LOG_C, NP>, lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_ks_rows<W, LOG_C, NP>), dim3(launched), dim3(G::THREADS), lds, k.s,
                      (W*)u0, (W*)u1, (const W*)S, (const W*)key_a, (const W*)key_b, key_ls,
                      (const W*)init0, (const W*)init1, init_ls, tab_ptrs<W>(k.t), g.log_n,
                      (uint32_t)k.src_limbs(), (uint32_t)k.B, ls, (uint32_t)pgroups,
-                     (uint32_t)blocks, (const W*)k.d2hat, k.d2hat_ls);
+                     (uint32_t)blocks, (const W*)k.d2hat, k.d2hat_ls, KsLinArgs<W, false>{});
   return hipGetLastError();
 }
 
@@ -2287,7 +2430,8 @@ static hipError_t ks_rows_launch(const Launch& k, void* u0, void* u1, uint64_t l
 template <class W, int LOG_C>
 static hipError_t ks_rows_pick(const Launch& k, void* u0, void* u1, uint64_t ls, const void* S,
                                const void* key_a, const void* key_b, uint64_t key_ls,
-                               const void* init0, const void* init1, uint64_t init_ls) {
+                               const void* init0, const void* init1, uint64_t init_ls,
+                               const KsLin* lin) {
   using G = RowGeo<LOG_C>;
   constexpr int RPW = G::RPW;
   const Geom g = geom_for(k.t->log_n);
@@ -2317,7 +2461,7 @@ static hipError_t ks_rows_pick(const Launch& k, void* u0, void* u1, uint64_t ls,
   }
 #define RNT_NP(V) \
   if (np == (V) && RPW % (V) == 0) \
-    return ks_rows_launch<W, LOG_C, (RPW % (V) == 0 ? (V) : RPW)>(k, u0, u1, ls, S, key_a, key_b, key_ls, init0, init1, init_ls);
+    return ks_rows_launch<W, LOG_C, (RPW % (V) == 0 ? (V) : RPW)>(k, u0, u1, ls, S, key_a, key_b, key_ls, init0, init1, init_ls, lin);
   if constexpr (sizeof(W) == 4 && G::C >= 64 && RPW > 1) {
     RNT_NP(1)
     if constexpr (LOG_C == 8 || LOG_C == 9) {
@@ -2327,16 +2471,17 @@ static hipError_t ks_rows_pick(const Launch& k, void* u0, void* u1, uint64_t ls,
     }
   }
 #undef RNT_NP
-  return ks_rows_launch<W, LOG_C, RPW>(k, u0, u1, ls, S, key_a, key_b, key_ls, init0, init1, init_ls);
+  return ks_rows_launch<W, LOG_C, RPW>(k, u0, u1, ls, S, key_a, key_b, key_ls, init0, init1, init_ls, lin);
 }
 
 template <class W>
 static hipError_t ks_rows_t(const Launch& k, void* u0, void* u1, uint64_t ls, const void* S,
                             const void* key_a, const void* key_b, uint64_t key_ls,
-                            const void* init0, const void* init1, uint64_t init_ls) {
+                            const void* init0, const void* init1, uint64_t init_ls,
+                            const KsLin* lin) {
   const Geom g = geom_for(k.t->log_n);
 #define RNT_L(C) \
-  return ks_rows_pick<W, C>(k, u0, u1, ls, S, key_a, key_b, key_ls, init0, init1, init_ls)
+  return ks_rows_pick<W, C>(k, u0, u1, ls, S, key_a, key_b, key_ls, init0, init1, init_ls, lin)
   RNT_DISPATCH_LOGC(g.log_c, RNT_L)
 #undef RNT_L
   return hipErrorInvalidValue;
@@ -2601,8 +2746,19 @@ hipError_t launch_ks_decompose(const Launch& k, void* S, const void* d, uint64_t
 hipError_t launch_ks_rows(const Launch& k, void* u0, void* u1, uint64_t u_ls, const void* S,
                           const void* key_a, const void* key_b, uint64_t key_ls,
                           const void* init0, const void* init1, uint64_t init_ls) {
-  RNT_WIDE(ks_rows_t<uint32_t>(k, u0, u1, u_ls, S, key_a, key_b, key_ls, init0, init1, init_ls),
-           ks_rows_t<uint64_t>(k, u0, u1, u_ls, S, key_a, key_b, key_ls, init0, init1, init_ls));
+  RNT_WIDE(ks_rows_t<uint32_t>(k, u0, u1, u_ls, S, key_a, key_b, key_ls, init0, init1, init_ls, nullptr),
+           ks_rows_t<uint64_t>(k, u0, u1, u_ls, S, key_a, key_b, key_ls, init0, init1, init_ls, nullptr));
+}
+hipError_t launch_ks_rows_lin(const Launch& k, void* u0, void* u1, uint64_t u_ls, const void* S,
+                              const void* key_a, const void* key_b, uint64_t key_ls,
+                              const void* init0, const void* init1, uint64_t init_ls, const KsLin& lin) {
+  RNT_WIDE(ks_rows_t<uint32_t>(k, u0, u1, u_ls, S, key_a, key_b, key_ls, init0, init1, init_ls, &lin),
+           ks_rows_t<uint64_t>(k, u0, u1, u_ls, S, key_a, key_b, key_ls, init0, init1, init_ls, &lin));
+}
+hipError_t launch_bcast_mul(const Launch& k, int kind, void* out, const void* x, const void* m,
+                            uint64_t m_ls, bool accum) {
+  RNT_WIDE(bcast_mul_t<uint32_t>(k, kind, out, x, m, m_ls, accum),
+           bcast_mul_t<uint64_t>(k, kind, out, x, m, m_ls, accum));
 }
 template <class W>
 static hipError_t ks_whole_t(const Launch& k, void* out0, void* out1, uint64_t out_ls, const void* src,

@@ -41,6 +41,8 @@ __all__ = [
     "mul_ciphertexts_gadget",
     "mul_ciphertexts_gadget_rescale",
     "rotate_ciphertext",
+    "RnsGadgetKeySet",
+    "linear_transform",
     "rescale_ciphertext",
     "Plaintext",
     "CkksEncoder",
@@ -443,6 +445,15 @@ class RnsPoly:
         check(load().rnt_copy(p._h, self._h))
         return p
 
+    def copy_polys(self, src: "RnsPoly", dst_first: int = 0, src_first: int = 0,
+                   count: Optional[int] = None) -> "RnsPoly":
+        """Polys ``src_first .. src_first+count-1`` of ``src`` into this batch
+        from ``dst_first`` on, device to device (rnt_copy_polys); ``count``
+        defaults to the rest of ``src``."""
+        n = src.n_polys - int(src_first) if count is None else int(count)
+        check(load().rnt_copy_polys(self._h, int(dst_first), src._h, int(src_first), n))
+        return self
+
     # -- domain conversion (poly.rs:136-166) --------------------------------
     def to_ntt_domain(self) -> None:
         check(load().rnt_ntt_fwd(self._h))
@@ -607,6 +618,56 @@ def rotate_ciphertext(ct: Ciphertext, rotk: RnsGadgetKey) -> Ciphertext:
     check(load().rnt_ct_rotate(out0.handle, out1.handle, ct.c0.handle, ct.c1.handle,
                                int(rotk.rotation or 0), rotk.a.handle, rotk.b.handle))
     return Ciphertext(out0, out1, ct.logp, ct.logq)
+
+
+class RnsGadgetKeySet:
+    """The gadget keys of a linear transform's terms, packed on the device as
+    rnt_ct_linear reads them: term t's L key polys at ``[t L, (t + 1) L)`` of
+    ``a`` / ``b`` (rnt_copy_polys, no host round trip).  ``keys[t]`` is a
+    prepared :class:`RnsGadgetKey` whose ``rotation`` is the term's step, or
+    None for a step-0 term (its slot stays zero and is never read)."""
+
+    def __init__(self, keys: Sequence[Optional[RnsGadgetKey]], basis: Optional[RnsBasis] = None):
+        keys = list(keys)
+        if not keys:
+            raise ValueError("RnsGadgetKeySet: no terms")
+        first = next((k for k in keys if k is not None), None)
+        if first is None and basis is None:
+            raise ValueError("RnsGadgetKeySet: a set of step-0 terms needs the basis")
+        self.basis = basis if basis is not None else first.a.basis
+        self.steps = [0 if k is None else int(k.rotation or 0) for k in keys]
+        L = self.basis.channel_count()
+        self.a = self.b = None
+        if first is not None:
+            self.a = RnsPoly(self.basis, len(keys) * L)
+            self.b = RnsPoly(self.basis, len(keys) * L)
+            # (zero-filled coefficient-domain buffers; a zero poly is zero in
+            # both domains, so the slots written below decide nothing else)
+            self.a.to_ntt_domain()
+            self.b.to_ntt_domain()
+            for t, k in enumerate(keys):
+                if k is not None:
+                    self.a.copy_polys(k.a, t * L, 0, L)
+                    self.b.copy_polys(k.b, t * L, 0, L)
+
+    def __len__(self) -> int:
+        return len(self.steps)
+
+
+def linear_transform(ct: Ciphertext, diag: RnsPoly, keyset: RnsGadgetKeySet,
+                     out: Optional[Ciphertext] = None) -> Ciphertext:
+    """``sum_t diag[t] * rotate_ciphertext(ct, keyset.steps[t])`` for every
+    ciphertext of the batch (rnt_ct_linear): ``diag`` holds one NTT-domain
+    plaintext poly per term.  ``out`` may be ``ct`` itself (in place)."""
+    basis = ct.c0.basis
+    if out is None:
+        out = Ciphertext(ct.c0._like(basis), ct.c0._like(basis), ct.logp, ct.logq)
+    steps = (ctypes.c_int32 * len(keyset.steps))(*keyset.steps)
+    check(load().rnt_ct_linear(out.c0.handle, out.c1.handle, ct.c0.handle, ct.c1.handle, steps,
+                               len(keyset.steps), diag.handle,
+                               keyset.a.handle if keyset.a is not None else None,
+                               keyset.b.handle if keyset.b is not None else None))
+    return out
 
 
 def mul_ciphertexts_gadget_rescale(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsGadgetKey) -> Ciphertext:

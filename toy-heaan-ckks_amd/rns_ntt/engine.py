@@ -23,8 +23,8 @@ from typing import Optional
 
 import numpy as np
 
-from . import (Ciphertext, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsPoly, mul_ciphertexts_gadget,
-               rescale_ciphertext, rotate_ciphertext)
+from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsGadgetKeySet, RnsPoly,
+               linear_transform, mul_ciphertexts_gadget, rescale_ciphertext, rotate_ciphertext)
 
 
 @dataclass
@@ -156,6 +156,36 @@ class CkksEngine:
     mul_ciphertexts_gadget = staticmethod(mul_ciphertexts_gadget)
     rotate_ciphertext = staticmethod(rotate_ciphertext)
     rescale_ciphertext = staticmethod(rescale_ciphertext)
+
+    # -- linear transforms (the diagonal method) -----------------------------
+    def generate_rotation_key_set(self, sk: RnsPoly, steps, rng) -> RnsGadgetKeySet:
+        """One gadget rotation key per step, packed for ``linear_transform``
+        (no key for a step of 0)."""
+        keys = [None if int(s) == 0 else self.generate_gadget_rotation_key(sk, int(s), rng) for s in steps]
+        return RnsGadgetKeySet(keys, self.basis)
+
+    def encode_diagonals(self, matrix, steps, encoder: CkksEncoder) -> Plaintext:
+        """The diagonal plaintexts of a slots x slots matrix for the steps of
+        a key set: ``diag_k[i] = M[i][(i + k) mod slots]`` (slot i of a
+        rotation by k holds old slot i + k), encoded as one batch, one poly
+        per step, and moved to the NTT domain."""
+        m = np.asarray(matrix)
+        slots = m.shape[0]
+        if m.ndim != 2 or m.shape[1] != slots or slots != encoder.max_slots():
+            raise ValueError("encode_diagonals: the matrix must be slots x slots with slots = N / 2")
+        i = np.arange(slots)
+        rows = np.stack([m[i, (i + int(k)) % slots] for k in steps])
+        pt = encoder.encode_complex(rows, self.basis)
+        pt.poly.to_ntt_domain()
+        return pt
+
+    @staticmethod
+    def linear_transform(ct: Ciphertext, diag_plaintexts: Plaintext, keyset: RnsGadgetKeySet) -> Ciphertext:
+        """``sum_k diag_k * rotate(ct, k)`` over the key set's steps as one
+        library call; the scales multiply, so logp grows by the diagonals'."""
+        out = linear_transform(ct, diag_plaintexts.poly, keyset)
+        out.logp = ct.logp + diag_plaintexts.scale_bits
+        return out
 
     @staticmethod
     def secret_on(sk: RnsPoly, basis: RnsBasis) -> RnsPoly:
