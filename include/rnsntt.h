@@ -90,8 +90,8 @@ int rnt_device_count(int* n);
  * "row_mul", "col_inv", "elementwise", "rescale", "automorphism",
  * "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt", "sfft",
  * "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd",
- * "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul"), the
- * launch count and summed device milliseconds since enabling. */
+ * "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
+ * "bsgs_mac"), the launch count and summed device milliseconds since enabling. */
 int rnt_profile_enable(const rnt_ctx* ctx, int enable);
 int rnt_profile_read(const rnt_ctx* ctx, const char* kernel, uint64_t* launches,
                      double* total_ms);
@@ -337,6 +337,27 @@ int rnt_ct_rotate(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0,
 int rnt_ct_linear(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
                   const int32_t* steps, size_t n_terms, const rnt_buf* diag,
                   const rnt_buf* keys_a, const rnt_buf* keys_b);
+/* The same sum regrouped by baby steps and giant steps (a matrix whose
+ * diagonal indices are giant_steps[j] + baby_steps[i]): for every ciphertext,
+ *   R_i = rotate_ciphertext((c0, c1), baby_steps[i]; baby key i),
+ *   V_j = sum_i diag[j n_baby + i] * R_i,
+ *   out = sum_j rotate_ciphertext(V_j, giant_steps[j]; giant key j),
+ * word for word that composition of rnt_ct_rotate, coefficient-domain products
+ * and rnt_add: n_baby + n_giant key-switches at the most where rnt_ct_linear
+ * runs one per diagonal.  A step of 0 in either list is the identity (its key
+ * slot is ignored; a stage's key buffers may be NULL when all its steps are
+ * 0); steps may be negative or repeated.  diag: n_giant * n_baby polys, NTT
+ * domain, poly j n_baby + i multiplying every ciphertext of the batch.
+ * baby_keys_a/b: n_baby * L prepared polys, giant_keys_a/b: n_giant * L, each
+ * laid out as rnt_ct_linear's key set.  Domains and aliasing as rnt_ct_linear.
+ * With n_giant == 1 and giant_steps[0] == 0 the result is rnt_ct_linear's on
+ * steps = baby_steps.  (Not rnt_ct_linear's words on the same matrix: the
+ * key-switch digits, and so the noise, differ.) */
+int rnt_ct_linear_bsgs(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                       const int32_t* baby_steps, size_t n_baby,
+                       const int32_t* giant_steps, size_t n_giant, const rnt_buf* diag,
+                       const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
+                       const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b);
 /* polys [src_first, src_first + count) of src -> [dst_first, ...) of dst (same
  * context; dst takes src's domain, which must equal dst's unless the copy
  * covers all of dst).  A range outside either batch -> RNT_ERR_BAD_ARGUMENT. */

@@ -96,7 +96,8 @@ thread_local Capture* g_capture = nullptr;
 const char* const kKernelNames[rnt::K_COUNT] = {
     "col_fwd", "row_fwd", "row_inv", "row_mul", "col_inv", "elementwise", "rescale",
     "automorphism", "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt",
-    "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul"};
+    "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
+    "bsgs_mac"};
 
 // A profiling call failed: clear the runtime's slot, keep the first failure
 // in the profiler, and stop profiling (rnt_profile_read reports it).
@@ -2601,6 +2602,382 @@ extern "C" int rnt_ct_linear(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
   else
     rc = ct_linear_fused(out0, out1, c0, c1, steps, n_terms, dm, keys_a, keys_b, dm + dm_bytes, bc, any_zero,
                          any_rot);
+  if (rc) return rc;
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// baby-step giant-step linear transform:
+//   R_i = rotate(ct, baby[i]),  V_j = sum_i P[j][i] R_i,  out = sum_j rotate(V_j, giant[j])
+// ---------------------------------------------------------------------------
+namespace {
+
+// Where the inner sums go and how k_bsgs_mac's launches group them.  Every
+// nonzero giant step owns a pair of blocks; the step-0 giants share one (their
+// V_j are only ever added), the first storing and the others accumulating, so
+// a launch -- a run of consecutive giants, kBsgsJt at the most -- holds at most
+// one of them.
+struct BsgsPlan {
+  struct Group {
+    size_t j0;
+    uint32_t nj, accum_mask;
+  };
+  std::vector<size_t> slot;  // giant j's pair of blocks
+  std::vector<Group> groups;
+  size_t nv = 0;             // pairs of blocks
+  size_t zslot = 0;          // the step-0 giants' pair (any_zero)
+  bool any_zero = false, any_rot = false;
+};
+
+BsgsPlan bsgs_plan(const int32_t* giant, size_t n2) {
+  BsgsPlan p;
+  p.slot.resize(n2);
+  bool zero_in_group = false;
+  for (size_t j = 0; j < n2; ++j) {
+    const bool zero = giant[j] == 0;
+    bool accum = false;
+    if (zero) {
+      accum = p.any_zero;
+      if (!p.any_zero) p.zslot = p.nv++;
+      p.any_zero = true;
+      p.slot[j] = p.zslot;
+    } else {
+      p.any_rot = true;
+      p.slot[j] = p.nv++;
+    }
+    if (p.groups.empty() || p.groups.back().nj == rnt::kBsgsJt || (zero && zero_in_group)) {
+      p.groups.push_back({j, 0, 0});
+      zero_in_group = false;
+    }
+    BsgsPlan::Group& g = p.groups.back();
+    if (accum) g.accum_mask |= 1u << g.nj;
+    ++g.nj;
+    zero_in_group = zero_in_group || zero;
+  }
+  return p;
+}
+
+// V^ = sum_i R^_i (.) P_ji for every giant j: RB holds the 2 n1 baby blocks
+// (block 2 i + component), VB the plan's 2 nv output blocks, each of blk bytes.
+int bsgs_inner_sums(const rnt::Launch& k, const BsgsPlan& plan, char* VB, const char* RB, size_t blk,
+                    const char* dm, size_t n1, size_t n2) {
+  const size_t n = k.t->n, wb = word_bytes(k.t);
+  for (const BsgsPlan::Group& g : plan.groups) {
+    void* outs[rnt::kBsgsJt] = {};
+    for (uint32_t jj = 0; jj < g.nj; ++jj) outs[jj] = VB + 2 * plan.slot[g.j0 + jj] * blk;
+    LAUNCH(k.t, rnt::K_BSGS_MAC,
+           rnt::launch_bsgs_mac(k, outs, g.nj, g.accum_mask, RB, blk / wb, dm + g.j0 * n1 * n * wb,
+                                (uint64_t)n1 * n2 * n, (uint32_t)n1),
+           "bsgs inner sums");
+  }
+  return RNT_OK;
+}
+
+void key_views(rnt_buf kv[2], const rnt_buf* c0, const rnt_buf* keys_a, const rnt_buf* keys_b, size_t t) {
+  const size_t L = c0->ctx->L, n = c0->ctx->t->n, wb = word_bytes(c0->ctx->t.get());
+  const rnt_buf* keys[2] = {keys_a, keys_b};
+  for (int o = 0; o < 2; ++o) {
+    kv[o].ctx = c0->ctx;
+    kv[o].n_polys = keys[o]->n_polys;  // (the packed set's limb stride)
+    kv[o].data = (char*)keys[o]->data + t * L * n * wb;
+    kv[o].in_ntt = 1;
+    kv[o].owns = false;
+  }
+}
+
+// The whole-plane rings: the composition itself on the whole batch -- every
+// baby rotation through the whole-plane key-switch and a forward transform,
+// the inner sums, one inverse per sum, every giant rotation, adds.
+// ws: RB (2 n1 blocks) | VB (2 nv) | T0 T1.
+int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                     const int32_t* baby, size_t n1, const int32_t* giant, size_t n2, const BsgsPlan& plan,
+                     const char* dm, const rnt_buf* bka, const rnt_buf* bkb, const rnt_buf* gka,
+                     const rnt_buf* gkb, char* ws) {
+  rnt::Launch k = launch_for(c0);
+  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
+  const size_t pw = L * B * n * wb;
+  const uint64_t ls = limb_stride(c0);
+  char* RB = ws;
+  char* VB = RB + 2 * n1 * pw;
+  char* T = VB + 2 * plan.nv * pw;
+  auto view = [&](rnt_buf& v, char* p) {
+    v.ctx = c0->ctx;
+    v.n_polys = B;
+    v.data = p;
+    v.in_ntt = 0;
+    v.owns = false;
+  };
+  const rnt_buf* src[2] = {c0, c1};
+  rnt_buf kv[2], a[2], b[2];
+  for (size_t i = 0; i < n1; ++i) {
+    char* R[2] = {RB + 2 * i * pw, RB + (2 * i + 1) * pw};
+    if (baby[i] == 0) {
+      for (int o = 0; o < 2; ++o)
+        if (int rc = copy_rows(k, R[o], ls, src[o]->data, ls, ls, L)) return rc;
+    } else {
+      key_views(kv, c0, bka, bkb, i);
+      view(a[0], R[0]);
+      view(a[1], R[1]);
+      if (int rc = ct_rotate_body(&a[0], &a[1], c0, c1, baby[i], &kv[0], &kv[1])) return rc;
+    }
+    for (int o = 0; o < 2; ++o)
+      if (int rc = fwd_raw(k, R[o], ls)) return rc;
+  }
+  if (int rc = bsgs_inner_sums(k, plan, VB, RB, pw, dm, n1, n2)) return rc;
+  for (size_t v = 0; v < 2 * plan.nv; ++v)
+    if (int rc = inv_raw(k, VB + v * pw, ls)) return rc;
+  // (the inputs are consumed: out may be c)
+  rnt_buf* out[2] = {out0, out1};
+  bool have = false;
+  if (plan.any_zero) {
+    for (int o = 0; o < 2; ++o)
+      if (int rc = copy_rows(k, out[o]->data, ls, VB + (2 * plan.zslot + o) * pw, ls, ls, L)) return rc;
+    have = true;
+  }
+  for (size_t j = 0; j < n2; ++j) {
+    if (giant[j] == 0) continue;
+    key_views(kv, c0, gka, gkb, j);
+    view(a[0], VB + 2 * plan.slot[j] * pw);
+    view(a[1], VB + (2 * plan.slot[j] + 1) * pw);
+    view(b[0], have ? T : (char*)out0->data);
+    view(b[1], have ? T + pw : (char*)out1->data);
+    if (int rc = ct_rotate_body(&b[0], &b[1], &a[0], &a[1], giant[j], &kv[0], &kv[1])) return rc;
+    if (have) {
+      for (int o = 0; o < 2; ++o)
+        LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_elementwise(k, 0, out[o]->data, out[o]->data, b[o].data),
+               "add_assign");
+    }
+    have = true;
+  }
+  return RNT_OK;
+}
+
+// The four-step key-switch: chunks outside as in ct_linear_fused.  Per chunk
+// the workspace holds (chunk planes of L bc N words) X0 X1 (the chunk gathered,
+// more than one chunk only) | SIG1 | SEED | RB (2 n1) | VB (2 nv) | S U0 U1.
+// Baby stage: every nonzero step runs the whole key-switch (sigma(c1) ->
+// decomposition -> rows -> the two inverse column passes, sigma(c0) as the
+// addend) into its pair of RB blocks, a step-0 baby is a copy; each block is
+// then transformed forward.  Inner sums: k_bsgs_mac, one inverse per block.
+// Giant stage: every nonzero step feeds sigma(V1_j) through the decomposition
+// and the LIN rows with the Montgomery-one plane `one`, the seed
+// NTT(sigma(V0_j)) 2^-w and (after the first) accumulation into U0/U1; the
+// step-0 giants' sum is the addend of the chunk's two inverse column passes.
+int ct_bsgs_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1, const int32_t* baby,
+                  size_t n1, const int32_t* giant, size_t n2, const BsgsPlan& plan, const char* dm,
+                  const char* one, const rnt_buf* bka, const rnt_buf* bkb, const rnt_buf* gka,
+                  const rnt_buf* gkb, char* ws, size_t bc) {
+  rnt::Launch k = launch_for(c0);
+  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
+  const size_t pw = L * bc * n * wb;
+  const uint64_t full_ls = limb_stride(c0);
+  const bool multi = bc < B;
+  char* p = ws;
+  auto take = [&](size_t blocks) {
+    char* r = p;
+    p += blocks * pw;
+    return r;
+  };
+  char* X[2] = {nullptr, nullptr};
+  if (multi) {
+    X[0] = take(1);
+    X[1] = take(1);
+  }
+  char* SIG1 = take(1);
+  char* SEED = take(1);
+  char* RB = take(2 * n1);
+  char* VB = take(2 * plan.nv);
+  char* KS = p;
+  const rnt_buf* src[2] = {c0, c1};
+  rnt_buf* out[2] = {out0, out1};
+  const uint64_t two_n = 2 * (uint64_t)n;
+  for (size_t p0 = 0; p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    rnt::Launch kc = k;
+    kc.B = c;
+    const uint64_t cls = (uint64_t)c * n;
+    char* S = KS;
+    char* U[2] = {S + L * L * c * n * wb, S + (L * L + L) * c * n * wb};
+    const char* x[2];
+    for (int o = 0; o < 2; ++o) {
+      x[o] = (const char*)src[o]->data + p0 * n * wb;
+      if (multi) {
+        if (int rc = copy_rows(kc, X[o], cls, x[o], full_ls, cls, L)) return rc;
+        x[o] = X[o];
+      }
+    }
+    // baby stage
+    const char* zero_done = nullptr;
+    for (size_t i = 0; i < n1; ++i) {
+      char* R[2] = {RB + 2 * i * pw, RB + (2 * i + 1) * pw};
+      if (baby[i] == 0) {
+        if (zero_done) {  // NTT(c) is there already
+          for (int o = 0; o < 2; ++o)
+            if (int rc = copy_rows(kc, R[o], cls, zero_done + o * pw, cls, cls, L)) return rc;
+          continue;
+        }
+        for (int o = 0; o < 2; ++o)
+          if (int rc = copy_rows(kc, R[o], cls, x[o], multi ? cls : full_ls, cls, L)) return rc;
+        zero_done = R[0];
+      } else {
+        const uint64_t g = rotation_exponent(baby[i], two_n);
+        LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG1, x[1], g), "automorphism");
+        LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SEED, x[0], g), "automorphism");
+        const size_t koff = i * L * n * wb;
+        LAUNCH(kc.t, rnt::K_KS_DECOMPOSE, rnt::launch_ks_decompose(kc, S, SIG1, cls), "ks decompose");
+        LAUNCH(kc.t, rnt::K_KS_ROWS,
+               rnt::launch_ks_rows(kc, U[0], U[1], cls, S, (const char*)bka->data + koff,
+                                   (const char*)bkb->data + koff, limb_stride(bka), nullptr, nullptr, 0),
+               "ks rows");
+        LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, R[0], cls, U[0], cls, 1, SEED), "ks inverse");
+        LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, R[1], cls, U[1], cls, 1, nullptr), "ks inverse");
+      }
+      for (int o = 0; o < 2; ++o)
+        if (int rc = fwd_raw(kc, R[o], cls)) return rc;
+    }
+    // inner sums, back to coefficients for the giant decomposition
+    if (int rc = bsgs_inner_sums(kc, plan, VB, RB, pw, dm, n1, n2)) return rc;
+    for (size_t v = 0; v < 2 * plan.nv; ++v)
+      if (int rc = inv_raw(kc, VB + v * pw, cls)) return rc;
+    // giant stage
+    bool first = true;
+    for (size_t j = 0; j < n2; ++j) {
+      if (giant[j] == 0) continue;
+      const char* V0 = VB + 2 * plan.slot[j] * pw;
+      const uint64_t g = rotation_exponent(giant[j], two_n);
+      LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG1, V0 + pw, g), "automorphism");
+      LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SEED, V0, g), "automorphism");
+      if (int rc = fwd_raw(kc, SEED, cls)) return rc;
+      LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 0, SEED, SEED, nullptr, 0, false), "seed scale");
+      rnt::KsLin lin;
+      lin.mul = one;
+      lin.mul_ls = (uint64_t)n;
+      lin.accum = first ? 0u : 1u;
+      const size_t koff = j * L * n * wb;
+      LAUNCH(kc.t, rnt::K_KS_DECOMPOSE, rnt::launch_ks_decompose(kc, S, SIG1, cls), "ks decompose");
+      LAUNCH(kc.t, rnt::K_KS_ROWS,
+             rnt::launch_ks_rows_lin(kc, U[0], U[1], cls, S, (const char*)gka->data + koff,
+                                     (const char*)gkb->data + koff, limb_stride(gka), SEED, nullptr, cls, lin),
+             "ks rows");
+      first = false;
+    }
+    for (int o = 0; o < 2; ++o) {
+      char* dst = (char*)out[o]->data + p0 * n * wb;
+      char* Z = plan.any_zero ? VB + (2 * plan.zslot + o) * pw : nullptr;
+      if (!plan.any_rot) {
+        if (int rc = copy_rows(kc, dst, full_ls, Z, cls, cls, L)) return rc;
+      } else if (!multi) {
+        LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, dst, full_ls, U[o], cls, 1, Z), "ks inverse");
+      } else {
+        // (the addend shares the output's limb stride: a chunk-local output)
+        char* tmp = o == 0 ? SEED : SIG1;
+        LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, tmp, cls, U[o], cls, 1, Z), "ks inverse");
+        if (int rc = copy_rows(kc, dst, full_ls, tmp, cls, cls, L)) return rc;
+      }
+    }
+  }
+  return RNT_OK;
+}
+
+int check_stage_keys(const rnt_buf* c0, const int32_t* steps, size_t count, const rnt_buf* keys_a,
+                     const rnt_buf* keys_b, const char* stage) {
+  bool any_rot = false;
+  for (size_t t = 0; t < count; ++t) any_rot = any_rot || steps[t] != 0;
+  if (!(any_rot || keys_a || keys_b)) return RNT_OK;
+  const size_t L = c0->ctx->L;
+  if (int rc = check_buf(keys_a, "rnt_ct_linear_bsgs keys")) return rc;
+  if (int rc = check_buf(keys_b, "rnt_ct_linear_bsgs keys")) return rc;
+  if (keys_a->ctx != c0->ctx || keys_b->ctx != c0->ctx)
+    return fail(RNT_ERR_BASIS_MISMATCH, "rnt_ct_linear_bsgs: %s keys and ciphertext belong to different bases",
+                stage);
+  if (keys_a->n_polys != count * L || keys_b->n_polys != count * L)
+    return fail_fields(RNT_ERR_CHANNEL_COUNT, count * L,
+                       keys_a->n_polys != count * L ? keys_a->n_polys : keys_b->n_polys,
+                       "the %s key set must hold one poly per step and channel (%zu)", stage, count * L);
+  if (!keys_a->in_ntt || !keys_b->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_ct_linear_bsgs: %s keys must be prepared (rnt_key_prepare)", stage);
+  return RNT_OK;
+}
+
+}  // namespace
+
+extern "C" int rnt_ct_linear_bsgs(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                  const int32_t* baby_steps, size_t n_baby, const int32_t* giant_steps,
+                                  size_t n_giant, const rnt_buf* diag, const rnt_buf* baby_keys_a,
+                                  const rnt_buf* baby_keys_b, const rnt_buf* giant_keys_a,
+                                  const rnt_buf* giant_keys_b) {
+  const rnt_buf* all[4] = {out0, out1, c0, c1};
+  for (const rnt_buf* b : all)
+    if (int rc = check_buf(b, "rnt_ct_linear_bsgs")) return rc;
+  if (int rc = check_buf(diag, "rnt_ct_linear_bsgs")) return rc;
+  if (n_baby == 0 || n_giant == 0) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_linear_bsgs: no steps");
+  if (!baby_steps || !giant_steps) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_linear_bsgs: null steps");
+  for (int i = 1; i < 4; ++i)
+    if (int rc = check_same(all[0], all[i], "rnt_ct_linear_bsgs")) return rc;
+  if (diag->ctx != c0->ctx)
+    return fail(RNT_ERR_BASIS_MISMATCH, "rnt_ct_linear_bsgs: the plaintexts belong to a different basis");
+  if (n_baby > SIZE_MAX / n_giant || diag->n_polys != n_baby * n_giant)
+    return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_linear_bsgs: %zu plaintexts for %zu x %zu steps", diag->n_polys,
+                n_giant, n_baby);
+  if (int rc = check_stage_keys(c0, baby_steps, n_baby, baby_keys_a, baby_keys_b, "baby")) return rc;
+  if (int rc = check_stage_keys(c0, giant_steps, n_giant, giant_keys_a, giant_keys_b, "giant")) return rc;
+  if (!diag->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_ct_linear_bsgs: the plaintexts must be in the NTT domain");
+  if (c0->in_ntt || c1->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_ct_linear_bsgs: the ciphertext must be in coefficient domain");
+  const rnt_buf* ins[7] = {c0, c1, diag, baby_keys_a, baby_keys_b, giant_keys_a, giant_keys_b};
+  if (out0 == out1) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_linear_bsgs: out0 aliases out1");
+  for (int i = 0; i < 7; ++i) {
+    if ((out0 == ins[i] && i != 0) || (out1 == ins[i] && i != 1))
+      return fail(RNT_ERR_BAD_ARGUMENT,
+                  "rnt_ct_linear_bsgs: an output aliases an input other than its own component");
+  }
+  if (int rc = set_device(c0->ctx)) return rc;
+  rnt::Launch k = launch_for(c0);
+  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
+  const size_t n_terms = n_baby * n_giant;
+  BsgsPlan plan;
+  try {
+    plan = bsgs_plan(giant_steps, n_giant);
+  } catch (...) {
+    return fail(RNT_ERR_OUT_OF_MEMORY, "host allocation failed");
+  }
+  const bool composed = rnt::ks_whole_ok(k.t);
+  // chunk planes per ciphertext: the baby blocks, the inner sums, SIG1, SEED
+  // and the gathered chunk (composed: the two rotation outputs); with the
+  // key-switch scratch they stay within the key-switch workspace cap, one
+  // ciphertext being the floor
+  const size_t planes = 2 * n_baby + 2 * plan.nv + (composed ? 2 : 4);
+  size_t bc = B;
+  if (!composed) {
+    const size_t per = (planes * L + L * L + 2 * L) * n * wb;
+    bc = std::min(B, std::max<size_t>(k.t->ks_ws_bytes / per, 1));
+  }
+  const size_t dm_bytes = L * n_terms * n * wb;
+  const size_t one_bytes = composed ? 0 : L * n * wb;
+  const size_t used = planes - (!composed && bc == B ? 2 : 0);
+  const size_t need =
+      dm_bytes + one_bytes + used * L * bc * n * wb + (composed ? 0 : ks_scratch_words(k.t, L, bc) * wb);
+  CallWs ws(out0);
+  if (int rc = ws.get(std::max<size_t>(need, 16))) return rc;
+  // the plaintexts in Montgomery form (m^ 2^w mod q), once per call: the inner
+  // sums' Montgomery products are then the canonical products
+  char* dm = (char*)ws.p;
+  rnt::Launch kd = k;
+  kd.B = n_terms;
+  LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kd, 1, dm, diag->data, nullptr, 0, false),
+         "plaintexts to Montgomery form");
+  int rc;
+  if (composed) {
+    rc = ct_bsgs_composed(out0, out1, c0, c1, baby_steps, n_baby, giant_steps, n_giant, plan, dm, baby_keys_a,
+                          baby_keys_b, giant_keys_a, giant_keys_b, dm + dm_bytes);
+  } else {
+    char* one = dm + dm_bytes;
+    if (plan.any_rot) LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_mont_one(k, one), "Montgomery one");
+    rc = ct_bsgs_fused(out0, out1, c0, c1, baby_steps, n_baby, giant_steps, n_giant, plan, dm, one, baby_keys_a,
+                       baby_keys_b, giant_keys_a, giant_keys_b, one + one_bytes, bc);
+  }
   if (rc) return rc;
   out0->in_ntt = out1->in_ntt = 0;
   return RNT_OK;

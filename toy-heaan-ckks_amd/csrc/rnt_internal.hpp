@@ -123,7 +123,7 @@ enum KernelId {
   K_COL_FWD, K_ROW_FWD, K_ROW_INV, K_ROW_MUL, K_COL_INV, K_ELEMENTWISE, K_RESCALE,
   K_AUTOMORPHISM, K_KS_DECOMPOSE, K_KS_ROWS, K_TENSOR_ROWS, K_IMPORT, K_EXPORT, K_CRT,
   K_SFFT, K_SAMPLE, K_COPY, K_PLANE_FUSED, K_MF_NTT_FWD, K_MF_NTT_INV, K_WHOLE_FWD, K_WHOLE_INV, K_WHOLE_MUL,
-  K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_COUNT
+  K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_COUNT
 };
 
 struct Prof {
@@ -323,6 +323,19 @@ hipError_t launch_ks_rows_lin(const Launch& k, void* u0, void* u1, uint64_t u_ls
 // kind 1: out = x 2^w mod q (canonical -> Montgomery form).  out may be x.
 hipError_t launch_bcast_mul(const Launch& k, int kind, void* out, const void* x, const void* m,
                             uint64_t m_ls, bool accum);
+// The inner sums of rnt_ct_linear_bsgs (k_bsgs_mac), both components of nj <=
+// kBsgsJt giant steps in one launch: outs[jj] + comp blk_words = sum_b
+// x[2 b + comp] (.) m[jj n_baby + b] (+ the words already there with bit jj of
+// accum_mask), b < n_baby, comp in {0, 1}.  x is 2 n_baby NTT-domain blocks of
+// blk_words words, each [k.L][k.B][N]; m points at plane (jj = 0, b = 0) of
+// the Montgomery-form plaintexts, one [N] plane per limb and pair at limb
+// stride m_ls, broadcast over the batch.  The outputs are distinct from x.
+constexpr uint32_t kBsgsJt = 4;
+hipError_t launch_bsgs_mac(const Launch& k, void* const* outs, uint32_t nj, uint32_t accum_mask,
+                           const void* x, uint64_t blk_words, const void* m, uint64_t m_ls,
+                           uint32_t n_baby);
+// out[l][i] = 2^w mod q_l over [k.L][N]: the Montgomery-form plaintext 1.
+hipError_t launch_mont_one(const Launch& k, void* out);
 // The whole-plane key-switch at 2^10 <= N <= 2^13 (k_ks_whole, one launch,
 // no S): out0 = INV(sum_i NTT(src_i mod q_j) (.) key_b[i][j] + init0) (+ add0),
 // out1 likewise with key_a; src is [k.src_limbs()][k.B][N] coefficient-domain

@@ -1768,6 +1768,105 @@ k_bcast_mul(W* out, const W* x, const W* __restrict__ m, TabPtrs<W> tp, uint32_t
   }
 }
 
+// The inner sums of rnt_ct_linear_bsgs in the NTT domain, both components of
+// up to BSGS_JT giant steps per launch: out_jj = sum_b x_b (.) m[jj][b] for
+// jj < nj.  x is the baby rotations, block 2 b + comp of blk_words words
+// ([L][B][N], limb stride B N) for blockIdx.z = comp; m points at plane
+// (jj = 0, b = 0) of the Montgomery-form plaintexts ([L][..][N] at limb stride
+// m_ls, plane jj n_baby + b, the same plane for every poly of the batch), so
+// every Montgomery product is the canonical product and the sums stay
+// canonical through add_mod.  Output jj is o.out[jj] + comp blk_words; with
+// bit jj of accum_mask the sum is added to the words already there.  A thread
+// reads each baby vector once for all nj sums: 2 n_baby + 2 nj batch-planes
+// of traffic per launch against the 6 n_baby nj of one k_bcast_mul per pair.
+constexpr int BSGS_JT = (int)kBsgsJt;
+template <class W>
+struct BsgsOuts {
+  W* out[BSGS_JT];
+};
+template <class W, bool VEC>
+__global__ void __launch_bounds__(256)
+k_bsgs_mac(BsgsOuts<W> o, const W* __restrict__ x, const W* __restrict__ m, TabPtrs<W> tp, uint32_t log_n,
+           uint64_t limb_words, uint64_t blk_words, uint64_t m_ls, uint32_t n_baby, uint32_t nj,
+           uint32_t accum_mask) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint32_t l = blockIdx.y;
+  const uint32_t comp = blockIdx.z;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= limb_words) return;
+  const LimbConst<W> lc = tp.lc[l];
+  const uint64_t N = 1ull << log_n;
+  const uint64_t g = (uint64_t)comp * blk_words + (uint64_t)l * limb_words + i;
+  const W* mp = m + (uint64_t)l * m_ls + (i & (N - 1));  // V divides N: one plane
+  const W* xp = x + g;
+  W acc[BSGS_JT][V];
+#pragma unroll
+  for (int jj = 0; jj < BSGS_JT; ++jj)
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[jj][v] = (W)0;
+  for (uint32_t b = 0; b < n_baby; ++b) {
+    W xv[V];
+    if constexpr (VEC) {
+      const uint4 xa = *reinterpret_cast<const uint4*>(xp + (uint64_t)b * 2 * blk_words);
+      __builtin_memcpy(xv, &xa, 16);
+    } else {
+      xv[0] = xp[(uint64_t)b * 2 * blk_words];
+    }
+#pragma unroll
+    for (int jj = 0; jj < BSGS_JT; ++jj) {
+      if ((uint32_t)jj < nj) {  // (uniform)
+        const W* mq = mp + ((uint64_t)jj * n_baby + b) * N;
+        W mv[V];
+        if constexpr (VEC) {
+          const uint4 ma = *reinterpret_cast<const uint4*>(mq);
+          __builtin_memcpy(mv, &ma, 16);
+        } else {
+          mv[0] = mq[0];
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+          acc[jj][v] = add_mod<W>(acc[jj][v], mont_mul<W>(xv[v], mv[v], lc.q, lc.qinv), lc.q);
+      }
+    }
+  }
+#pragma unroll
+  for (int jj = 0; jj < BSGS_JT; ++jj) {
+    if ((uint32_t)jj < nj) {
+      W* op = o.out[jj] + g;
+      if ((accum_mask >> jj) & 1u) {
+        W ov[V];
+        if constexpr (VEC) {
+          const uint4 oa = *reinterpret_cast<const uint4*>(op);
+          __builtin_memcpy(ov, &oa, 16);
+        } else {
+          ov[0] = op[0];
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[jj][v] = add_mod<W>(ov[v], acc[jj][v], lc.q);
+      }
+      if constexpr (VEC) {
+        uint4 r;
+        __builtin_memcpy(&r, acc[jj], 16);
+        *reinterpret_cast<uint4*>(op) = r;
+      } else {
+        op[0] = acc[jj][0];
+      }
+    }
+  }
+}
+
+// One [N] plane per limb of Montgomery ones (2^w mod q): the plaintext row of
+// the LIN key-switch rows where a term has no plaintext (the giant rotations
+// of rnt_ct_linear_bsgs).
+template <class W>
+__global__ void __launch_bounds__(256)
+k_mont_one(W* __restrict__ out, TabPtrs<W> tp, uint32_t log_n) {
+  const uint32_t l = blockIdx.y;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (1u << log_n)) return;
+  out[((uint64_t)l << log_n) + i] = tp.lc[l].rmod;
+}
+
 // rescale_into (poly.rs:212-225): out[l] = (c_l - (c_last mod q_l)) * q_last^-1.
 template <class W>
 __global__ void __launch_bounds__(256)
@@ -2197,6 +2296,46 @@ static hipError_t bcast_mul_t(const Launch& k, int kind, void* out, const void* 
     if (vec) RNT_BM(1, true); else RNT_BM(1, false);
   }
 #undef RNT_BM
+  return hipGetLastError();
+}
+
+template <class W>
+static hipError_t bsgs_mac_t(const Launch& k, void* const* outs, uint32_t nj, uint32_t accum_mask,
+                             const void* x, uint64_t blk_words, const void* m, uint64_t m_ls,
+                             uint32_t n_baby) {
+  const uint64_t N = 1ull << k.t->log_n;
+  const uint64_t limb_words = (uint64_t)k.B * N;
+  if (nj == 0 || nj > (uint32_t)BSGS_JT || n_baby == 0 || blk_words < (uint64_t)k.L * limb_words)
+    return hipErrorInvalidValue;
+  if (limb_words == 0 || k.L == 0) return hipSuccess;
+  constexpr int V = 16 / (int)sizeof(W);
+  BsgsOuts<W> o{};
+  uintptr_t align = (uintptr_t)x | (uintptr_t)m;
+  for (uint32_t jj = 0; jj < nj; ++jj) {
+    o.out[jj] = (W*)outs[jj];
+    align |= (uintptr_t)outs[jj];
+  }
+  // 16-byte accesses: whole vectors within a plane, every plane and block 16-byte aligned
+  const bool vec = N % V == 0 && m_ls % V == 0 && blk_words % V == 0 && align % 16 == 0;
+  const uint64_t per = vec ? limb_words / V : limb_words;
+  const uint64_t bx = (per + 255) / 256;
+  if (bx > 0x7fffffffull || k.L > 65535) return hipErrorInvalidConfiguration;
+  const dim3 grid((unsigned)bx, (unsigned)k.L, 2);
+#define RNT_BG(VEC)                                                                                   \
+  hipLaunchKernelGGL((k_bsgs_mac<W, VEC>), grid, dim3(256), 0, k.s, o, (const W*)x, (const W*)m,      \
+                     tab_ptrs<W>(k.t), k.t->log_n, limb_words, blk_words, m_ls, n_baby, nj, accum_mask)
+  if (vec) RNT_BG(true); else RNT_BG(false);
+#undef RNT_BG
+  return hipGetLastError();
+}
+
+template <class W>
+static hipError_t mont_one_t(const Launch& k, void* out) {
+  const uint64_t N = 1ull << k.t->log_n;
+  if (k.L == 0) return hipSuccess;
+  if (k.L > 65535) return hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL((k_mont_one<W>), dim3((unsigned)((N + 255) / 256), (unsigned)k.L), dim3(256), 0, k.s,
+                     (W*)out, tab_ptrs<W>(k.t), k.t->log_n);
   return hipGetLastError();
 }
 
@@ -2759,6 +2898,15 @@ hipError_t launch_bcast_mul(const Launch& k, int kind, void* out, const void* x,
                             uint64_t m_ls, bool accum) {
   RNT_WIDE(bcast_mul_t<uint32_t>(k, kind, out, x, m, m_ls, accum),
            bcast_mul_t<uint64_t>(k, kind, out, x, m, m_ls, accum));
+}
+hipError_t launch_bsgs_mac(const Launch& k, void* const* outs, uint32_t nj, uint32_t accum_mask,
+                           const void* x, uint64_t blk_words, const void* m, uint64_t m_ls,
+                           uint32_t n_baby) {
+  RNT_WIDE(bsgs_mac_t<uint32_t>(k, outs, nj, accum_mask, x, blk_words, m, m_ls, n_baby),
+           bsgs_mac_t<uint64_t>(k, outs, nj, accum_mask, x, blk_words, m, m_ls, n_baby));
+}
+hipError_t launch_mont_one(const Launch& k, void* out) {
+  RNT_WIDE(mont_one_t<uint32_t>(k, out), mont_one_t<uint64_t>(k, out));
 }
 template <class W>
 static hipError_t ks_whole_t(const Launch& k, void* out0, void* out1, uint64_t out_ls, const void* src,

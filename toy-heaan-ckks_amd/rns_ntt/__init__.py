@@ -43,6 +43,8 @@ __all__ = [
     "rotate_ciphertext",
     "RnsGadgetKeySet",
     "linear_transform",
+    "linear_transform_bsgs",
+    "bsgs_diagonal_rows",
     "rescale_ciphertext",
     "Plaintext",
     "CkksEncoder",
@@ -668,6 +670,66 @@ def linear_transform(ct: Ciphertext, diag: RnsPoly, keyset: RnsGadgetKeySet,
                                keyset.a.handle if keyset.a is not None else None,
                                keyset.b.handle if keyset.b is not None else None))
     return out
+
+
+def linear_transform_bsgs(ct: Ciphertext, diag: RnsPoly, baby_keyset: RnsGadgetKeySet,
+                          giant_keyset: RnsGadgetKeySet, out: Optional[Ciphertext] = None) -> Ciphertext:
+    """The baby-step giant-step form of :func:`linear_transform`
+    (rnt_ct_linear_bsgs): with ``b = baby_keyset.steps`` (n1 of them) and
+    ``g = giant_keyset.steps`` (n2),
+
+        ``sum_j rotate(sum_i diag[j n1 + i] * rotate(ct, b[i]), g[j])``
+
+    for every ciphertext of the batch -- at most n1 + n2 key-switches for the
+    n1 n2 diagonals ``g[j] + b[i]``.  ``diag`` holds the n2 n1 NTT-domain
+    plaintext polys (:func:`bsgs_diagonal_rows` gives their slots).  ``out``
+    may be ``ct`` itself (in place)."""
+    basis = ct.c0.basis
+    if out is None:
+        out = Ciphertext(ct.c0._like(basis), ct.c0._like(basis), ct.logp, ct.logq)
+    baby = (ctypes.c_int32 * len(baby_keyset.steps))(*baby_keyset.steps)
+    giant = (ctypes.c_int32 * len(giant_keyset.steps))(*giant_keyset.steps)
+
+    def h(p):
+        return p.handle if p is not None else None
+
+    check(load().rnt_ct_linear_bsgs(out.c0.handle, out.c1.handle, ct.c0.handle, ct.c1.handle, baby,
+                                    len(baby_keyset.steps), giant, len(giant_keyset.steps), diag.handle,
+                                    h(baby_keyset.a), h(baby_keyset.b), h(giant_keyset.a), h(giant_keyset.b)))
+    return out
+
+
+def bsgs_diagonal_rows(matrix, baby_steps, giant_steps) -> np.ndarray:
+    """The plaintext slot vectors of a slots x slots matrix for
+    :func:`linear_transform_bsgs`, ``[n2][n1][slots]``:
+
+        ``rows[j][i][s] = M[(s - g_j) mod slots][(s + b_i) mod slots]``
+
+    -- diagonal ``g_j + b_i`` of the matrix, rotated back by its giant step
+    (slot s of a rotation by k holds old slot s + k), so that
+    ``sum_j rot_{g_j}(sum_i rows[j][i] * rot_{b_i}(x)) = M_banded x`` with
+    M_banded the matrix restricted to those diagonals.  Pure numpy.  Steps
+    are slot rotations in ``[0, slots)``: a negative step raises ValueError
+    (pass ``slots - k``), and so do two pairs that name one diagonal."""
+    m = np.asarray(matrix)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError("bsgs_diagonal_rows: the matrix must be square")
+    slots = m.shape[0]
+    baby = [int(b) for b in baby_steps]
+    giant = [int(g) for g in giant_steps]
+    if not baby or not giant:
+        raise ValueError("bsgs_diagonal_rows: no steps")
+    if any(k < 0 for k in baby + giant):
+        raise ValueError("bsgs_diagonal_rows: negative step (pass slots - k for a rotation by -k)")
+    seen = {}
+    for j, g in enumerate(giant):
+        for i, b in enumerate(baby):
+            d = (g + b) % slots
+            if d in seen:
+                raise ValueError(f"bsgs_diagonal_rows: pairs {seen[d]} and {(j, i)} both give diagonal {d}")
+            seen[d] = (j, i)
+    s = np.arange(slots)
+    return np.stack([np.stack([m[(s - g) % slots, (s + b) % slots] for b in baby]) for g in giant])
 
 
 def mul_ciphertexts_gadget_rescale(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsGadgetKey) -> Ciphertext:

@@ -24,7 +24,7 @@ from typing import Optional
 import numpy as np
 
 from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsGadgetKeySet, RnsPoly,
-               linear_transform, mul_ciphertexts_gadget, rescale_ciphertext, rotate_ciphertext)
+               bsgs_diagonal_rows, linear_transform, linear_transform_bsgs, mul_ciphertexts_gadget, rescale_ciphertext, rotate_ciphertext)
 
 
 @dataclass
@@ -184,6 +184,29 @@ class CkksEngine:
         """``sum_k diag_k * rotate(ct, k)`` over the key set's steps as one
         library call; the scales multiply, so logp grows by the diagonals'."""
         out = linear_transform(ct, diag_plaintexts.poly, keyset)
+        out.logp = ct.logp + diag_plaintexts.scale_bits
+        return out
+
+    def encode_diagonals_bsgs(self, matrix, baby_steps, giant_steps, encoder: CkksEncoder) -> Plaintext:
+        """The n2 n1 plaintexts of a slots x slots matrix for
+        ``linear_transform_bsgs`` (``bsgs_diagonal_rows``: diagonal
+        ``g_j + b_i`` rotated back by ``g_j``), encoded as one batch, poly
+        ``j n1 + i`` for (giant j, baby i), and moved to the NTT domain."""
+        m = np.asarray(matrix)
+        if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] != encoder.max_slots():
+            raise ValueError("encode_diagonals_bsgs: the matrix must be slots x slots with slots = N / 2")
+        rows = bsgs_diagonal_rows(m, baby_steps, giant_steps)
+        pt = encoder.encode_complex(rows.reshape(-1, rows.shape[-1]), self.basis)
+        pt.poly.to_ntt_domain()
+        return pt
+
+    @staticmethod
+    def linear_transform_bsgs(ct: Ciphertext, diag_plaintexts: Plaintext, baby_keyset: RnsGadgetKeySet,
+                              giant_keyset: RnsGadgetKeySet) -> Ciphertext:
+        """``sum_j rotate(sum_i diag_ji * rotate(ct, b_i), g_j)`` over the two
+        key sets' steps as one library call: n1 + n2 key-switches for n1 n2
+        diagonals; logp grows by the diagonals' scale."""
+        out = linear_transform_bsgs(ct, diag_plaintexts.poly, baby_keyset, giant_keyset)
         out.logp = ct.logp + diag_plaintexts.scale_bits
         return out
 
