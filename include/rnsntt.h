@@ -91,7 +91,7 @@ int rnt_device_count(int* n);
  * "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt", "sfft",
  * "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd",
  * "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
- * "bsgs_mac"), the launch count and summed device milliseconds since enabling. */
+ * "bsgs_mac", "hoist_digits", "hoist_mac"), the launch count and summed device milliseconds since enabling. */
 int rnt_profile_enable(const rnt_ctx* ctx, int enable);
 int rnt_profile_read(const rnt_ctx* ctx, const char* kernel, uint64_t* launches,
                      double* total_ms);
@@ -358,6 +358,59 @@ int rnt_ct_linear_bsgs(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rn
                        const int32_t* giant_steps, size_t n_giant, const rnt_buf* diag,
                        const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
                        const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b);
+/* ---- hoisted rotations: one gadget decomposition for many steps --------
+ * For one ciphertext (c0, c1), a step k with sigma_k = rotate_slots(., k)
+ * (poly.rs:546-569; for k < 0 its two-automorphism composition), that step's
+ * ordinary gadget rotation key (key_a[i], key_b[i]) and the gadget digits
+ * D_i = alpha_i(c1) (channel j of D_i = channel i of c1 mod q_j,
+ * engine.rs:429-443), the hoisted rotation is
+ *   out0 = sigma_k(c0) + sum_i sigma_k(D_i) * key_b[i]
+ *   out1 =               sum_i sigma_k(D_i) * key_a[i]
+ * (negacyclic products, coefficient domain, exact mod q_j, canonical outputs).
+ * It is a valid rotation -- sum_i sigma(D_i) g_i = sigma(c1) mod Q, and sigma
+ * only permutes and negates the digits, so the noise is rnt_ct_rotate's -- but
+ * NOT rnt_ct_rotate's words, whose digits are alpha_i(sigma(c1)).  Because
+ * sigma is a ring automorphism the same words are
+ *   out0 = sigma_k(c0 + sum_i D_i * sigma_k^-1(key_b[i]))
+ *   out1 = sigma_k(     sum_i D_i * sigma_k^-1(key_a[i]))
+ * which is what runs: the transformed digits carry no step and are computed
+ * once for every step; the step lives in the key's HOISTING FORM
+ * NTT(sigma_k^-1(key)) and in one automorphism of the two sums.
+ *
+ * rnt_key_prepare_hoisted: (key_a, key_b) <- NTT(sigma_k^-1(key)), the hoisting
+ * form of the gadget rotation key for step k.  Either domain on entry, NTT
+ * domain on return; k == 0 is rnt_key_prepare.  A caller that needs both forms
+ * of a key keeps two copies. */
+int rnt_key_prepare_hoisted(rnt_buf* key_a, rnt_buf* key_b, int32_t k);
+/* n_steps hoisted rotations (the definition above) of every ciphertext of the
+ * batch with one decomposition.  c0, c1: B polys, coefficient domain (an
+ * NTT-domain input -> RNT_ERR_DOMAIN_MISMATCH).  out0/out1: n_steps * B polys
+ * on the same basis, rotation t of ciphertext b at poly t B + b, coefficient
+ * domain on return.  A step of 0 is the identity (c0, c1) itself with no key;
+ * steps may be negative or repeated.  keys_a/keys_b: n_steps * L polys laid out
+ * as rnt_ct_linear's key set, step t's key in the hoisting form for steps[t]
+ * (rnt_key_prepare_hoisted); a step-0 slot is ignored and the buffers may be
+ * NULL when every step is 0; a coefficient-domain key ->
+ * RNT_ERR_DOMAIN_MISMATCH, a wrong poly count -> RNT_ERR_CHANNEL_COUNT (fields:
+ * expected, got).  n_steps == 0, outputs of the wrong size, an output aliasing
+ * an input or the other output -> RNT_ERR_BAD_ARGUMENT.  The library cannot
+ * tell an ordinary prepared key from a hoisting-form one: passing the wrong
+ * form gives a wrong, not a rejected, result.  With a single step the call
+ * pays the whole transform of the L^2 digits for it and is slower than
+ * rnt_ct_rotate; it gains from the second step of the same ciphertext on. */
+int rnt_ct_rotate_hoisted(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                          const int32_t* steps, size_t n_steps,
+                          const rnt_buf* keys_a, const rnt_buf* keys_b);
+/* rnt_ct_linear_bsgs with R_i defined by the hoisted rotation above instead of
+ * rotate_ciphertext: every nonzero baby step shares one decomposition of c1.
+ * baby_keys_a/b in hoisting form (rnt_key_prepare_hoisted with baby_steps[i]),
+ * giant_keys_a/b ordinary (rnt_key_prepare).  Same argument rules otherwise.
+ * Not rnt_ct_linear_bsgs' words: the baby digits differ. */
+int rnt_ct_linear_bsgs_hoisted(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                               const int32_t* baby_steps, size_t n_baby,
+                               const int32_t* giant_steps, size_t n_giant, const rnt_buf* diag,
+                               const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
+                               const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b);
 /* polys [src_first, src_first + count) of src -> [dst_first, ...) of dst (same
  * context; dst takes src's domain, which must equal dst's unless the copy
  * covers all of dst).  A range outside either batch -> RNT_ERR_BAD_ARGUMENT. */

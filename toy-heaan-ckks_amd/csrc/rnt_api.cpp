@@ -97,7 +97,7 @@ const char* const kKernelNames[rnt::K_COUNT] = {
     "col_fwd", "row_fwd", "row_inv", "row_mul", "col_inv", "elementwise", "rescale",
     "automorphism", "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt",
     "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
-    "bsgs_mac"};
+    "bsgs_mac", "hoist_digits", "hoist_mac"};
 
 // A profiling call failed: clear the runtime's slot, keep the first failure
 // in the profiler, and stop profiling (rnt_profile_read reports it).
@@ -2388,6 +2388,72 @@ int lin_mac(const rnt::Launch& k, void* z, const void* x, const char* dm, size_t
   return RNT_OK;
 }
 
+// g^-1 mod 2N (g odd): Newton's iteration mod 2^64, then the mask.
+uint64_t exponent_inverse(uint64_t g, uint64_t two_n) {
+  uint64_t x = g;
+  for (int it = 0; it < 6; ++it) x *= 2 - g * x;
+  return x & (two_n - 1);
+}
+
+// inv_raw, then + addend (coefficient domain, a contiguous block in p's
+// layout): the four-step inverse column pass adds it as it stores, the
+// one-launch transforms take an add_assign after them.
+int inv_add_raw(const rnt::Launch& k, void* p, uint64_t ls, const void* addend) {
+  if (use_mf(k) || rnt::whole_ok(k.t, 1)) {
+    if (int rc = inv_raw(k, p, ls)) return rc;
+    LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_elementwise(k, 0, p, p, addend), "add_assign");
+    return RNT_OK;
+  }
+  LAUNCH(k.t, rnt::K_ROW_INV, rnt::launch_row(k, 1, p, nullptr, ls), "row inverse");
+  LAUNCH(k.t, rnt::K_COL_INV, rnt::launch_col_inv(k, p, ls, p, ls, 0, addend), "column inverse");
+  return RNT_OK;
+}
+
+// The hoisted gadget sums of one chunk (kc.B polys of c1 at limb stride
+// c1_ls): the digits once -- D ([L][L kc.B][N]) <- NTT_j(c1_i 2^w mod q_j), a
+// buffer of L limbs and L kc.B polys through the ordinary forward transform,
+// so in the device order of rnt_key_prepare's output -- then one k_hoist_mac
+// launch per group of kHoistT nonzero steps into ACC (2 kHoistT blocks of
+// [L][kc.B][N]) and finish(t, acc0, acc1) for every step t of the group, the
+// accumulators canonical and in the NTT domain: INV(acc0) = sum_i D_i
+// sigma^-1(key_b[t][i]).
+template <class Finish>
+int hoist_chunk(const rnt::Launch& kc, char* D, char* ACC, const void* c1, uint64_t c1_ls, const int32_t* steps,
+                size_t n_steps, const rnt_buf* keys_a, const rnt_buf* keys_b, Finish&& finish) {
+  const size_t L = kc.L, n = kc.t->n, wb = word_bytes(kc.t);
+  const size_t pw = L * kc.B * n * wb;
+  bool any_rot = false;
+  for (size_t t = 0; t < n_steps; ++t) any_rot = any_rot || steps[t] != 0;
+  if (!any_rot) return RNT_OK;
+  LAUNCH(kc.t, rnt::K_HOIST_DIGITS, rnt::launch_hoist_digits(kc, D, c1, c1_ls), "hoisted digits");
+  rnt::Launch kd = kc;
+  kd.B = L * kc.B;
+  if (int rc = fwd_raw(kd, D, (uint64_t)kd.B * n)) return rc;
+  for (size_t t = 0; t < n_steps;) {
+    size_t idx[rnt::kHoistT];
+    void* a0[rnt::kHoistT] = {};
+    void* a1[rnt::kHoistT] = {};
+    const void* ka[rnt::kHoistT] = {};
+    const void* kb[rnt::kHoistT] = {};
+    uint32_t nt = 0;
+    for (; t < n_steps && nt < rnt::kHoistT; ++t) {
+      if (steps[t] == 0) continue;
+      idx[nt] = t;
+      a0[nt] = ACC + 2 * nt * pw;
+      a1[nt] = ACC + (2 * nt + 1) * pw;
+      ka[nt] = (const char*)keys_a->data + t * L * n * wb;
+      kb[nt] = (const char*)keys_b->data + t * L * n * wb;
+      ++nt;
+    }
+    if (nt == 0) break;
+    LAUNCH(kc.t, rnt::K_HOIST_MAC, rnt::launch_hoist_mac(kc, a0, a1, nt, D, ka, kb, limb_stride(keys_a)),
+           "hoisted gadget sums");
+    for (uint32_t u = 0; u < nt; ++u)
+      if (int rc = finish(idx[u], (char*)a0[u], (char*)a1[u])) return rc;
+  }
+  return RNT_OK;
+}
+
 // The whole-plane rings (ks_whole_ok: no U0/U1 for the terms to share): the
 // composition itself -- every term's rotation through the whole-plane
 // key-switch, its product with the plaintext taken in the NTT domain and
@@ -2608,6 +2674,129 @@ extern "C" int rnt_ct_linear(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
 }
 
 // ---------------------------------------------------------------------------
+// hoisted rotations: out_t = sigma_t(c0 + sum_i D_i sigma_t^-1(key_b[t][i])),
+//                            sigma_t(     sum_i D_i sigma_t^-1(key_a[t][i]))
+// with D_i = alpha_i(c1) decomposed and transformed once for every step
+// ---------------------------------------------------------------------------
+extern "C" int rnt_key_prepare_hoisted(rnt_buf* key_a, rnt_buf* key_b, int32_t k) {
+  if (int rc = check_buf(key_a, "rnt_key_prepare_hoisted")) return rc;
+  if (int rc = check_buf(key_b, "rnt_key_prepare_hoisted")) return rc;
+  if (int rc = check_same(key_a, key_b, "rnt_key_prepare_hoisted")) return rc;
+  if (k == 0) return rnt_key_prepare(key_a, key_b);
+  const uint64_t two_n = 2 * (uint64_t)key_a->ctx->t->n;
+  const uint64_t ginv = exponent_inverse(rotation_exponent(k, two_n), two_n);
+  // (rnt_automorphism converts an NTT-domain key first and runs in place
+  // through the buffer's workspace)
+  for (rnt_buf* key : {key_a, key_b}) {
+    if (int rc = rnt_automorphism(key, key, ginv)) return rc;
+    if (int rc = rnt_ntt_fwd(key)) return rc;
+  }
+  return RNT_OK;
+}
+
+extern "C" int rnt_ct_rotate_hoisted(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                     const int32_t* steps, size_t n_steps, const rnt_buf* keys_a,
+                                     const rnt_buf* keys_b) {
+  const rnt_buf* all[4] = {out0, out1, c0, c1};
+  for (const rnt_buf* b : all)
+    if (int rc = check_buf(b, "rnt_ct_rotate_hoisted")) return rc;
+  if (n_steps == 0) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_rotate_hoisted: no steps");
+  if (!steps) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_rotate_hoisted: null steps");
+  if (int rc = check_same(c0, c1, "rnt_ct_rotate_hoisted")) return rc;
+  if (out0->ctx != c0->ctx || out1->ctx != c0->ctx)
+    return fail(RNT_ERR_BASIS_MISMATCH, "rnt_ct_rotate_hoisted: operands belong to different bases");
+  const size_t L = c0->ctx->L, B = c0->n_polys;
+  if (n_steps > SIZE_MAX / std::max<size_t>(B, 1) || out0->n_polys != n_steps * B || out1->n_polys != n_steps * B)
+    return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_rotate_hoisted: outputs of %zu and %zu polys for %zu steps of %zu",
+                out0->n_polys, out1->n_polys, n_steps, B);
+  size_t nz = 0;
+  for (size_t t = 0; t < n_steps; ++t) nz += steps[t] != 0;
+  if (nz || keys_a || keys_b) {
+    if (int rc = check_buf(keys_a, "rnt_ct_rotate_hoisted keys")) return rc;
+    if (int rc = check_buf(keys_b, "rnt_ct_rotate_hoisted keys")) return rc;
+    if (keys_a->ctx != c0->ctx || keys_b->ctx != c0->ctx)
+      return fail(RNT_ERR_BASIS_MISMATCH, "rnt_ct_rotate_hoisted: keys and ciphertext belong to different bases");
+    if (keys_a->n_polys != n_steps * L || keys_b->n_polys != n_steps * L)
+      return fail_fields(RNT_ERR_CHANNEL_COUNT, n_steps * L,
+                         keys_a->n_polys != n_steps * L ? keys_a->n_polys : keys_b->n_polys,
+                         "the key set must hold one poly per step and channel (%zu)", n_steps * L);
+    if (!keys_a->in_ntt || !keys_b->in_ntt)
+      return fail(RNT_ERR_DOMAIN_MISMATCH,
+                  "rnt_ct_rotate_hoisted: keys must be in hoisting form (rnt_key_prepare_hoisted)");
+  }
+  if (c0->in_ntt || c1->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_ct_rotate_hoisted: the ciphertext must be in coefficient domain");
+  if (out0 == out1) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_rotate_hoisted: out0 aliases out1");
+  for (const rnt_buf* in : {c0, c1, keys_a, keys_b})
+    if (in && (out0 == in || out1 == in || out0->data == in->data || out1->data == in->data))
+      return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_rotate_hoisted: an output aliases an input");
+  if (int rc = set_device(c0->ctx)) return rc;
+  rnt::Launch k = launch_for(c0);
+  const size_t n = k.t->n, wb = word_bytes(k.t);
+  const uint64_t full_ls = limb_stride(c0), out_ls = limb_stride(out0), two_n = 2 * (uint64_t)n;
+  const rnt_buf* src[2] = {c0, c1};
+  rnt_buf* out[2] = {out0, out1};
+  // per ciphertext of a chunk: the digits (L^2 planes of N words), the
+  // accumulator pairs of one k_hoist_mac group, the automorphism's staging
+  // block and the gathered c0 (more than one chunk only), within the
+  // key-switch workspace cap, one ciphertext being the floor
+  const size_t tg = std::min<size_t>(nz, rnt::kHoistT);
+  const size_t per = (L * L + (2 * tg + 2) * L) * n * wb;
+  const size_t bc = nz ? std::min(B, std::max<size_t>(k.t->ks_ws_bytes / per, 1)) : B;
+  const bool multi = bc < B;
+  const size_t pw = L * bc * n * wb;
+  CallWs ws(out0);
+  if (nz)
+    if (int rc = ws.get(L * pw + (2 * tg + 1 + (multi ? 1 : 0)) * pw)) return rc;
+  char* D = (char*)ws.p;
+  char* ACC = D + L * pw;
+  char* TMP = ACC + 2 * tg * pw;
+  char* X0 = TMP + pw;
+  for (size_t t = 0; t < n_steps; ++t) {
+    if (steps[t] != 0) continue;
+    for (int o = 0; o < 2; ++o)
+      LAUNCH(k.t, rnt::K_COPY,
+             rnt::launch_copy_rows(k.s, (char*)out[o]->data + t * B * n * wb, out_ls * wb, src[o]->data,
+                                   full_ls * wb, full_ls * wb, L),
+             "step-0 copy");
+  }
+  for (size_t p0 = 0; nz && p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    rnt::Launch kc = k;
+    kc.B = c;
+    const uint64_t cls = (uint64_t)c * n;
+    const char* x0 = (const char*)c0->data + p0 * n * wb;
+    if (multi) {
+      LAUNCH(kc.t, rnt::K_COPY, rnt::launch_copy_rows(kc.s, X0, cls * wb, x0, full_ls * wb, cls * wb, L),
+             "chunk gather");
+      x0 = X0;
+    }
+    auto finish = [&](size_t t, char* A0, char* A1) -> int {
+      const uint64_t g = rotation_exponent(steps[t], two_n);
+      if (int rc = inv_add_raw(kc, A0, cls, x0)) return rc;
+      if (int rc = inv_raw(kc, A1, cls)) return rc;
+      char* A[2] = {A0, A1};
+      for (int o = 0; o < 2; ++o) {
+        char* dst = (char*)out[o]->data + (t * B + p0) * n * wb;
+        if (out_ls == cls) {  // one step, one chunk
+          LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, dst, A[o], g), "automorphism");
+        } else {  // (the automorphism launch takes no limb stride)
+          LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, TMP, A[o], g), "automorphism");
+          LAUNCH(kc.t, rnt::K_COPY, rnt::launch_copy_rows(kc.s, dst, out_ls * wb, TMP, cls * wb, cls * wb, L),
+                 "rotation into its output polys");
+        }
+      }
+      return RNT_OK;
+    };
+    if (int rc = hoist_chunk(kc, D, ACC, (const char*)c1->data + p0 * n * wb, full_ls, steps, n_steps, keys_a,
+                             keys_b, finish))
+      return rc;
+  }
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
+// ---------------------------------------------------------------------------
 // baby-step giant-step linear transform:
 //   R_i = rotate(ct, baby[i]),  V_j = sum_i P[j][i] R_i,  out = sum_j rotate(V_j, giant[j])
 // ---------------------------------------------------------------------------
@@ -2693,7 +2882,7 @@ void key_views(rnt_buf kv[2], const rnt_buf* c0, const rnt_buf* keys_a, const rn
 int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
                      const int32_t* baby, size_t n1, const int32_t* giant, size_t n2, const BsgsPlan& plan,
                      const char* dm, const rnt_buf* bka, const rnt_buf* bkb, const rnt_buf* gka,
-                     const rnt_buf* gkb, char* ws) {
+                     const rnt_buf* gkb, char* ws, bool hoisted) {
   rnt::Launch k = launch_for(c0);
   const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
   const size_t pw = L * B * n * wb;
@@ -2701,6 +2890,8 @@ int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_
   char* RB = ws;
   char* VB = RB + 2 * n1 * pw;
   char* T = VB + 2 * plan.nv * pw;
+  char* HD = T + 2 * pw;      // hoisted: the digits (L blocks) | 2 kHoistT accumulator blocks
+  char* HACC = HD + L * pw;
   auto view = [&](rnt_buf& v, char* p) {
     v.ctx = c0->ctx;
     v.n_polys = B;
@@ -2715,6 +2906,8 @@ int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_
     if (baby[i] == 0) {
       for (int o = 0; o < 2; ++o)
         if (int rc = copy_rows(k, R[o], ls, src[o]->data, ls, ls, L)) return rc;
+    } else if (hoisted) {
+      continue;  // below: one decomposition for all of them
     } else {
       key_views(kv, c0, bka, bkb, i);
       view(a[0], R[0]);
@@ -2723,6 +2916,21 @@ int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_
     }
     for (int o = 0; o < 2; ++o)
       if (int rc = fwd_raw(k, R[o], ls)) return rc;
+  }
+  if (hoisted) {
+    auto finish = [&](size_t i, char* A0, char* A1) -> int {
+      const uint64_t g = rotation_exponent(baby[i], 2 * (uint64_t)n);
+      if (int rc = inv_add_raw(k, A0, ls, c0->data)) return rc;
+      if (int rc = inv_raw(k, A1, ls)) return rc;
+      char* A[2] = {A0, A1};
+      for (int o = 0; o < 2; ++o) {
+        char* R = RB + (2 * i + o) * pw;
+        LAUNCH(k.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(k, R, A[o], g), "automorphism");
+        if (int rc = fwd_raw(k, R, ls)) return rc;
+      }
+      return RNT_OK;
+    };
+    if (int rc = hoist_chunk(k, HD, HACC, c1->data, ls, baby, n1, bka, bkb, finish)) return rc;
   }
   if (int rc = bsgs_inner_sums(k, plan, VB, RB, pw, dm, n1, n2)) return rc;
   for (size_t v = 0; v < 2 * plan.nv; ++v)
@@ -2767,7 +2975,7 @@ int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_
 int ct_bsgs_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1, const int32_t* baby,
                   size_t n1, const int32_t* giant, size_t n2, const BsgsPlan& plan, const char* dm,
                   const char* one, const rnt_buf* bka, const rnt_buf* bkb, const rnt_buf* gka,
-                  const rnt_buf* gkb, char* ws, size_t bc) {
+                  const rnt_buf* gkb, char* ws, size_t bc, bool hoisted) {
   rnt::Launch k = launch_for(c0);
   const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
   const size_t pw = L * bc * n * wb;
@@ -2788,6 +2996,7 @@ int ct_bsgs_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf
   char* SEED = take(1);
   char* RB = take(2 * n1);
   char* VB = take(2 * plan.nv);
+  char* HACC = hoisted ? take(2 * rnt::kHoistT) : nullptr;  // (the digits take S)
   char* KS = p;
   const rnt_buf* src[2] = {c0, c1};
   rnt_buf* out[2] = {out0, out1};
@@ -2820,6 +3029,8 @@ int ct_bsgs_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf
         for (int o = 0; o < 2; ++o)
           if (int rc = copy_rows(kc, R[o], cls, x[o], multi ? cls : full_ls, cls, L)) return rc;
         zero_done = R[0];
+      } else if (hoisted) {
+        continue;  // below: one decomposition for all of them
       } else {
         const uint64_t g = rotation_exponent(baby[i], two_n);
         LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG1, x[1], g), "automorphism");
@@ -2835,6 +3046,21 @@ int ct_bsgs_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf
       }
       for (int o = 0; o < 2; ++o)
         if (int rc = fwd_raw(kc, R[o], cls)) return rc;
+    }
+    if (hoisted) {
+      auto finish = [&](size_t i, char* A0, char* A1) -> int {
+        const uint64_t g = rotation_exponent(baby[i], two_n);
+        if (int rc = inv_add_raw(kc, A0, cls, x[0])) return rc;
+        if (int rc = inv_raw(kc, A1, cls)) return rc;
+        char* A[2] = {A0, A1};
+        for (int o = 0; o < 2; ++o) {
+          char* R = RB + (2 * i + o) * pw;
+          LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, R, A[o], g), "automorphism");
+          if (int rc = fwd_raw(kc, R, cls)) return rc;
+        }
+        return RNT_OK;
+      };
+      if (int rc = hoist_chunk(kc, S, HACC, x[1], cls, baby, n1, bka, bkb, finish)) return rc;
     }
     // inner sums, back to coefficients for the giant decomposition
     if (int rc = bsgs_inner_sums(kc, plan, VB, RB, pw, dm, n1, n2)) return rc;
@@ -2902,11 +3128,11 @@ int check_stage_keys(const rnt_buf* c0, const int32_t* steps, size_t count, cons
 
 }  // namespace
 
-extern "C" int rnt_ct_linear_bsgs(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
-                                  const int32_t* baby_steps, size_t n_baby, const int32_t* giant_steps,
-                                  size_t n_giant, const rnt_buf* diag, const rnt_buf* baby_keys_a,
-                                  const rnt_buf* baby_keys_b, const rnt_buf* giant_keys_a,
-                                  const rnt_buf* giant_keys_b) {
+static int ct_linear_bsgs_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                               const int32_t* baby_steps, size_t n_baby, const int32_t* giant_steps,
+                               size_t n_giant, const rnt_buf* diag, const rnt_buf* baby_keys_a,
+                               const rnt_buf* baby_keys_b, const rnt_buf* giant_keys_a,
+                               const rnt_buf* giant_keys_b, bool hoisted) {
   const rnt_buf* all[4] = {out0, out1, c0, c1};
   for (const rnt_buf* b : all)
     if (int rc = check_buf(b, "rnt_ct_linear_bsgs")) return rc;
@@ -2948,7 +3174,10 @@ extern "C" int rnt_ct_linear_bsgs(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c
   // and the gathered chunk (composed: the two rotation outputs); with the
   // key-switch scratch they stay within the key-switch workspace cap, one
   // ciphertext being the floor
-  const size_t planes = 2 * n_baby + 2 * plan.nv + (composed ? 2 : 4);
+  // (hoisted: the accumulator pairs of one k_hoist_mac group; the digits take
+  // the key-switch scratch's S, which the whole-plane rings lack)
+  const size_t planes =
+      2 * n_baby + 2 * plan.nv + (composed ? 2 : 4) + (hoisted ? 2 * rnt::kHoistT + (composed ? L : 0) : 0);
   size_t bc = B;
   if (!composed) {
     const size_t per = (planes * L + L * L + 2 * L) * n * wb;
@@ -2971,16 +3200,34 @@ extern "C" int rnt_ct_linear_bsgs(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c
   int rc;
   if (composed) {
     rc = ct_bsgs_composed(out0, out1, c0, c1, baby_steps, n_baby, giant_steps, n_giant, plan, dm, baby_keys_a,
-                          baby_keys_b, giant_keys_a, giant_keys_b, dm + dm_bytes);
+                          baby_keys_b, giant_keys_a, giant_keys_b, dm + dm_bytes, hoisted);
   } else {
     char* one = dm + dm_bytes;
     if (plan.any_rot) LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_mont_one(k, one), "Montgomery one");
     rc = ct_bsgs_fused(out0, out1, c0, c1, baby_steps, n_baby, giant_steps, n_giant, plan, dm, one, baby_keys_a,
-                       baby_keys_b, giant_keys_a, giant_keys_b, one + one_bytes, bc);
+                       baby_keys_b, giant_keys_a, giant_keys_b, one + one_bytes, bc, hoisted);
   }
   if (rc) return rc;
   out0->in_ntt = out1->in_ntt = 0;
   return RNT_OK;
+}
+
+extern "C" int rnt_ct_linear_bsgs(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                  const int32_t* baby_steps, size_t n_baby, const int32_t* giant_steps,
+                                  size_t n_giant, const rnt_buf* diag, const rnt_buf* baby_keys_a,
+                                  const rnt_buf* baby_keys_b, const rnt_buf* giant_keys_a,
+                                  const rnt_buf* giant_keys_b) {
+  return ct_linear_bsgs_body(out0, out1, c0, c1, baby_steps, n_baby, giant_steps, n_giant, diag, baby_keys_a,
+                             baby_keys_b, giant_keys_a, giant_keys_b, false);
+}
+
+extern "C" int rnt_ct_linear_bsgs_hoisted(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                          const int32_t* baby_steps, size_t n_baby, const int32_t* giant_steps,
+                                          size_t n_giant, const rnt_buf* diag, const rnt_buf* baby_keys_a,
+                                          const rnt_buf* baby_keys_b, const rnt_buf* giant_keys_a,
+                                          const rnt_buf* giant_keys_b) {
+  return ct_linear_bsgs_body(out0, out1, c0, c1, baby_steps, n_baby, giant_steps, n_giant, diag, baby_keys_a,
+                             baby_keys_b, giant_keys_a, giant_keys_b, true);
 }
 
 extern "C" int rnt_copy_polys(rnt_buf* dst, size_t dst_first, const rnt_buf* src, size_t src_first,

@@ -123,7 +123,7 @@ enum KernelId {
   K_COL_FWD, K_ROW_FWD, K_ROW_INV, K_ROW_MUL, K_COL_INV, K_ELEMENTWISE, K_RESCALE,
   K_AUTOMORPHISM, K_KS_DECOMPOSE, K_KS_ROWS, K_TENSOR_ROWS, K_IMPORT, K_EXPORT, K_CRT,
   K_SFFT, K_SAMPLE, K_COPY, K_PLANE_FUSED, K_MF_NTT_FWD, K_MF_NTT_INV, K_WHOLE_FWD, K_WHOLE_INV, K_WHOLE_MUL,
-  K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_COUNT
+  K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_COUNT
 };
 
 struct Prof {
@@ -278,6 +278,11 @@ hipError_t launch_elementwise(const Launch& k, int op, void* out, const void* a,
 // Plain device copy of `bytes` (16-byte aligned pointers, bytes % 16 == 0):
 // every lane moves 4 x 16 B, loads before stores (Clone, rnt_copy).
 hipError_t launch_copy(hipStream_t s, void* dst, const void* src, uint64_t bytes);
+// `rows` runs of run_bytes bytes in one launch (k_copy_rows), row r at + r
+// pitch on either side; everything a multiple of 4 bytes, 16-byte accesses
+// where everything is a multiple of 16.  dst and src do not overlap.
+hipError_t launch_copy_rows(hipStream_t s, void* dst, uint64_t dst_pitch_bytes, const void* src,
+                            uint64_t src_pitch_bytes, uint64_t run_bytes, size_t rows);
 // k.L = limbs of the input; output has k.L - 1 (same poly count / stride B*N).
 hipError_t launch_rescale(const Launch& k, void* out, const void* in);
 // Centred CRT of every coefficient (coefficient-domain `in`, k.L limbs) into
@@ -334,6 +339,18 @@ constexpr uint32_t kBsgsJt = 4;
 hipError_t launch_bsgs_mac(const Launch& k, void* const* outs, uint32_t nj, uint32_t accum_mask,
                            const void* x, uint64_t blk_words, const void* m, uint64_t m_ls,
                            uint32_t n_baby);
+// The hoisted rotations (rnt_ct_rotate_hoisted).  launch_hoist_digits
+// (k_hoist_digits): D[j][i][p] = (limb i, poly p of c1) 2^w mod q_j for j < k.L,
+// i < k.src_limbs(), p < k.B; c1 coefficient-domain at limb stride src_ls, D
+// [k.L][k.src_limbs()][k.B][N], to be transformed forward as a buffer of k.L
+// limbs and src_limbs k.B polys.  launch_hoist_mac (k_hoist_mac), nt <= kHoistT
+// steps in one launch: acc0[t] = sum_i D^[j][i] (.) key_b[t][i][j], acc1[t] with
+// key_a ([k.L][k.B][N] each, NTT domain, canonical); key_*[t] points at step t's
+// hoisting-form key (source limb i at + i N words, limb j at + j key_ls).
+constexpr uint32_t kHoistT = 4;
+hipError_t launch_hoist_digits(const Launch& k, void* D, const void* c1, uint64_t src_ls);
+hipError_t launch_hoist_mac(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt, const void* d,
+                            const void* const* key_a, const void* const* key_b, uint64_t key_ls);
 // out[l][i] = 2^w mod q_l over [k.L][N]: the Montgomery-form plaintext 1.
 hipError_t launch_mont_one(const Launch& k, void* out);
 // The whole-plane key-switch at 2^10 <= N <= 2^13 (k_ks_whole, one launch,

@@ -1867,6 +1867,128 @@ k_mont_one(W* __restrict__ out, TabPtrs<W> tp, uint32_t log_n) {
   out[((uint64_t)l << log_n) + i] = tp.lc[l].rmod;
 }
 
+// The gadget digits of the hoisted rotations before their forward transform:
+// D[j][i][p] = (c1 limb i, poly p) 2^w mod q_j, canonical, for every target
+// limb j < L.  Grid (16-byte vectors of a source limb's chunk, source limb i);
+// a thread reads its source vector once and writes the L residues.  c1 is the
+// chunk's first poly at limb stride src_ls; D is [L][gridDim.y][B][N].  The
+// factor 2^w (Montgomery form, linear through the transform) is what makes
+// k_hoist_mac's Montgomery products with the canonical keys canonical.
+template <class W, bool VEC>
+__global__ void __launch_bounds__(256)
+k_hoist_digits(W* __restrict__ D, const W* __restrict__ c1, TabPtrs<W> tp, uint64_t limb_words,
+               uint64_t src_ls, uint32_t L) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint32_t s = blockIdx.y;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= limb_words) return;
+  W xv[V];
+  if constexpr (VEC) {
+    const uint4 xa = *reinterpret_cast<const uint4*>(c1 + (uint64_t)s * src_ls + i);
+    __builtin_memcpy(xv, &xa, 16);
+  } else {
+    xv[0] = c1[(uint64_t)s * src_ls + i];
+  }
+  for (uint32_t j = 0; j < L; ++j) {
+    const LimbConst<W> lc = tp.lc[j];
+    W* dp = D + ((uint64_t)j * gridDim.y + s) * limb_words + i;
+    W r[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) r[v] = shoup_mul<W>(xv[v], lc.rmod, lc.rmod_p, lc.q);
+    if constexpr (VEC) {
+      uint4 o;
+      __builtin_memcpy(&o, r, 16);
+      *reinterpret_cast<uint4*>(dp) = o;
+    } else {
+      dp[0] = r[0];
+    }
+  }
+}
+
+// The gadget sums of up to HOIST_T hoisted rotations of one chunk in the NTT
+// domain: acc0[t] = sum_i D^[j][i] (.) key_b[t][i], acc1[t] with key_a, for
+// t < nt.  d is the transformed Montgomery-form digits ([L][Ls][B][N]); the
+// keys are in hoisting form, key_*[t] pointing at (source limb 0, limb 0) of
+// step t's key: source limb i at + i N, limb j at + j key_ls, the same plane
+// for every poly of the batch.  Grid (16-byte vectors of a target limb's
+// chunk, target limb j); a thread holds one vector position, loops over the Ls
+// source limbs, reads each digit vector once and keeps 2 HOIST_T accumulators.
+// mont_mul(d 2^w, key) is the canonical product and the sums stay canonical
+// through add_mod.  No gather: the pre-rotated keys make it a stream.
+constexpr int HOIST_T = (int)kHoistT;
+template <class W>
+struct HoistArgs {
+  const W* key_b[HOIST_T];
+  const W* key_a[HOIST_T];
+  W* acc0[HOIST_T];
+  W* acc1[HOIST_T];
+};
+template <class W, bool VEC>
+__global__ void __launch_bounds__(256)
+k_hoist_mac(HoistArgs<W> a, const W* __restrict__ d, TabPtrs<W> tp, uint32_t log_n, uint64_t limb_words,
+            uint64_t key_ls, uint32_t Ls, uint32_t nt) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint32_t j = blockIdx.y;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= limb_words) return;
+  const LimbConst<W> lc = tp.lc[j];
+  const uint64_t N = 1ull << log_n;
+  const W* dp = d + (uint64_t)j * Ls * limb_words + i;
+  const uint64_t ko = (uint64_t)j * key_ls + (i & (N - 1));  // V divides N: one plane
+  W acc0[HOIST_T][V], acc1[HOIST_T][V];
+#pragma unroll
+  for (int t = 0; t < HOIST_T; ++t)
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc0[t][v] = acc1[t][v] = (W)0;
+  for (uint32_t s = 0; s < Ls; ++s) {
+    W xv[V];
+    if constexpr (VEC) {
+      const uint4 xa = *reinterpret_cast<const uint4*>(dp + (uint64_t)s * limb_words);
+      __builtin_memcpy(xv, &xa, 16);
+    } else {
+      xv[0] = dp[(uint64_t)s * limb_words];
+    }
+#pragma unroll
+    for (int t = 0; t < HOIST_T; ++t) {
+      if ((uint32_t)t < nt) {  // (uniform)
+        const W* bq = a.key_b[t] + ko + (uint64_t)s * N;
+        const W* aq = a.key_a[t] + ko + (uint64_t)s * N;
+        W bv[V], av[V];
+        if constexpr (VEC) {
+          const uint4 b4 = *reinterpret_cast<const uint4*>(bq);
+          const uint4 a4 = *reinterpret_cast<const uint4*>(aq);
+          __builtin_memcpy(bv, &b4, 16);
+          __builtin_memcpy(av, &a4, 16);
+        } else {
+          bv[0] = bq[0];
+          av[0] = aq[0];
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          acc0[t][v] = add_mod<W>(acc0[t][v], mont_mul<W>(xv[v], bv[v], lc.q, lc.qinv), lc.q);
+          acc1[t][v] = add_mod<W>(acc1[t][v], mont_mul<W>(xv[v], av[v], lc.q, lc.qinv), lc.q);
+        }
+      }
+    }
+  }
+  const uint64_t g = (uint64_t)j * limb_words + i;
+#pragma unroll
+  for (int t = 0; t < HOIST_T; ++t) {
+    if ((uint32_t)t < nt) {
+      if constexpr (VEC) {
+        uint4 r0, r1;
+        __builtin_memcpy(&r0, acc0[t], 16);
+        __builtin_memcpy(&r1, acc1[t], 16);
+        *reinterpret_cast<uint4*>(a.acc0[t] + g) = r0;
+        *reinterpret_cast<uint4*>(a.acc1[t] + g) = r1;
+      } else {
+        a.acc0[t][g] = acc0[t][0];
+        a.acc1[t][g] = acc1[t][0];
+      }
+    }
+  }
+}
+
 // rescale_into (poly.rs:212-225): out[l] = (c_l - (c_last mod q_l)) * q_last^-1.
 template <class W>
 __global__ void __launch_bounds__(256)
@@ -2339,6 +2461,61 @@ static hipError_t mont_one_t(const Launch& k, void* out) {
   return hipGetLastError();
 }
 
+template <class W>
+static hipError_t hoist_digits_t(const Launch& k, void* D, const void* c1, uint64_t src_ls) {
+  const uint64_t N = 1ull << k.t->log_n;
+  const uint64_t limb_words = (uint64_t)k.B * N;
+  const size_t Ls = k.src_limbs();
+  if (limb_words == 0 || k.L == 0 || Ls == 0) return hipSuccess;
+  if (src_ls < limb_words) return hipErrorInvalidValue;
+  constexpr int V = 16 / (int)sizeof(W);
+  // 16-byte accesses: whole vectors within a plane, every plane 16-byte aligned
+  const bool vec = N % V == 0 && src_ls % V == 0 && ((uintptr_t)D | (uintptr_t)c1) % 16 == 0;
+  const uint64_t per = vec ? limb_words / V : limb_words;
+  const uint64_t bx = (per + 255) / 256;
+  if (bx > 0x7fffffffull || Ls > 65535) return hipErrorInvalidConfiguration;
+  const dim3 grid((unsigned)bx, (unsigned)Ls);
+#define RNT_HD(VEC)                                                                                   \
+  hipLaunchKernelGGL((k_hoist_digits<W, VEC>), grid, dim3(256), 0, k.s, (W*)D, (const W*)c1,          \
+                     tab_ptrs<W>(k.t), limb_words, src_ls, (uint32_t)k.L)
+  if (vec) RNT_HD(true); else RNT_HD(false);
+#undef RNT_HD
+  return hipGetLastError();
+}
+
+template <class W>
+static hipError_t hoist_mac_t(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt,
+                              const void* d, const void* const* key_a, const void* const* key_b,
+                              uint64_t key_ls) {
+  const uint64_t N = 1ull << k.t->log_n;
+  const uint64_t limb_words = (uint64_t)k.B * N;
+  const size_t Ls = k.src_limbs();
+  if (nt == 0 || nt > (uint32_t)HOIST_T || Ls == 0 || key_ls < Ls * N) return hipErrorInvalidValue;
+  if (limb_words == 0 || k.L == 0) return hipSuccess;
+  constexpr int V = 16 / (int)sizeof(W);
+  HoistArgs<W> a{};
+  uintptr_t align = (uintptr_t)d;
+  for (uint32_t t = 0; t < nt; ++t) {
+    a.key_a[t] = (const W*)key_a[t];
+    a.key_b[t] = (const W*)key_b[t];
+    a.acc0[t] = (W*)acc0[t];
+    a.acc1[t] = (W*)acc1[t];
+    align |= (uintptr_t)key_a[t] | (uintptr_t)key_b[t] | (uintptr_t)acc0[t] | (uintptr_t)acc1[t];
+  }
+  // 16-byte accesses: whole vectors within a plane, every plane and block 16-byte aligned
+  const bool vec = N % V == 0 && key_ls % V == 0 && align % 16 == 0;
+  const uint64_t per = vec ? limb_words / V : limb_words;
+  const uint64_t bx = (per + 255) / 256;
+  if (bx > 0x7fffffffull || k.L > 65535) return hipErrorInvalidConfiguration;
+  const dim3 grid((unsigned)bx, (unsigned)k.L);
+#define RNT_HM(VEC)                                                                              \
+  hipLaunchKernelGGL((k_hoist_mac<W, VEC>), grid, dim3(256), 0, k.s, a, (const W*)d,             \
+                     tab_ptrs<W>(k.t), k.t->log_n, limb_words, key_ls, (uint32_t)Ls, nt)
+  if (vec) RNT_HM(true); else RNT_HM(false);
+#undef RNT_HM
+  return hipGetLastError();
+}
+
 // Clone: 4 x 16 B per lane, all four loads issued before the stores.
 __global__ void __launch_bounds__(256)
 k_copy16(uint4* __restrict__ dst, const uint4* __restrict__ src, uint64_t n16) {
@@ -2359,6 +2536,38 @@ hipError_t launch_copy(hipStream_t s, void* dst, const void* src, uint64_t bytes
   if (blocks > 0x7fffffffull) return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(k_copy16, dim3((unsigned)blocks), dim3(256), 0, s, (uint4*)dst,
                      (const uint4*)src, n16);
+  return hipGetLastError();
+}
+
+// Strided copy: gridDim.y rows of `run` elements (16 bytes, or 4 where a
+// pointer, a pitch or the run is not a multiple of 16), row r at + r pitch
+// elements on either side -- polys [first, first + count) of every limb of a
+// [L][B][N] buffer in one launch.
+template <class E>
+__global__ void __launch_bounds__(256)
+k_copy_rows(E* __restrict__ dst, const E* __restrict__ src, uint64_t run, uint64_t dst_pitch,
+            uint64_t src_pitch) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= run) return;
+  dst[(uint64_t)blockIdx.y * dst_pitch + i] = src[(uint64_t)blockIdx.y * src_pitch + i];
+}
+
+hipError_t launch_copy_rows(hipStream_t s, void* dst, uint64_t dst_pitch_bytes, const void* src,
+                            uint64_t src_pitch_bytes, uint64_t run_bytes, size_t rows) {
+  if (run_bytes == 0 || rows == 0) return hipSuccess;
+  if (rows > 65535 || dst_pitch_bytes < run_bytes || src_pitch_bytes < run_bytes) return hipErrorInvalidValue;
+  const uint64_t all = (uint64_t)(uintptr_t)dst | (uint64_t)(uintptr_t)src | dst_pitch_bytes | src_pitch_bytes | run_bytes;
+  if (all % 4 != 0) return hipErrorInvalidValue;  // (words are 4 or 8 bytes)
+  const uint64_t eb = all % 16 == 0 ? 16 : 4;
+  const uint64_t bx = (run_bytes / eb + 255) / 256;
+  if (bx > 0x7fffffffull) return hipErrorInvalidConfiguration;
+  const dim3 grid((unsigned)bx, (unsigned)rows);
+  if (eb == 16)
+    hipLaunchKernelGGL((k_copy_rows<uint4>), grid, dim3(256), 0, s, (uint4*)dst, (const uint4*)src, run_bytes / 16,
+                       dst_pitch_bytes / 16, src_pitch_bytes / 16);
+  else
+    hipLaunchKernelGGL((k_copy_rows<uint32_t>), grid, dim3(256), 0, s, (uint32_t*)dst, (const uint32_t*)src,
+                       run_bytes / 4, dst_pitch_bytes / 4, src_pitch_bytes / 4);
   return hipGetLastError();
 }
 
@@ -2904,6 +3113,14 @@ hipError_t launch_bsgs_mac(const Launch& k, void* const* outs, uint32_t nj, uint
                            uint32_t n_baby) {
   RNT_WIDE(bsgs_mac_t<uint32_t>(k, outs, nj, accum_mask, x, blk_words, m, m_ls, n_baby),
            bsgs_mac_t<uint64_t>(k, outs, nj, accum_mask, x, blk_words, m, m_ls, n_baby));
+}
+hipError_t launch_hoist_digits(const Launch& k, void* D, const void* c1, uint64_t src_ls) {
+  RNT_WIDE(hoist_digits_t<uint32_t>(k, D, c1, src_ls), hoist_digits_t<uint64_t>(k, D, c1, src_ls));
+}
+hipError_t launch_hoist_mac(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt, const void* d,
+                            const void* const* key_a, const void* const* key_b, uint64_t key_ls) {
+  RNT_WIDE(hoist_mac_t<uint32_t>(k, acc0, acc1, nt, d, key_a, key_b, key_ls),
+           hoist_mac_t<uint64_t>(k, acc0, acc1, nt, d, key_a, key_b, key_ls));
 }
 hipError_t launch_mont_one(const Launch& k, void* out) {
   RNT_WIDE(mont_one_t<uint32_t>(k, out), mont_one_t<uint64_t>(k, out));

@@ -44,6 +44,8 @@ __all__ = [
     "RnsGadgetKeySet",
     "linear_transform",
     "linear_transform_bsgs",
+    "linear_transform_bsgs_hoisted",
+    "rotate_ciphertext_hoisted",
     "bsgs_diagonal_rows",
     "rescale_ciphertext",
     "Plaintext",
@@ -571,14 +573,30 @@ class RnsGadgetKey:
     """RnsGadgetRelinKey / RnsGadgetRotationKey (engine.rs:224-253).
 
     ``a`` and ``b`` are RnsPoly batches holding the L key polynomials; they
-    are made NTT-resident once by :meth:`prepare`.
+    are made NTT-resident once by :meth:`prepare`.  ``hoisted`` says which
+    form the key is in: the ordinary prepared one, or (after
+    :meth:`prepare_hoisted`) the hoisting form of the hoisted rotations.
     """
 
     def __init__(self, a: RnsPoly, b: RnsPoly, rotation: Optional[int] = None):
         self.a = a
         self.b = b
         self.rotation = rotation
+        self.hoisted = False
         check(load().rnt_key_prepare(a.handle, b.handle))
+
+    def prepare_hoisted(self) -> "RnsGadgetKey":
+        """Turn this rotation key into its hoisting form
+        ``NTT(sigma_k^-1(key))``, k the key's ``rotation``
+        (rnt_key_prepare_hoisted), in place.  The ordinary form is gone: a
+        caller that needs both keeps a second key."""
+        if self.rotation is None:
+            raise ValueError("prepare_hoisted: not a rotation key (no rotation step)")
+        if self.hoisted:
+            raise ValueError("prepare_hoisted: the key is in hoisting form already")
+        check(load().rnt_key_prepare_hoisted(self.a.handle, self.b.handle, int(self.rotation)))
+        self.hoisted = True
+        return self
 
     @classmethod
     def from_channels(cls, a_channels, b_channels, basis: RnsBasis, rotation: Optional[int] = None):
@@ -613,8 +631,18 @@ def mul_ciphertexts_gadget(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsGadgetKey) 
     return Ciphertext(out0, out1, ct1.logp + ct2.logp, ct1.logq)
 
 
+def _require_form(keys, hoisted: bool, what: str) -> None:
+    """``keys`` (an RnsGadgetKey or RnsGadgetKeySet) must be in the form the
+    call reads: the library cannot tell the two apart and would compute a
+    wrong result from the wrong one."""
+    if bool(getattr(keys, "hoisted", False)) != hoisted:
+        raise ValueError(f"{what}: needs {'hoisting-form' if hoisted else 'ordinary prepared'} keys, got "
+                         f"{'ordinary prepared' if hoisted else 'hoisting-form'} ones")
+
+
 def rotate_ciphertext(ct: Ciphertext, rotk: RnsGadgetKey) -> Ciphertext:
     """engine.rs:412-463."""
+    _require_form(rotk, False, "rotate_ciphertext")
     basis = ct.c0.basis
     out0, out1 = ct.c0._like(basis), ct.c0._like(basis)
     check(load().rnt_ct_rotate(out0.handle, out1.handle, ct.c0.handle, ct.c1.handle,
@@ -627,12 +655,18 @@ class RnsGadgetKeySet:
     rnt_ct_linear reads them: term t's L key polys at ``[t L, (t + 1) L)`` of
     ``a`` / ``b`` (rnt_copy_polys, no host round trip).  ``keys[t]`` is a
     prepared :class:`RnsGadgetKey` whose ``rotation`` is the term's step, or
-    None for a step-0 term (its slot stays zero and is never read)."""
+    None for a step-0 term (its slot stays zero and is never read).  The keys
+    are all ordinary or all in hoisting form (``hoisted``); a set without any
+    key serves both."""
 
     def __init__(self, keys: Sequence[Optional[RnsGadgetKey]], basis: Optional[RnsBasis] = None):
         keys = list(keys)
         if not keys:
             raise ValueError("RnsGadgetKeySet: no terms")
+        forms = {bool(getattr(k, "hoisted", False)) for k in keys if k is not None}
+        if len(forms) > 1:
+            raise ValueError("RnsGadgetKeySet: a mix of hoisting-form and ordinary keys")
+        self.hoisted = forms.pop() if forms else False
         first = next((k for k in keys if k is not None), None)
         if first is None and basis is None:
             raise ValueError("RnsGadgetKeySet: a set of step-0 terms needs the basis")
@@ -661,6 +695,8 @@ def linear_transform(ct: Ciphertext, diag: RnsPoly, keyset: RnsGadgetKeySet,
     """``sum_t diag[t] * rotate_ciphertext(ct, keyset.steps[t])`` for every
     ciphertext of the batch (rnt_ct_linear): ``diag`` holds one NTT-domain
     plaintext poly per term.  ``out`` may be ``ct`` itself (in place)."""
+    if keyset.a is not None:
+        _require_form(keyset, False, "linear_transform")
     basis = ct.c0.basis
     if out is None:
         out = Ciphertext(ct.c0._like(basis), ct.c0._like(basis), ct.logp, ct.logq)
@@ -684,6 +720,25 @@ def linear_transform_bsgs(ct: Ciphertext, diag: RnsPoly, baby_keyset: RnsGadgetK
     n1 n2 diagonals ``g[j] + b[i]``.  ``diag`` holds the n2 n1 NTT-domain
     plaintext polys (:func:`bsgs_diagonal_rows` gives their slots).  ``out``
     may be ``ct`` itself (in place)."""
+    return _linear_bsgs(ct, diag, baby_keyset, giant_keyset, out, False)
+
+
+def linear_transform_bsgs_hoisted(ct: Ciphertext, diag: RnsPoly, baby_keyset: RnsGadgetKeySet,
+                                  giant_keyset: RnsGadgetKeySet, out: Optional[Ciphertext] = None) -> Ciphertext:
+    """:func:`linear_transform_bsgs` with the baby rotations hoisted
+    (rnt_ct_linear_bsgs_hoisted): one gadget decomposition of ``ct`` serves
+    every baby step.  ``baby_keyset`` is in hoisting form, ``giant_keyset``
+    ordinary.  A valid transform with the same noise, but not
+    ``linear_transform_bsgs``' words."""
+    return _linear_bsgs(ct, diag, baby_keyset, giant_keyset, out, True)
+
+
+def _linear_bsgs(ct, diag, baby_keyset, giant_keyset, out, hoisted: bool):
+    name = "linear_transform_bsgs_hoisted" if hoisted else "linear_transform_bsgs"
+    if baby_keyset.a is not None:
+        _require_form(baby_keyset, hoisted, f"{name} (baby keys)")
+    if giant_keyset.a is not None:
+        _require_form(giant_keyset, False, f"{name} (giant keys)")
     basis = ct.c0.basis
     if out is None:
         out = Ciphertext(ct.c0._like(basis), ct.c0._like(basis), ct.logp, ct.logq)
@@ -693,9 +748,31 @@ def linear_transform_bsgs(ct: Ciphertext, diag: RnsPoly, baby_keyset: RnsGadgetK
     def h(p):
         return p.handle if p is not None else None
 
-    check(load().rnt_ct_linear_bsgs(out.c0.handle, out.c1.handle, ct.c0.handle, ct.c1.handle, baby,
-                                    len(baby_keyset.steps), giant, len(giant_keyset.steps), diag.handle,
-                                    h(baby_keyset.a), h(baby_keyset.b), h(giant_keyset.a), h(giant_keyset.b)))
+    fn = load().rnt_ct_linear_bsgs_hoisted if hoisted else load().rnt_ct_linear_bsgs
+    check(fn(out.c0.handle, out.c1.handle, ct.c0.handle, ct.c1.handle, baby, len(baby_keyset.steps), giant,
+             len(giant_keyset.steps), diag.handle, h(baby_keyset.a), h(baby_keyset.b), h(giant_keyset.a),
+             h(giant_keyset.b)))
+    return out
+
+
+def rotate_ciphertext_hoisted(ct: Ciphertext, keyset: RnsGadgetKeySet,
+                              out: Optional[Ciphertext] = None) -> Ciphertext:
+    """The hoisted rotations of every ciphertext of the batch by each of
+    ``keyset.steps`` with one gadget decomposition (rnt_ct_rotate_hoisted):
+    a batch of ``n_steps * B``, rotation t of ciphertext b at poly
+    ``t * B + b``.  ``keyset`` is in hoisting form
+    (``generate_rotation_key_set(..., hoisted=True)``).  Valid rotations with
+    ``rotate_ciphertext``'s noise, not its words."""
+    if keyset.a is not None:
+        _require_form(keyset, True, "rotate_ciphertext_hoisted")
+    basis = ct.c0.basis
+    n_out = len(keyset.steps) * ct.c0.n_polys
+    if out is None:
+        out = Ciphertext(RnsPoly(basis, n_out, _uninit=True), RnsPoly(basis, n_out, _uninit=True), ct.logp, ct.logq)
+    steps = (ctypes.c_int32 * len(keyset.steps))(*keyset.steps)
+    check(load().rnt_ct_rotate_hoisted(out.c0.handle, out.c1.handle, ct.c0.handle, ct.c1.handle, steps,
+                                       len(keyset.steps), keyset.a.handle if keyset.a is not None else None,
+                                       keyset.b.handle if keyset.b is not None else None))
     return out
 
 

@@ -24,7 +24,8 @@ from typing import Optional
 import numpy as np
 
 from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsGadgetKeySet, RnsPoly,
-               bsgs_diagonal_rows, linear_transform, linear_transform_bsgs, mul_ciphertexts_gadget, rescale_ciphertext, rotate_ciphertext)
+               bsgs_diagonal_rows, linear_transform, linear_transform_bsgs, linear_transform_bsgs_hoisted,
+               mul_ciphertexts_gadget, rescale_ciphertext, rotate_ciphertext, rotate_ciphertext_hoisted)
 
 
 @dataclass
@@ -158,11 +159,24 @@ class CkksEngine:
     rescale_ciphertext = staticmethod(rescale_ciphertext)
 
     # -- linear transforms (the diagonal method) -----------------------------
-    def generate_rotation_key_set(self, sk: RnsPoly, steps, rng) -> RnsGadgetKeySet:
+    def generate_rotation_key_set(self, sk: RnsPoly, steps, rng, hoisted: bool = False) -> RnsGadgetKeySet:
         """One gadget rotation key per step, packed for ``linear_transform``
-        (no key for a step of 0)."""
+        (no key for a step of 0); with ``hoisted`` every key in its hoisting
+        form, for ``rotate_hoisted`` and the baby keys of
+        ``linear_transform_bsgs_hoisted``."""
         keys = [None if int(s) == 0 else self.generate_gadget_rotation_key(sk, int(s), rng) for s in steps]
+        if hoisted:
+            for k in keys:
+                if k is not None:
+                    k.prepare_hoisted()
         return RnsGadgetKeySet(keys, self.basis)
+
+    @staticmethod
+    def rotate_hoisted(ct: Ciphertext, keyset: RnsGadgetKeySet) -> Ciphertext:
+        """Every ciphertext of the batch rotated by each of the key set's
+        steps with one gadget decomposition: a batch of ``n_steps * B``,
+        rotation t of ciphertext b at ``t * B + b``."""
+        return rotate_ciphertext_hoisted(ct, keyset)
 
     def encode_diagonals(self, matrix, steps, encoder: CkksEncoder) -> Plaintext:
         """The diagonal plaintexts of a slots x slots matrix for the steps of
@@ -207,6 +221,16 @@ class CkksEngine:
         key sets' steps as one library call: n1 + n2 key-switches for n1 n2
         diagonals; logp grows by the diagonals' scale."""
         out = linear_transform_bsgs(ct, diag_plaintexts.poly, baby_keyset, giant_keyset)
+        out.logp = ct.logp + diag_plaintexts.scale_bits
+        return out
+
+    @staticmethod
+    def linear_transform_bsgs_hoisted(ct: Ciphertext, diag_plaintexts: Plaintext, baby_keyset: RnsGadgetKeySet,
+                                      giant_keyset: RnsGadgetKeySet) -> Ciphertext:
+        """``linear_transform_bsgs`` with hoisted baby rotations (baby keys
+        in hoisting form, giant keys ordinary): one decomposition for all the
+        babies; logp grows by the diagonals' scale."""
+        out = linear_transform_bsgs_hoisted(ct, diag_plaintexts.poly, baby_keyset, giant_keyset)
         out.logp = ct.logp + diag_plaintexts.scale_bits
         return out
 
