@@ -34,13 +34,17 @@ def _rand(rng, mod, n, batch):
 
 
 class Case:
-    """Random ciphertexts, plaintexts and key channels on one ring, uploaded."""
+    """Random ciphertexts, plaintexts and key channels on one ring, uploaded.
+    With `drop`, the L limbs are a drop_last(drop) view of a root basis of
+    L + drop primes (`root`) instead of a basis of their own."""
 
-    def __init__(self, rn, log_n, L, B, bits, baby=BABY, giant=GIANT, seed=0, edge=False):
+    def __init__(self, rn, log_n, L, B, bits, baby=BABY, giant=GIANT, seed=0, edge=False, drop=0):
         self.rn, self.n, self.L, self.B = rn, 1 << log_n, L, B
         self.baby, self.giant = list(baby), list(giant)
         n, nt = self.n, len(baby) * len(giant)
-        self.mod = rn.generate_primes(bits, L, n)
+        self.drop = drop
+        self.root_mod = rn.generate_primes(bits, L + drop, n)
+        self.mod = self.root_mod[:L]
         rng = np.random.default_rng(3100 + 31 * log_n + seed)
         self.c0, self.c1 = _rand(rng, self.mod, n, B), _rand(rng, self.mod, n, B)
         self.diag = _rand(rng, self.mod, n, nt)  # coefficient domain, poly j n1 + i
@@ -54,7 +58,8 @@ class Case:
 
     def upload(self):
         rn = self.rn
-        self.basis = Bd = rn.RnsBasis(self.mod, self.n)
+        self.root = rn.RnsBasis(self.root_mod, self.n)
+        self.basis = Bd = self.root.drop_last(self.drop) if self.drop else self.root
 
         def up(steps, keys):
             return [None if kk is None else rn.RnsGadgetKey.from_channels(kk[0], kk[1], Bd, rotation=k)

@@ -41,6 +41,13 @@ def _keys(rng, mod, n, L, steps):
     return [None if k == 0 else (_rand(rng, mod, n, L), _rand(rng, mod, n, L)) for k in steps]
 
 
+def _place(rn, root_mod, n, drop):
+    """(root, basis): a root basis of `root_mod`, and the basis under test --
+    the root itself, or its drop_last(drop) view."""
+    root = rn.RnsBasis(root_mod, n)
+    return root, (root.drop_last(drop) if drop else root)
+
+
 def _upload_keys(rn, basis, steps, keys, hoisted):
     out = []
     for k, kk in zip(steps, keys):
@@ -53,12 +60,14 @@ def _upload_keys(rn, basis, steps, keys, hoisted):
 
 class Case:
     """Random ciphertexts and ordinary key channels on one ring; the keys
-    uploaded and turned into their hoisting form."""
+    uploaded and turned into their hoisting form.  With `drop`, the L limbs
+    are a drop_last(drop) view of a root basis of L + drop primes (`root`)."""
 
-    def __init__(self, rn, log_n, L, B, bits, steps=STEPS, seed=0, edge=False):
+    def __init__(self, rn, log_n, L, B, bits, steps=STEPS, seed=0, edge=False, drop=0):
         self.rn, self.n, self.L, self.B, self.steps = rn, 1 << log_n, L, B, list(steps)
         n = self.n
-        self.mod = rn.generate_primes(bits, L, n)
+        self.root_mod = rn.generate_primes(bits, L + drop, n)
+        self.mod = self.root_mod[:L]
         rng = np.random.default_rng(4100 + 37 * log_n + seed)
         self.c0, self.c1 = _rand(rng, self.mod, n, B), _rand(rng, self.mod, n, B)
         self.keys = _keys(rng, self.mod, n, L, self.steps)
@@ -68,7 +77,8 @@ class Case:
             t = next(i for i, k in enumerate(self.steps) if k != 0)
             self.keys[t][0][:] = np.broadcast_to(qm1, (L, L, n))
             self.keys[t][1][:] = np.broadcast_to(qm1, (L, L, n))
-        self.basis = Bd = rn.RnsBasis(self.mod, n)
+        self.root, self.basis = _place(rn, self.root_mod, n, drop)
+        Bd = self.basis
         self.Bo = orc.Basis(self.mod, n)
         self.gk = _upload_keys(rn, Bd, self.steps, self.keys, True)
         self.kset = rn.RnsGadgetKeySet(self.gk, Bd)
@@ -327,16 +337,18 @@ def test_python_layer_guards_the_key_form(gpu):
 # rnt_ct_linear_bsgs_hoisted
 # ---------------------------------------------------------------------------
 class BsgsCase:
-    def __init__(self, rn, log_n, L, B, bits, baby=BABY, giant=GIANT, seed=0):
+    def __init__(self, rn, log_n, L, B, bits, baby=BABY, giant=GIANT, seed=0, drop=0):
         self.rn, self.n, self.L, self.B = rn, 1 << log_n, L, B
         self.baby, self.giant = list(baby), list(giant)
         n, nt = self.n, len(baby) * len(giant)
-        self.mod = rn.generate_primes(bits, L, n)
+        self.root_mod = rn.generate_primes(bits, L + drop, n)
+        self.mod = self.root_mod[:L]
         rng = np.random.default_rng(5100 + 41 * log_n + seed)
         self.c0, self.c1 = _rand(rng, self.mod, n, B), _rand(rng, self.mod, n, B)
         self.diag = _rand(rng, self.mod, n, nt)  # coefficient domain, poly j n1 + i
         self.bkeys, self.gkeys = _keys(rng, self.mod, n, L, baby), _keys(rng, self.mod, n, L, giant)
-        self.basis = Bd = rn.RnsBasis(self.mod, n)
+        self.root, self.basis = _place(rn, self.root_mod, n, drop)
+        Bd = self.basis
         self.bset = rn.RnsGadgetKeySet(_upload_keys(rn, Bd, self.baby, self.bkeys, True), Bd)
         self.gset = rn.RnsGadgetKeySet(_upload_keys(rn, Bd, self.giant, self.gkeys, False), Bd)
         self.d = rn.RnsPoly.from_channels(self.diag, Bd)
