@@ -91,7 +91,8 @@ int rnt_device_count(int* n);
  * "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt", "sfft",
  * "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd",
  * "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
- * "bsgs_mac", "hoist_digits", "hoist_mac"), the launch count and summed device milliseconds since enabling. */
+ * "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown"), the launch
+ * count and summed device milliseconds since enabling. */
 int rnt_profile_enable(const rnt_ctx* ctx, int enable);
 int rnt_profile_read(const rnt_ctx* ctx, const char* kernel, uint64_t* launches,
                      double* total_ms);
@@ -411,6 +412,54 @@ int rnt_ct_linear_bsgs_hoisted(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, 
                                const int32_t* giant_steps, size_t n_giant, const rnt_buf* diag,
                                const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
                                const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b);
+/* ---- hybrid key-switching with special primes (DESIGN.md "Hybrid
+ * key-switching") ---------------------------------------------------------
+ * The ciphertext lives on a context C over q_0 .. q_{Lv-1}; the key on a
+ * context E over q_0 .. q_{Lv-1}, p_0 .. p_{K-1} (K >= 1 special primes, P
+ * their product).  E must have C's degree and device and its first Lv moduli
+ * must equal C's BY VALUE: C may be E's drop_last(K) view, an unrelated root
+ * or a view of another root, so a levelled ciphertext works with a per-level
+ * key context.  The limbs are grouped into beta = ceil(Lv / alpha) digits of
+ * alpha limbs (the last one may be partial), Q_d the product of digit d's.
+ *   ModUp_d(x): y_i = x_i (Q_d/q_i)^-1 mod q_i for i in digit d; limb t of the
+ *     result is x_t for t in the digit, else sum_i y_i (Q_d/q_i mod m_t) mod
+ *     m_t (the fast base conversion: [x]_{Q_d} + u Q_d with 0 <= u < |digit|).
+ *   A0 = sum_d ModUp_d(x) key_b[d], A1 with key_a (negacyclic, over E).
+ *   ModDown(A): z_k = A_{p_k} (P/p_k)^-1 mod p_k; out_j = (A_j - sum_k z_k
+ *     (P/p_k mod q_j)) P^-1 mod q_j (no rounding term: the floor-like
+ *     quotient, off by at most K per coefficient).
+ * rnt_keyswitch_hybrid: acc0 = ModDown(A0), acc1 = ModDown(A1) with x = d,
+ * coefficient domain, canonical.  key_a / key_b: beta polys each over E,
+ * prepared with rnt_key_prepare; the key for a target s' under s is
+ * b_d = -a_d s + e_d + G_d with limb t of G_d = P s' mod q_t for t in digit d
+ * and 0 elsewhere (all special limbs 0); the caller chooses P >~ alpha max Q_d.
+ * At a lower level Lv' the key is the first ceil(Lv'/alpha) polys of the full
+ * one restricted to the limbs q_0 .. q_{Lv'-1}, p_0 .. p_{K-1}, on a root
+ * context over exactly those moduli.
+ * Errors: alpha == 0, acc0 aliasing acc1 or d, batch sizes that differ ->
+ * RNT_ERR_BAD_ARGUMENT; degree, device or moduli-prefix mismatch, or E without
+ * a limb above C's -> RNT_ERR_BASIS_MISMATCH; E and C of different device word
+ * widths -> RNT_ERR_UNSUPPORTED (fields 0, 0); a key poly count other than
+ * beta -> RNT_ERR_CHANNEL_COUNT (fields: beta, got); a coefficient-domain key
+ * or an NTT-domain d -> RNT_ERR_DOMAIN_MISMATCH.  The constants of (E, Lv,
+ * alpha) are built on the first call, which therefore cannot be recorded
+ * (rnt_capture_begin: run the sequence once first).  Launches run on C's
+ * stream, after whatever E's stream held at the call. */
+int rnt_keyswitch_hybrid(rnt_buf* acc0, rnt_buf* acc1, const rnt_buf* d,
+                         const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha);
+/* rotate_ciphertext with the hybrid key-switch: (sigma_k(c0) + acc0, acc1) for
+ * x = sigma_k(c1); k == 0 copies the input and does not read the key.  c0, c1
+ * coefficient domain; the outputs may be the inputs (out0 == out1 ->
+ * RNT_ERR_BAD_ARGUMENT).  Not rnt_ct_rotate's words: it decrypts alike, with
+ * less noise. */
+int rnt_ct_rotate_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                         int32_t k, const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha);
+/* mul_ciphertexts_gadget with the hybrid key-switch: the tensor d0, d1, d2 of
+ * rnt_ct_mul_relin, then (d0 + acc0, d1 + acc1) for x = d2; coefficient domain
+ * in and out, aliasing as rnt_ct_mul_relin. */
+int rnt_ct_mul_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                            const rnt_buf* c0p, const rnt_buf* c1p,
+                            const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha);
 /* polys [src_first, src_first + count) of src -> [dst_first, ...) of dst (same
  * context; dst takes src's domain, which must equal dst's unless the copy
  * covers all of dst).  A range outside either batch -> RNT_ERR_BAD_ARGUMENT. */

@@ -97,7 +97,7 @@ const char* const kKernelNames[rnt::K_COUNT] = {
     "col_fwd", "row_fwd", "row_inv", "row_mul", "col_inv", "elementwise", "rescale",
     "automorphism", "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt",
     "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
-    "bsgs_mac", "hoist_digits", "hoist_mac"};
+    "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown"};
 
 // A profiling call failed: clear the runtime's slot, keep the first failure
 // in the profiler, and stop profiling (rnt_profile_read reports it).
@@ -571,6 +571,7 @@ rnt::Tables::~Tables() {
   }
   for (auto& e : resc_ext) cleanup(hipFree(e.second), "hipFree(context tables)");
   for (auto& e : crt_cache) cleanup(hipFree(e.second.dev), "hipFree(context tables)");
+  for (auto& e : hyb_cache) cleanup(hipFree(e.dev), "hipFree(context tables)");
   for (void* p : {tw_fwd, tw_inv, sfft_tw, lconst, resc, resc_p, mf})
     cleanup(hipFree(p), "hipFree(context tables)");
   if (prof) {
@@ -2355,26 +2356,31 @@ int copy_rows(const rnt::Launch& k, void* dst, uint64_t dst_ls, const void* src,
 }
 
 // Forward / inverse transform in place of a raw [k.L][k.B][N] block at limb
-// stride ls: the launches of rnt_ntt_fwd / rnt_ntt_inv.
-int fwd_raw(const rnt::Launch& k, void* p, uint64_t ls) {
+// stride ls: the launches of rnt_ntt_fwd / rnt_ntt_inv, on k.s.  pt: the
+// tables whose profile counts them (nullptr: k.t, whose stream k.s then is) --
+// the hybrid key-switch transforms over the key basis' tables on the
+// ciphertext context's stream.
+int fwd_raw(const rnt::Launch& k, void* p, uint64_t ls, const rnt::Tables* pt = nullptr) {
+  if (!pt) pt = k.t;
   if (use_mf(k)) {
-    LAUNCH(k.t, rnt::K_MF_NTT_FWD, rnt::launch_mf_ntt(k, 0, p, ls), "MFMA forward transform");
+    LAUNCH_ON(pt, k.s, rnt::K_MF_NTT_FWD, rnt::launch_mf_ntt(k, 0, p, ls), "MFMA forward transform");
   } else if (rnt::whole_ok(k.t, 0)) {
-    LAUNCH(k.t, rnt::K_WHOLE_FWD, rnt::launch_whole(k, 0, p, p, nullptr, ls), "whole-plane forward");
+    LAUNCH_ON(pt, k.s, rnt::K_WHOLE_FWD, rnt::launch_whole(k, 0, p, p, nullptr, ls), "whole-plane forward");
   } else {
-    LAUNCH(k.t, rnt::K_COL_FWD, rnt::launch_col_fwd(k, p, p, nullptr, nullptr, ls, ls), "column forward");
-    LAUNCH(k.t, rnt::K_ROW_FWD, rnt::launch_row(k, 0, p, nullptr, ls), "row forward");
+    LAUNCH_ON(pt, k.s, rnt::K_COL_FWD, rnt::launch_col_fwd(k, p, p, nullptr, nullptr, ls, ls), "column forward");
+    LAUNCH_ON(pt, k.s, rnt::K_ROW_FWD, rnt::launch_row(k, 0, p, nullptr, ls), "row forward");
   }
   return RNT_OK;
 }
-int inv_raw(const rnt::Launch& k, void* p, uint64_t ls) {
+int inv_raw(const rnt::Launch& k, void* p, uint64_t ls, const rnt::Tables* pt = nullptr) {
+  if (!pt) pt = k.t;
   if (use_mf(k)) {
-    LAUNCH(k.t, rnt::K_MF_NTT_INV, rnt::launch_mf_ntt(k, 1, p, ls), "MFMA inverse transform");
+    LAUNCH_ON(pt, k.s, rnt::K_MF_NTT_INV, rnt::launch_mf_ntt(k, 1, p, ls), "MFMA inverse transform");
   } else if (rnt::whole_ok(k.t, 1)) {
-    LAUNCH(k.t, rnt::K_WHOLE_INV, rnt::launch_whole(k, 1, p, p, nullptr, ls), "whole-plane inverse");
+    LAUNCH_ON(pt, k.s, rnt::K_WHOLE_INV, rnt::launch_whole(k, 1, p, p, nullptr, ls), "whole-plane inverse");
   } else {
-    LAUNCH(k.t, rnt::K_ROW_INV, rnt::launch_row(k, 1, p, nullptr, ls), "row inverse");
-    LAUNCH(k.t, rnt::K_COL_INV, rnt::launch_col_inv(k, p, ls, p, ls, 0, nullptr), "column inverse");
+    LAUNCH_ON(pt, k.s, rnt::K_ROW_INV, rnt::launch_row(k, 1, p, nullptr, ls), "row inverse");
+    LAUNCH_ON(pt, k.s, rnt::K_COL_INV, rnt::launch_col_inv(k, p, ls, p, ls, 0, nullptr), "column inverse");
   }
   return RNT_OK;
 }
@@ -2790,6 +2796,322 @@ extern "C" int rnt_ct_rotate_hoisted(rnt_buf* out0, rnt_buf* out1, const rnt_buf
     };
     if (int rc = hoist_chunk(kc, D, ACC, (const char*)c1->data + p0 * n * wb, full_ls, steps, n_steps, keys_a,
                              keys_b, finish))
+      return rc;
+  }
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// hybrid key-switching: digits of alpha limbs raised to Q u P (ModUp), one
+// multiply-accumulate against a key over Q u P, division by P (ModDown)
+// ---------------------------------------------------------------------------
+namespace {
+
+struct HybridPlan {
+  const rnt_ctx* C = nullptr;  // the ciphertext's context (Lv limbs)
+  const rnt_ctx* E = nullptr;  // the key's context (Lv + K limbs)
+  size_t Lv = 0, K = 0, LE = 0, alpha = 0, beta = 0;
+  rnt::HybridConsts hc{};
+};
+
+// The argument rules the three hybrid calls share (no device work).
+int hybrid_check(const char* name, const rnt_ctx* C, const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha,
+                 HybridPlan* pl) {
+  if (alpha == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: alpha must be at least 1", name);
+  if (int rc = check_buf(key_a, name)) return rc;
+  if (int rc = check_buf(key_b, name)) return rc;
+  if (key_a->ctx != key_b->ctx)
+    return fail(RNT_ERR_BASIS_MISMATCH, "%s: the key halves belong to different bases", name);
+  const rnt_ctx* E = key_a->ctx;
+  const rnt::Tables* tc = C->t.get();
+  const rnt::Tables* te = E->t.get();
+  if (te->log_n != tc->log_n || te->device != tc->device)
+    return fail(RNT_ERR_BASIS_MISMATCH, "%s: key and ciphertext bases differ in degree or device", name);
+  const size_t Lv = C->L;
+  if (E->L <= Lv)
+    return fail(RNT_ERR_BASIS_MISMATCH, "%s: the key basis (%zu limbs) has no special limb above the ciphertext's %zu",
+                name, E->L, Lv);
+  for (size_t l = 0; l < Lv; ++l)
+    if (te->moduli[l] != tc->moduli[l])
+      return fail(RNT_ERR_BASIS_MISMATCH, "%s: limb %zu of the key basis is %" PRIu64 ", the ciphertext's %" PRIu64,
+                  name, l, te->moduli[l], tc->moduli[l]);
+  if (te->wide != tc->wide)
+    return fail_fields(RNT_ERR_UNSUPPORTED, 0, 0, "%s: key and ciphertext bases have different device word widths",
+                       name);
+  const size_t beta = (Lv + alpha - 1) / alpha;
+  if (key_a->n_polys != beta || key_b->n_polys != beta)
+    return fail_fields(RNT_ERR_CHANNEL_COUNT, beta, key_a->n_polys != beta ? key_a->n_polys : key_b->n_polys,
+                       "a hybrid key for %zu limbs in digits of %zu holds %zu polys", Lv, alpha, beta);
+  if (!key_a->in_ntt || !key_b->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: keys must be prepared (rnt_key_prepare)", name);
+  pl->C = C;
+  pl->E = E;
+  pl->Lv = Lv;
+  pl->LE = E->L;
+  pl->K = E->L - Lv;
+  pl->alpha = std::min(alpha, Lv);  // (one digit holds every limb from alpha = Lv on)
+  pl->beta = beta;
+  return RNT_OK;
+}
+
+// The device constants of (key limbs, ciphertext limbs, alpha), cached on the
+// key basis' tables; the first use allocates and copies, so it cannot be
+// recorded into a graph (one un-recorded run first).  Also orders the call
+// after the work queued on the key basis' stream where that is another stream
+// than the ciphertext's (its keys may still be in preparation there).
+int hybrid_prepare(HybridPlan* pl) {
+  rnt::Tables* te = pl->E->t.get();
+  const rnt::Tables* tc = pl->C->t.get();
+  if (te != tc && te->stream != tc->stream && g_capture == nullptr) {
+    hipEvent_t ev = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate(hybrid key order)");
+    hipError_t e = hipEventRecord(ev, te->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(tc->stream, ev, 0);
+    cleanup(hipEventDestroy(ev), "hipEventDestroy(hybrid key order)");
+    HIP_TRY(e, "hipStreamWaitEvent(hybrid key order)");
+  }
+  std::lock_guard<std::mutex> g(te->resc_mu);
+  for (auto& e : te->hyb_cache)
+    if (e.LE == pl->LE && e.Lv == pl->Lv && e.alpha == pl->alpha) {
+      pl->hc = e.hc;
+      return RNT_OK;
+    }
+  const rnt::host::HybridLayout lay(pl->Lv, pl->K, pl->alpha);
+  std::vector<uint64_t> h(lay.total);
+  if (!rnt::host::hybrid_constants(te->moduli.data(), lay, te->wide ? 64 : 32, h.data()))
+    return fail(RNT_ERR_BAD_ARGUMENT, "hybrid key-switch: the moduli of the key basis are not pairwise coprime");
+  const size_t wb = word_bytes(te);
+  void* d = nullptr;
+  HIP_TRY(hipMalloc(&d, lay.total * wb), "hipMalloc(hybrid constants)");
+  hipError_t e;
+  if (wb == 4) {
+    std::vector<uint32_t> h32(h.begin(), h.end());
+    e = hipMemcpy(d, h32.data(), lay.total * 4, hipMemcpyHostToDevice);
+  } else {
+    e = hipMemcpy(d, h.data(), lay.total * 8, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    cleanup(hipFree(d), "hipFree(hybrid constants)");
+    return hip_fail(e, "hipMemcpy(hybrid constants)");
+  }
+  rnt::HybridDev hd;
+  hd.LE = pl->LE;
+  hd.Lv = pl->Lv;
+  hd.alpha = pl->alpha;
+  hd.dev = d;
+  auto at = [&](size_t o) { return (const void*)((const char*)d + o * wb); };
+  hd.hc.yinv = at(lay.yinv), hd.hc.yinvp = at(lay.yinvp);
+  hd.hc.conv = at(lay.conv), hd.hc.convp = at(lay.convp);
+  hd.hc.pinv = at(lay.pinv), hd.hc.pinvp = at(lay.pinvp);
+  hd.hc.pq = at(lay.pq), hd.hc.pqp = at(lay.pqp);
+  hd.hc.Pinv = at(lay.Pinv), hd.hc.Pinvp = at(lay.Pinvp);
+  hd.hc.Lv = (uint32_t)pl->Lv, hd.hc.K = (uint32_t)pl->K;
+  hd.hc.alpha = (uint32_t)pl->alpha, hd.hc.beta = (uint32_t)pl->beta;
+  te->hyb_cache.push_back(hd);
+  pl->hc = hd.hc;
+  return RNT_OK;
+}
+
+// Planes of N words one poly of a chunk needs: the raised digits D
+// ((Lv + K) beta) and the two accumulators over the key basis.
+size_t hybrid_planes(const HybridPlan& pl) { return pl.LE * pl.beta + 2 * pl.LE; }
+
+// Polys per chunk within the key-switch workspace cap (`extra` further planes
+// per poly are the caller's), one poly being the floor.
+size_t hybrid_chunk(const HybridPlan& pl, size_t B, size_t extra) {
+  const rnt::Tables* t = pl.C->t.get();
+  const size_t per = (hybrid_planes(pl) + extra) * t->n * word_bytes(t);
+  return std::min(std::max<size_t>(B, 1), std::max<size_t>(t->ks_ws_bytes / per, 1));
+}
+
+// One chunk of c polys: x (coefficient domain, the chunk's first poly, limb
+// stride x_ls over the ciphertext's limbs) -> out0 = ModDown(sum_d ModUp_d(x)
+// key_b[d]) (+ add0), out1 with key_a (+ add1), at limb stride out_ls; the
+// addends (optional, coefficient domain) at add_ls.  ws: D | A0 | A1.  Every
+// launch runs on the ciphertext context's stream and counts in its profile;
+// the transforms and constants are the key basis'.
+int hybrid_chunk_run(const HybridPlan& pl, size_t c, char* ws, const void* x, uint64_t x_ls, const rnt_buf* key_a,
+                     const rnt_buf* key_b, void* out0, void* out1, uint64_t out_ls, const void* add0,
+                     const void* add1, uint64_t add_ls) {
+  const rnt::Tables* tc = pl.C->t.get();
+  const rnt::Tables* te = pl.E->t.get();
+  const size_t n = te->n, wb = word_bytes(te);
+  rnt::Launch k;
+  k.t = te;
+  k.L = pl.LE;
+  k.B = c;
+  k.s = tc->stream;
+  char* D = ws;
+  char* A0 = D + pl.LE * pl.beta * c * n * wb;
+  char* A1 = A0 + pl.LE * c * n * wb;
+  const uint64_t cls = (uint64_t)c * n;
+  LAUNCH_ON(tc, k.s, rnt::K_MODUP, rnt::launch_modup(k, D, x, x_ls, pl.hc), "ModUp");
+  rnt::Launch kd = k;
+  kd.B = pl.beta * c;
+  if (int rc = fwd_raw(kd, D, (uint64_t)kd.B * n, tc)) return rc;
+  rnt::Launch km = k;
+  km.Ls = pl.beta;
+  void* a0[1] = {A0};
+  void* a1[1] = {A1};
+  const void* ka[1] = {key_a->data};
+  const void* kb[1] = {key_b->data};
+  LAUNCH_ON(tc, k.s, rnt::K_HOIST_MAC, rnt::launch_hoist_mac(km, a0, a1, 1, D, ka, kb, limb_stride(key_a)),
+            "hybrid key products");
+  if (int rc = inv_raw(k, A0, cls, tc)) return rc;
+  if (int rc = inv_raw(k, A1, cls, tc)) return rc;
+  LAUNCH_ON(tc, k.s, rnt::K_MODDOWN, rnt::launch_moddown(k, out0, out_ls, A0, cls, add0, add_ls, pl.hc), "ModDown");
+  LAUNCH_ON(tc, k.s, rnt::K_MODDOWN, rnt::launch_moddown(k, out1, out_ls, A1, cls, add1, add_ls, pl.hc), "ModDown");
+  return RNT_OK;
+}
+
+}  // namespace
+
+extern "C" int rnt_keyswitch_hybrid(rnt_buf* acc0, rnt_buf* acc1, const rnt_buf* d, const rnt_buf* key_a,
+                                    const rnt_buf* key_b, size_t alpha) {
+  const char* name = "rnt_keyswitch_hybrid";
+  for (const rnt_buf* b : {(const rnt_buf*)acc0, (const rnt_buf*)acc1, d})
+    if (int rc = check_buf(b, name)) return rc;
+  if (acc0 == acc1 || acc0 == d || acc1 == d || acc0->data == acc1->data || acc0->data == d->data ||
+      acc1->data == d->data)
+    return fail(RNT_ERR_BAD_ARGUMENT, "%s: outputs must not alias each other or d", name);
+  if (int rc = check_same(acc0, d, name)) return rc;
+  if (int rc = check_same(acc1, d, name)) return rc;
+  HybridPlan pl;
+  if (int rc = hybrid_check(name, d->ctx, key_a, key_b, alpha, &pl)) return rc;
+  if (d->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: d must be in coefficient domain", name);
+  if (int rc = set_device(d->ctx)) return rc;
+  if (int rc = hybrid_prepare(&pl)) return rc;
+  const size_t n = d->ctx->t->n, wb = word_bytes(d->ctx->t.get()), B = d->n_polys;
+  const size_t bc = hybrid_chunk(pl, B, 0);
+  CallWs ws(acc0);
+  if (int rc = ws.get(std::max<size_t>(hybrid_planes(pl) * bc * n * wb, 16))) return rc;
+  const uint64_t ls = limb_stride(d);
+  for (size_t p0 = 0; p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    const size_t off = p0 * n * wb;
+    if (int rc = hybrid_chunk_run(pl, c, (char*)ws.p, (const char*)d->data + off, ls, key_a, key_b,
+                                  (char*)acc0->data + off, (char*)acc1->data + off, ls, nullptr, nullptr, 0))
+      return rc;
+  }
+  acc0->in_ntt = acc1->in_ntt = 0;
+  return RNT_OK;
+}
+
+extern "C" int rnt_ct_rotate_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1, int32_t kk,
+                                    const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha) {
+  const char* name = "rnt_ct_rotate_hybrid";
+  const rnt_buf* all[4] = {out0, out1, c0, c1};
+  for (const rnt_buf* b : all)
+    if (int rc = check_buf(b, name)) return rc;
+  if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
+  for (int i = 1; i < 4; ++i)
+    if (int rc = check_same(all[0], all[i], name)) return rc;
+  if (alpha == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: alpha must be at least 1", name);
+  if (c0->in_ntt || c1->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the ciphertext must be in coefficient domain", name);
+  if (kk == 0) {  // the identity: no key-switch, the key is not read
+    if (out0 == c1 && out1 == c0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: the outputs swap the inputs", name);
+    if (out0 == c1) {
+      if (int rc = rnt_copy(out1, c1)) return rc;
+      return rnt_copy(out0, c0);
+    }
+    if (int rc = rnt_copy(out0, c0)) return rc;
+    return rnt_copy(out1, c1);
+  }
+  HybridPlan pl;
+  if (int rc = hybrid_check(name, c0->ctx, key_a, key_b, alpha, &pl)) return rc;
+  if (int rc = set_device(c0->ctx)) return rc;
+  if (int rc = hybrid_prepare(&pl)) return rc;
+  rnt::Launch k = launch_for(c0);
+  const size_t n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
+  const size_t words = pl.Lv * B * n;
+  const uint64_t g = rotation_exponent(kk, 2 * (uint64_t)n);
+  const size_t bc = hybrid_chunk(pl, B, 0);
+  // ws: sigma(c0) | sigma(c1) (the batch, so the outputs may be the inputs) | the chunk's D, A0, A1
+  CallWs ws(out0);
+  if (int rc = ws.get(std::max<size_t>((2 * words + hybrid_planes(pl) * bc * n) * wb, 16))) return rc;
+  char* sig0 = (char*)ws.p;
+  char* sig1 = sig0 + words * wb;
+  char* HW = sig1 + words * wb;
+  LAUNCH(k.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(k, sig0, c0->data, g), "automorphism");
+  LAUNCH(k.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(k, sig1, c1->data, g), "automorphism");
+  const uint64_t ls = limb_stride(c0);
+  for (size_t p0 = 0; p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    const size_t off = p0 * n * wb;
+    if (int rc = hybrid_chunk_run(pl, c, HW, sig1 + off, ls, key_a, key_b, (char*)out0->data + off,
+                                  (char*)out1->data + off, ls, sig0 + off, nullptr, ls))
+      return rc;
+  }
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
+extern "C" int rnt_ct_mul_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                       const rnt_buf* c0p, const rnt_buf* c1p, const rnt_buf* key_a,
+                                       const rnt_buf* key_b, size_t alpha) {
+  const char* name = "rnt_ct_mul_relin_hybrid";
+  const rnt_buf* all[6] = {out0, out1, c0, c1, c0p, c1p};
+  for (const rnt_buf* b : all)
+    if (int rc = check_buf(b, name)) return rc;
+  if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
+  for (int i = 1; i < 6; ++i)
+    if (int rc = check_same(all[0], all[i], name)) return rc;
+  HybridPlan pl;
+  if (int rc = hybrid_check(name, c0->ctx, key_a, key_b, alpha, &pl)) return rc;
+  if (c0->in_ntt || c1->in_ntt || c0p->in_ntt || c1p->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: inputs must be in coefficient domain", name);
+  if (int rc = set_device(c0->ctx)) return rc;
+  if (int rc = hybrid_prepare(&pl)) return rc;
+  rnt::Launch k = launch_for(c0);
+  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
+  // the tensor of rnt_ct_mul_relin per chunk: d0^, d1^ (NTT domain, scaled by
+  // 2^-w as its key-switch seeds are) and d2; here d0, d1 go back to the
+  // coefficient domain and are ModDown's addends
+  const bool whole = rnt::tensor_whole_ok(k.t);
+  const bool mf = !whole && use_mf(k);
+  const size_t nt = whole ? 0 : mf ? 1 : 4;
+  const size_t bc = hybrid_chunk(pl, B, (nt + 3) * L);
+  const size_t chunk_words = L * bc * n;
+  // ws: [T0..T3] | D0 | D1 | D2 | the chunk's D, A0, A1
+  CallWs cws(out0);
+  if (int rc = cws.get(std::max<size_t>(((nt + 3) * chunk_words + hybrid_planes(pl) * bc * n) * wb, 16))) return rc;
+  char* ws = (char*)cws.p;
+  char* T[4];
+  for (int i = 0; i < 4; ++i) T[i] = ws + i * chunk_words * wb;
+  char* D0 = ws + nt * chunk_words * wb;
+  char* D1 = D0 + chunk_words * wb;
+  char* D2 = D1 + chunk_words * wb;
+  char* HW = D2 + chunk_words * wb;
+  const uint64_t full_ls = limb_stride(c0);
+  for (size_t p0 = 0; p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    rnt::Launch kc = k;
+    kc.B = c;
+    const uint64_t cls = (uint64_t)c * n;
+    const size_t po = p0 * n * wb;
+    auto off = [&](const rnt_buf* b) { return (const char*)b->data + po; };
+    if (whole) {
+      LAUNCH(kc.t, rnt::K_TENSOR_WHOLE,
+             rnt::launch_tensor_whole(kc, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls),
+             "tensor whole");
+    } else if (mf) {
+      LAUNCH(kc.t, rnt::K_MF_TENSOR,
+             rnt::launch_mf_tensor(kc, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls, T[0]),
+             "MFMA tensor");
+    } else {
+      LAUNCH(kc.t, rnt::K_COL_FWD, rnt::launch_col_fwd(kc, T[0], off(c0), T[1], off(c1), full_ls, cls), "tensor column");
+      LAUNCH(kc.t, rnt::K_COL_FWD, rnt::launch_col_fwd(kc, T[2], off(c0p), T[3], off(c1p), full_ls, cls), "tensor column");
+      LAUNCH(kc.t, rnt::K_TENSOR_ROWS, rnt::launch_tensor_rows(kc, D0, D1, D2, T[0], T[1], T[2], T[3], cls), "tensor rows");
+      LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, D2, cls, D2, cls, 1, nullptr), "d2 inverse");
+    }
+    for (char* Dx : {D0, D1}) {  // INV(d^ 2^-w) 2^w = d, canonical
+      if (int rc = inv_raw(kc, Dx, cls)) return rc;
+      LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 1, Dx, Dx, nullptr, 0, false), "seed unscale");
+    }
+    if (int rc = hybrid_chunk_run(pl, c, HW, D2, cls, key_a, key_b, (char*)out0->data + po, (char*)out1->data + po,
+                                  full_ls, D0, D1, cls))
       return rc;
   }
   out0->in_ntt = out1->in_ntt = 0;

@@ -9,6 +9,7 @@
 //   find_primitive_root (psi rule)          src/rings/backends/rns_ntt/basis.rs:217-237
 //   mod_inverse                             basis.rs:198-210
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace rnt {
@@ -144,6 +145,81 @@ inline uint64_t neg_free_qinv(uint64_t q, unsigned wbits) {
   uint64_t x = q;
   for (int i = 0; i < 6; ++i) x *= 2 - q * x;
   return wbits == 32 ? (x & 0xffffffffull) : x;
+}
+
+// Constants of the hybrid key-switch (k_modup / k_moddown) over the moduli
+// m[0 .. LE): the first Lv are the ciphertext's q_j, the rest the K = LE - Lv
+// special primes p_k; digits of alpha limbs, beta = ceil(Lv / alpha).  One flat
+// array of residues in the order of HybridLayout (each table followed by its
+// Shoup companions for wbits-bit words).  Only residues are needed, so every
+// product is taken mod its target.  Returns false when two moduli share a factor.
+struct HybridLayout {
+  size_t Lv, K, alpha, beta, LE;
+  size_t yinv, yinvp, conv, convp, pinv, pinvp, pq, pqp, Pinv, Pinvp, total;
+  HybridLayout(size_t Lv_, size_t K_, size_t alpha_)
+      : Lv(Lv_), K(K_), alpha(alpha_), beta((Lv_ + alpha_ - 1) / alpha_), LE(Lv_ + K_) {
+    size_t o = 0;
+    yinv = o, o += Lv;
+    yinvp = o, o += Lv;
+    conv = o, o += beta * alpha * LE;
+    convp = o, o += beta * alpha * LE;
+    pinv = o, o += K;
+    pinvp = o, o += K;
+    pq = o, o += K * Lv;
+    pqp = o, o += K * Lv;
+    Pinv = o, o += Lv;
+    Pinvp = o, o += Lv;
+    total = o;
+  }
+};
+inline bool hybrid_constants(const uint64_t* m, const HybridLayout& h, unsigned wbits, uint64_t* out) {
+  for (size_t w = 0; w < h.total; ++w) out[w] = 0;
+  auto pair = [&](size_t at, size_t atp, uint64_t v, uint64_t q) {
+    out[at] = v;
+    out[atp] = shoup_companion(v, q, wbits);
+  };
+  for (size_t d = 0; d < h.beta; ++d) {
+    const size_t first = d * h.alpha, cnt = h.Lv - first < h.alpha ? h.Lv - first : h.alpha;
+    for (size_t a = 0; a < cnt; ++a) {
+      const size_t i = first + a;
+      for (size_t t = 0; t < h.LE; ++t) {  // (Q_d / q_i) mod m_t, then its Montgomery form
+        uint64_t r = 1 % m[t];
+        for (size_t b = 0; b < cnt; ++b)
+          if (b != a) r = mulmod(r, m[first + b] % m[t], m[t]);
+        if (t == i) {
+          const uint64_t inv = invmod(r, m[i]);
+          if (inv == 0) return false;
+          pair(h.yinv + i, h.yinvp + i, inv, m[i]);
+        }
+        const uint64_t rw = (uint64_t)((((u128)1) << wbits) % m[t]);
+        const size_t at = (d * h.alpha + a) * h.LE + t;
+        pair(h.conv + at, h.convp + at, mulmod(r, rw, m[t]), m[t]);
+      }
+    }
+  }
+  for (size_t k = 0; k < h.K; ++k) {
+    const uint64_t pk = m[h.Lv + k];
+    uint64_t r = 1 % pk;
+    for (size_t b = 0; b < h.K; ++b)
+      if (b != k) r = mulmod(r, m[h.Lv + b] % pk, pk);
+    const uint64_t inv = invmod(r, pk);
+    if (inv == 0) return false;
+    pair(h.pinv + k, h.pinvp + k, inv, pk);
+    for (size_t j = 0; j < h.Lv; ++j) {
+      uint64_t s = 1 % m[j];
+      for (size_t b = 0; b < h.K; ++b)
+        if (b != k) s = mulmod(s, m[h.Lv + b] % m[j], m[j]);
+      pair(h.pq + k * h.Lv + j, h.pqp + k * h.Lv + j, s, m[j]);
+    }
+  }
+  for (size_t j = 0; j < h.Lv; ++j) {
+    uint64_t s = 1 % m[j];
+    for (size_t b = 0; b < h.K; ++b) s = mulmod(s, m[h.Lv + b] % m[j], m[j]);
+    const uint64_t inv = invmod(s, m[j]);
+    if (inv == 0) return false;
+    pair(h.Pinv + j, h.Pinvp + j, inv, m[j]);
+  }
+  return true;
 }
 
 }  // namespace host

@@ -77,6 +77,28 @@ struct CrtDev {
   CrtConsts cc{};
 };
 
+// Device pointers of the hybrid key-switch constants (k_modup, k_moddown;
+// words of the basis' width).  Lv ciphertext limbs q_j, K special limbs p_k
+// (the key basis' limbs Lv .. Lv + K - 1), beta digits of alpha limbs.
+struct HybridConsts {
+  const void* yinv = nullptr;   // [Lv]  (Q_d / q_i)^-1 mod q_i, d the digit of i
+  const void* yinvp = nullptr;  //       Shoup companions (of every table below too)
+  const void* conv = nullptr;   // [beta][alpha][Lv + K]  (Q_d / q_i) 2^w mod m_t
+  const void* convp = nullptr;
+  const void* pinv = nullptr;   // [K]  (P / p_k)^-1 mod p_k
+  const void* pinvp = nullptr;
+  const void* pq = nullptr;     // [K][Lv]  (P / p_k) mod q_j
+  const void* pqp = nullptr;
+  const void* Pinv = nullptr;   // [Lv]  P^-1 mod q_j
+  const void* Pinvp = nullptr;
+  uint32_t Lv = 0, K = 0, alpha = 0, beta = 0;
+};
+struct HybridDev {
+  size_t LE = 0, Lv = 0, alpha = 0;
+  void* dev = nullptr;
+  HybridConsts hc{};
+};
+
 struct Tables {
   int device = 0;
   int wide = 0;            // 0: W = u32, 1: W = u64
@@ -107,6 +129,9 @@ struct Tables {
   std::vector<std::pair<uint64_t, void*>> resc_ext;
   // centred-CRT constants per limb count (rnt_to_coeffs / rnt_crt_centered)
   std::vector<std::pair<size_t, struct CrtDev>> crt_cache;
+  // hybrid key-switch constants (rnt_*_hybrid) of a key basis, per (key limbs,
+  // ciphertext limbs, alpha); under resc_mu, built on first use
+  std::vector<struct HybridDev> hyb_cache;
   // CKKS special-FFT twiddles (rnt_encode.hip), [N/2] double2, built on
   // first encode/decode
   std::mutex sfft_mu;
@@ -123,7 +148,7 @@ enum KernelId {
   K_COL_FWD, K_ROW_FWD, K_ROW_INV, K_ROW_MUL, K_COL_INV, K_ELEMENTWISE, K_RESCALE,
   K_AUTOMORPHISM, K_KS_DECOMPOSE, K_KS_ROWS, K_TENSOR_ROWS, K_IMPORT, K_EXPORT, K_CRT,
   K_SFFT, K_SAMPLE, K_COPY, K_PLANE_FUSED, K_MF_NTT_FWD, K_MF_NTT_INV, K_WHOLE_FWD, K_WHOLE_INV, K_WHOLE_MUL,
-  K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_COUNT
+  K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_MODUP, K_MODDOWN, K_COUNT
 };
 
 struct Prof {
@@ -351,6 +376,17 @@ constexpr uint32_t kHoistT = 4;
 hipError_t launch_hoist_digits(const Launch& k, void* D, const void* c1, uint64_t src_ls);
 hipError_t launch_hoist_mac(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt, const void* d,
                             const void* const* key_a, const void* const* key_b, uint64_t key_ls);
+// Hybrid key-switching (rnt_keyswitch_hybrid).  k.t is the KEY basis' tables,
+// k.L = Lv + K its limbs, k.B the chunk's polys.  launch_modup (k_modup): the
+// Montgomery-form raised digits D[t][d][p] = ModUp_d(x) 2^w mod m_t for t < k.L,
+// d < hc.beta, x coefficient-domain over the first Lv limbs at limb stride
+// src_ls; D is [k.L][beta][k.B][N], the block launch_hoist_mac reads with
+// Ls = beta.  launch_moddown (k_moddown): out_j = (A_j - conv_j) P^-1 (+ add_j)
+// for j < Lv from the coefficient-domain A ([k.L][k.B][N] at limb stride a_ls);
+// out at limb stride out_ls, the optional addend at add_ls.
+hipError_t launch_modup(const Launch& k, void* D, const void* x, uint64_t src_ls, const HybridConsts& hc);
+hipError_t launch_moddown(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
+                          const void* add, uint64_t add_ls, const HybridConsts& hc);
 // out[l][i] = 2^w mod q_l over [k.L][N]: the Montgomery-form plaintext 1.
 hipError_t launch_mont_one(const Launch& k, void* out);
 // The whole-plane key-switch at 2^10 <= N <= 2^13 (k_ks_whole, one launch,

@@ -29,6 +29,7 @@
 //                compile-time, so only one base address per thread is live.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 
 #include "rnt_internal.hpp"
@@ -1989,6 +1990,171 @@ k_hoist_mac(HoistArgs<W> a, const W* __restrict__ d, TabPtrs<W> tp, uint32_t log
   }
 }
 
+// 16-byte (VEC) or one-word access of V words at p.
+template <class W, bool VEC, int V>
+__device__ __forceinline__ void ld_vec(W (&o)[V], const W* p) {
+  if constexpr (VEC) {
+    const uint4 a = *reinterpret_cast<const uint4*>(p);
+    __builtin_memcpy(o, &a, 16);
+  } else {
+    o[0] = p[0];
+  }
+}
+template <class W, bool VEC, int V>
+__device__ __forceinline__ void st_vec(W* p, const W (&r)[V]) {
+  if constexpr (VEC) {
+    uint4 o;
+    __builtin_memcpy(&o, r, 16);
+    *reinterpret_cast<uint4*>(p) = o;
+  } else {
+    p[0] = r[0];
+  }
+}
+
+// ModUp of the hybrid key-switch: digit d = blockIdx.y owns the cnt <= alpha
+// source limbs from d alpha on.  A thread reads its vector of each of them
+// once, takes y_i = x_i (Q_d/q_i)^-1 mod q_i, and writes for every limb t of
+// the key basis (tp: its tables, LE limbs) sum_i y_i conv[d][i][t] mod m_t with
+// conv = (Q_d/q_i) 2^w mod m_t: the fast base conversion in Montgomery form.
+// For t in the digit the constant row is one-hot -- Q_d/q_i = 0 mod q_t for
+// i != t, and y_t (Q_d/q_t) = x_t -- so the same sum stores x_t 2^w exactly
+// and no lane branches on t.  y_i < q_i may exceed m_t: the Shoup product takes
+// any word.  D is [LE][gridDim.y][B][N].  AMAX >= alpha keeps the y_i in
+// registers (the unrolled loop's `a < cnt` is uniform); AMAX == 0 serves any
+// alpha by recomputing y_i per target limb (the re-reads hit the cache).
+// blockIdx.z takes a run of tper target limbs: one run at large batches, several
+// where one ciphertext's vectors alone would leave most of the CUs idle.
+template <class W, bool VEC, int AMAX>
+__global__ void __launch_bounds__(256)
+k_modup(W* __restrict__ D, const W* __restrict__ x, TabPtrs<W> tp, const W* __restrict__ yinv,
+        const W* __restrict__ yinvp, const W* __restrict__ conv, const W* __restrict__ convp,
+        uint64_t limb_words, uint64_t src_ls, uint32_t alpha, uint32_t Lv, uint32_t LE, uint32_t tper) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint32_t d = blockIdx.y;
+  const uint32_t t0 = blockIdx.z * tper;
+  const uint32_t t1 = t0 + tper < LE ? t0 + tper : LE;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= limb_words) return;
+  const uint32_t first = d * alpha;
+  const uint32_t cnt = Lv - first < alpha ? Lv - first : alpha;
+  const W* xp = x + (uint64_t)first * src_ls + i;
+  const W* crow = conv + (uint64_t)d * alpha * LE;
+  const W* prow = convp + (uint64_t)d * alpha * LE;
+  W y[AMAX > 0 ? AMAX : 1][V];
+  if constexpr (AMAX > 0) {
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a) {
+      if ((uint32_t)a < cnt) {  // (uniform)
+        W xv[V];
+        ld_vec<W, VEC, V>(xv, xp + (uint64_t)a * src_ls);
+        const W q = tp.lc[first + a].q, c = yinv[first + a], cp = yinvp[first + a];
+#pragma unroll
+        for (int v = 0; v < V; ++v) y[a][v] = shoup_mul<W>(xv[v], c, cp, q);
+      }
+    }
+  }
+  for (uint32_t t = t0; t < t1; ++t) {
+    const W q = tp.lc[t].q;
+    W acc[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[v] = (W)0;
+    if constexpr (AMAX > 0) {
+#pragma unroll
+      for (int a = 0; a < AMAX; ++a) {
+        if ((uint32_t)a < cnt) {
+          const W c = crow[(uint64_t)a * LE + t], cp = prow[(uint64_t)a * LE + t];
+#pragma unroll
+          for (int v = 0; v < V; ++v) acc[v] = add_mod<W>(acc[v], shoup_mul<W>(y[a][v], c, cp, q), q);
+        }
+      }
+    } else {
+      for (uint32_t a = 0; a < cnt; ++a) {
+        W xv[V];
+        ld_vec<W, VEC, V>(xv, xp + (uint64_t)a * src_ls);
+        const W qs = tp.lc[first + a].q, ci = yinv[first + a], cip = yinvp[first + a];
+        const W c = crow[(uint64_t)a * LE + t], cp = prow[(uint64_t)a * LE + t];
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+          acc[v] = add_mod<W>(acc[v], shoup_mul<W>(shoup_mul<W>(xv[v], ci, cip, qs), c, cp, q), q);
+      }
+    }
+    st_vec<W, VEC, V>(D + ((uint64_t)t * gridDim.y + d) * limb_words + i, acc);
+  }
+}
+
+// ModDown of the hybrid key-switch: A is a coefficient-domain accumulator over
+// the key basis ([Lv + K][B][N] at limb stride a_ls, tp its tables).  A thread
+// reads its vector of the K special planes once, z_k = A_{p_k} (P/p_k)^-1 mod
+// p_k, and writes for every ciphertext limb j < Lv
+//   out_j = (A_j - sum_k z_k (P/p_k mod q_j)) P^-1 mod q_j  (+ add_j),
+// canonical, at limb stride out_ls (the addend, optional and uniform, at
+// add_ls).  z_k < p_k may exceed q_j: Shoup products.  KMAX as k_modup's AMAX;
+// blockIdx.y takes a run of jper output limbs, as k_modup's blockIdx.z.
+template <class W, bool VEC, int KMAX>
+__global__ void __launch_bounds__(256)
+k_moddown(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A, uint64_t a_ls, const W* add,
+          uint64_t add_ls, TabPtrs<W> tp, const W* __restrict__ pinv, const W* __restrict__ pinvp,
+          const W* __restrict__ pq, const W* __restrict__ pqp, const W* __restrict__ Pinv,
+          const W* __restrict__ Pinvp, uint64_t limb_words, uint32_t Lv, uint32_t K, uint32_t jper) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= limb_words) return;
+  const uint32_t j0 = blockIdx.y * jper;
+  const uint32_t j1 = j0 + jper < Lv ? j0 + jper : Lv;
+  const W* sp = A + (uint64_t)Lv * a_ls + i;
+  W z[KMAX > 0 ? KMAX : 1][V];
+  if constexpr (KMAX > 0) {
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      if ((uint32_t)k < K) {  // (uniform)
+        W av[V];
+        ld_vec<W, VEC, V>(av, sp + (uint64_t)k * a_ls);
+        const W p = tp.lc[Lv + k].q, c = pinv[k], cp = pinvp[k];
+#pragma unroll
+        for (int v = 0; v < V; ++v) z[k][v] = shoup_mul<W>(av[v], c, cp, p);
+      }
+    }
+  }
+  for (uint32_t j = j0; j < j1; ++j) {
+    const W q = tp.lc[j].q;
+    W cv[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) cv[v] = (W)0;
+    if constexpr (KMAX > 0) {
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+        if ((uint32_t)k < K) {
+          const W c = pq[(uint64_t)k * Lv + j], cp = pqp[(uint64_t)k * Lv + j];
+#pragma unroll
+          for (int v = 0; v < V; ++v) cv[v] = add_mod<W>(cv[v], shoup_mul<W>(z[k][v], c, cp, q), q);
+        }
+      }
+    } else {
+      for (uint32_t k = 0; k < K; ++k) {
+        W av[V];
+        ld_vec<W, VEC, V>(av, sp + (uint64_t)k * a_ls);
+        const W p = tp.lc[Lv + k].q, ci = pinv[k], cip = pinvp[k];
+        const W c = pq[(uint64_t)k * Lv + j], cp = pqp[(uint64_t)k * Lv + j];
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+          cv[v] = add_mod<W>(cv[v], shoup_mul<W>(shoup_mul<W>(av[v], ci, cip, p), c, cp, q), q);
+      }
+    }
+    W av[V], r[V];
+    ld_vec<W, VEC, V>(av, A + (uint64_t)j * a_ls + i);
+    const W c = Pinv[j], cp = Pinvp[j];
+#pragma unroll
+    for (int v = 0; v < V; ++v) r[v] = shoup_mul<W>(av[v] - cv[v] + q, c, cp, q);  // a - conv + q in (0, 2q)
+    if (add != nullptr) {  // (uniform)
+      W dv[V];
+      ld_vec<W, VEC, V>(dv, add + (uint64_t)j * add_ls + i);
+#pragma unroll
+      for (int v = 0; v < V; ++v) r[v] = add_mod<W>(r[v], dv[v], q);
+    }
+    st_vec<W, VEC, V>(out + (uint64_t)j * out_ls + i, r);
+  }
+}
+
 // rescale_into (poly.rs:212-225): out[l] = (c_l - (c_last mod q_l)) * q_last^-1.
 template <class W>
 __global__ void __launch_bounds__(256)
@@ -2513,6 +2679,75 @@ static hipError_t hoist_mac_t(const Launch& k, void* const* acc0, void* const* a
                      tab_ptrs<W>(k.t), k.t->log_n, limb_words, key_ls, (uint32_t)Ls, nt)
   if (vec) RNT_HM(true); else RNT_HM(false);
 #undef RNT_HM
+  return hipGetLastError();
+}
+
+// k.t: the key basis' tables, k.L = Lv + K, k.B the chunk's polys.
+// Workgroups from which a grid over the vectors alone fills the 256 CUs.
+constexpr uint64_t kSplitBlocks = 1024;
+template <class W>
+static hipError_t modup_t(const Launch& k, void* D, const void* x, uint64_t src_ls, const HybridConsts& hc) {
+  const uint64_t N = 1ull << k.t->log_n;
+  const uint64_t limb_words = (uint64_t)k.B * N;
+  if (hc.alpha == 0 || hc.beta == 0 || hc.Lv == 0 || k.L != (size_t)hc.Lv + hc.K || k.L > k.t->L ||
+      (uint64_t)hc.beta * hc.alpha < hc.Lv || (uint64_t)(hc.beta - 1) * hc.alpha >= hc.Lv || src_ls < limb_words)
+    return hipErrorInvalidValue;
+  if (limb_words == 0) return hipSuccess;
+  constexpr int V = 16 / (int)sizeof(W);
+  // 16-byte accesses: whole vectors within a plane, every plane 16-byte aligned
+  const bool vec = N % V == 0 && src_ls % V == 0 && ((uintptr_t)D | (uintptr_t)x) % 16 == 0;
+  const uint64_t per = vec ? limb_words / V : limb_words;
+  const uint64_t bx = (per + 255) / 256;
+  if (bx > 0x7fffffffull || hc.beta > 65535) return hipErrorInvalidConfiguration;
+  // runs of target limbs per lane: all of them in one lane where the vectors
+  // alone fill the device (kSplitBlocks workgroups), else split over grid.z
+  const uint64_t runs = std::min<uint64_t>(k.L, std::max<uint64_t>(kSplitBlocks / (bx * hc.beta), 1));
+  const uint32_t tper = (uint32_t)((k.L + runs - 1) / runs);
+  const dim3 grid((unsigned)bx, (unsigned)hc.beta, (unsigned)((k.L + tper - 1) / tper));
+#define RNT_MU(VEC, AMAX)                                                                              \
+  hipLaunchKernelGGL((k_modup<W, VEC, AMAX>), grid, dim3(256), 0, k.s, (W*)D, (const W*)x,             \
+                     tab_ptrs<W>(k.t), (const W*)hc.yinv, (const W*)hc.yinvp, (const W*)hc.conv,       \
+                     (const W*)hc.convp, limb_words, src_ls, hc.alpha, hc.Lv, (uint32_t)k.L, tper)
+#define RNT_MU_A(AMAX) do { if (vec) RNT_MU(true, AMAX); else RNT_MU(false, AMAX); } while (0)
+  if (hc.alpha <= 4) RNT_MU_A(4);
+  else if (hc.alpha <= 8) RNT_MU_A(8);
+  else if (hc.alpha <= 16) RNT_MU_A(16);
+  else RNT_MU_A(0);
+#undef RNT_MU_A
+#undef RNT_MU
+  return hipGetLastError();
+}
+
+template <class W>
+static hipError_t moddown_t(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
+                            const void* add, uint64_t add_ls, const HybridConsts& hc) {
+  const uint64_t N = 1ull << k.t->log_n;
+  const uint64_t limb_words = (uint64_t)k.B * N;
+  if (hc.Lv == 0 || hc.K == 0 || k.L != (size_t)hc.Lv + hc.K || k.L > k.t->L || out_ls < limb_words ||
+      a_ls < limb_words || (add && add_ls < limb_words))
+    return hipErrorInvalidValue;
+  if (limb_words == 0) return hipSuccess;
+  constexpr int V = 16 / (int)sizeof(W);
+  const bool vec = N % V == 0 && out_ls % V == 0 && a_ls % V == 0 && (!add || add_ls % V == 0) &&
+                   ((uintptr_t)out | (uintptr_t)A | (uintptr_t)add) % 16 == 0;
+  const uint64_t per = vec ? limb_words / V : limb_words;
+  const uint64_t bx = (per + 255) / 256;
+  if (bx > 0x7fffffffull) return hipErrorInvalidConfiguration;
+  const uint64_t runs = std::min<uint64_t>(hc.Lv, std::max<uint64_t>(kSplitBlocks / bx, 1));
+  const uint32_t jper = (uint32_t)((hc.Lv + runs - 1) / runs);
+  const dim3 grid((unsigned)bx, (unsigned)((hc.Lv + jper - 1) / jper));
+#define RNT_MD(VEC, KMAX)                                                                              \
+  hipLaunchKernelGGL((k_moddown<W, VEC, KMAX>), grid, dim3(256), 0, k.s, (W*)out, out_ls,               \
+                     (const W*)A, a_ls, (const W*)add, add_ls, tab_ptrs<W>(k.t), (const W*)hc.pinv,     \
+                     (const W*)hc.pinvp, (const W*)hc.pq, (const W*)hc.pqp, (const W*)hc.Pinv,          \
+                     (const W*)hc.Pinvp, limb_words, hc.Lv, hc.K, jper)
+#define RNT_MD_K(KMAX) do { if (vec) RNT_MD(true, KMAX); else RNT_MD(false, KMAX); } while (0)
+  if (hc.K <= 4) RNT_MD_K(4);
+  else if (hc.K <= 8) RNT_MD_K(8);
+  else if (hc.K <= 16) RNT_MD_K(16);
+  else RNT_MD_K(0);
+#undef RNT_MD_K
+#undef RNT_MD
   return hipGetLastError();
 }
 
@@ -3121,6 +3356,14 @@ hipError_t launch_hoist_mac(const Launch& k, void* const* acc0, void* const* acc
                             const void* const* key_a, const void* const* key_b, uint64_t key_ls) {
   RNT_WIDE(hoist_mac_t<uint32_t>(k, acc0, acc1, nt, d, key_a, key_b, key_ls),
            hoist_mac_t<uint64_t>(k, acc0, acc1, nt, d, key_a, key_b, key_ls));
+}
+hipError_t launch_modup(const Launch& k, void* D, const void* x, uint64_t src_ls, const HybridConsts& hc) {
+  RNT_WIDE(modup_t<uint32_t>(k, D, x, src_ls, hc), modup_t<uint64_t>(k, D, x, src_ls, hc));
+}
+hipError_t launch_moddown(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
+                          const void* add, uint64_t add_ls, const HybridConsts& hc) {
+  RNT_WIDE(moddown_t<uint32_t>(k, out, out_ls, A, a_ls, add, add_ls, hc),
+           moddown_t<uint64_t>(k, out, out_ls, A, a_ls, add, add_ls, hc));
 }
 hipError_t launch_mont_one(const Launch& k, void* out) {
   RNT_WIDE(mont_one_t<uint32_t>(k, out), mont_one_t<uint64_t>(k, out));

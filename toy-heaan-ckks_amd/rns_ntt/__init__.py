@@ -33,6 +33,10 @@ __all__ = [
     "RnsBasis",
     "RnsPoly",
     "RnsGadgetKey",
+    "RnsHybridKey",
+    "keyswitch_hybrid",
+    "rotate_ciphertext_hybrid",
+    "mul_ciphertexts_hybrid",
     "Ciphertext",
     "generate_primes",
     "is_ntt_friendly_prime",
@@ -614,8 +618,17 @@ class Ciphertext:
     logq: int = 0
 
 
+def _require_class(key, cls, what: str) -> None:
+    """``key`` must be of the class the call reads (RnsGadgetKey for the
+    gadget calls, RnsHybridKey for the hybrid ones): the library sees only
+    buffers and would at best report a poly count."""
+    if not isinstance(key, cls):
+        raise TypeError(f"{what}: needs an {cls.__name__}, got {type(key).__name__}")
+
+
 def keyswitch(d: RnsPoly, key: RnsGadgetKey) -> tuple[RnsPoly, RnsPoly]:
     """Gadget sum (engine.rs:505-528 / 429-452) on a coefficient-domain batch."""
+    _require_class(key, RnsGadgetKey, "keyswitch")
     acc0, acc1 = d._like(), d._like()
     check(load().rnt_keyswitch(acc0.handle, acc1.handle, d.handle, key.a.handle, key.b.handle))
     return acc0, acc1
@@ -623,6 +636,7 @@ def keyswitch(d: RnsPoly, key: RnsGadgetKey) -> tuple[RnsPoly, RnsPoly]:
 
 def mul_ciphertexts_gadget(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsGadgetKey) -> Ciphertext:
     """engine.rs:473-539."""
+    _require_class(rlk, RnsGadgetKey, "mul_ciphertexts_gadget")
     assert ct1.logq == ct2.logq, "logq mismatch in gadget multiplication"
     basis = ct1.c0.basis
     out0, out1 = ct1.c0._like(basis), ct1.c0._like(basis)
@@ -642,12 +656,96 @@ def _require_form(keys, hoisted: bool, what: str) -> None:
 
 def rotate_ciphertext(ct: Ciphertext, rotk: RnsGadgetKey) -> Ciphertext:
     """engine.rs:412-463."""
+    _require_class(rotk, RnsGadgetKey, "rotate_ciphertext")
     _require_form(rotk, False, "rotate_ciphertext")
     basis = ct.c0.basis
     out0, out1 = ct.c0._like(basis), ct.c0._like(basis)
     check(load().rnt_ct_rotate(out0.handle, out1.handle, ct.c0.handle, ct.c1.handle,
                                int(rotk.rotation or 0), rotk.a.handle, rotk.b.handle))
     return Ciphertext(out0, out1, ct.logp, ct.logq)
+
+
+class RnsHybridKey:
+    """A hybrid (special-prime) relinearisation or rotation key: ``a`` and
+    ``b`` are RnsPoly batches of ``beta = ceil(L / alpha)`` polys on the
+    EXTENDED basis ``q_0..q_{L-1}, p_0..p_{K-1}``, made NTT-resident here
+    (rnt_key_prepare).  ``alpha`` is the digit size the key was generated
+    for and ``rotation`` the step of a rotation key."""
+
+    def __init__(self, a: RnsPoly, b: RnsPoly, alpha: int, rotation: Optional[int] = None):
+        if int(alpha) < 1:
+            raise ValueError("RnsHybridKey: alpha must be at least 1")
+        if a.basis is not b.basis and a.basis.moduli() != b.basis.moduli():
+            raise ValueError("RnsHybridKey: the key halves are on different bases")
+        self.a = a
+        self.b = b
+        self.alpha = int(alpha)
+        self.rotation = rotation
+        check(load().rnt_key_prepare(a.handle, b.handle))
+
+    @classmethod
+    def from_channels(cls, a_channels, b_channels, ext_basis: RnsBasis, alpha: int,
+                      rotation: Optional[int] = None) -> "RnsHybridKey":
+        """a_channels / b_channels: [beta][L + K][N] coefficient-domain residues."""
+        return cls(RnsPoly.from_channels(np.asarray(a_channels, dtype=np.uint64), ext_basis),
+                   RnsPoly.from_channels(np.asarray(b_channels, dtype=np.uint64), ext_basis), alpha, rotation)
+
+    def restrict(self, ext_basis_lv: RnsBasis) -> "RnsHybridKey":
+        """The key of a lower level: ``ext_basis_lv`` is a root basis over
+        ``q_0..q_{L'-1}, p_0..p_{K-1}``; the result holds the first
+        ``ceil(L'/alpha)`` polys on the kept limbs (the digit boundaries do not
+        move).  Set-up: the polys make one host round trip, in the NTT domain
+        (a limb's transform does not depend on the others)."""
+        full = self.a.basis.moduli()
+        low = ext_basis_lv.moduli()
+        lv = 0
+        while lv < min(len(full), len(low)) and full[lv] == low[lv]:
+            lv += 1
+        if lv == len(full) == len(low):
+            keep, n_polys = list(range(len(full))), self.a.n_polys
+        else:
+            k = len(low) - lv
+            if k < 1 or lv < 1 or low[lv:] != full[len(full) - k:]:
+                raise ValueError("restrict: the basis is not a prefix of the key's ciphertext moduli followed by "
+                                 "its special primes")
+            keep = list(range(lv)) + list(range(len(full) - k, len(full)))
+            n_polys = -(-lv // self.alpha)
+        if ext_basis_lv.degree != self.a.basis.degree:
+            raise ValueError("restrict: ring degrees differ")
+        halves = []
+        for p in (self.a, self.b):
+            ch = p.channels_of(0, n_polys)[:, keep, :]
+            halves.append(RnsPoly.from_channels(ch, ext_basis_lv, in_ntt_domain=True))
+        return RnsHybridKey(halves[0], halves[1], self.alpha, self.rotation)
+
+
+def keyswitch_hybrid(d: RnsPoly, key: RnsHybridKey) -> tuple[RnsPoly, RnsPoly]:
+    """The hybrid key-switch sums of a coefficient-domain batch
+    (rnt_keyswitch_hybrid): ``acc0 + acc1 s = d s' + small``."""
+    _require_class(key, RnsHybridKey, "keyswitch_hybrid")
+    acc0, acc1 = d._like(), d._like()
+    check(load().rnt_keyswitch_hybrid(acc0.handle, acc1.handle, d.handle, key.a.handle, key.b.handle, key.alpha))
+    return acc0, acc1
+
+
+def rotate_ciphertext_hybrid(ct: Ciphertext, rotk: RnsHybridKey) -> Ciphertext:
+    """rotate_ciphertext with the hybrid key-switch (rnt_ct_rotate_hybrid):
+    the same rotation with less noise, not the gadget call's words."""
+    _require_class(rotk, RnsHybridKey, "rotate_ciphertext_hybrid")
+    out0, out1 = ct.c0._like(), ct.c0._like()
+    check(load().rnt_ct_rotate_hybrid(out0.handle, out1.handle, ct.c0.handle, ct.c1.handle,
+                                      int(rotk.rotation or 0), rotk.a.handle, rotk.b.handle, rotk.alpha))
+    return Ciphertext(out0, out1, ct.logp, ct.logq)
+
+
+def mul_ciphertexts_hybrid(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsHybridKey) -> Ciphertext:
+    """mul_ciphertexts_gadget with the hybrid key-switch (rnt_ct_mul_relin_hybrid)."""
+    _require_class(rlk, RnsHybridKey, "mul_ciphertexts_hybrid")
+    assert ct1.logq == ct2.logq, "logq mismatch in hybrid multiplication"
+    out0, out1 = ct1.c0._like(), ct1.c0._like()
+    check(load().rnt_ct_mul_relin_hybrid(out0.handle, out1.handle, ct1.c0.handle, ct1.c1.handle,
+                                         ct2.c0.handle, ct2.c1.handle, rlk.a.handle, rlk.b.handle, rlk.alpha))
+    return Ciphertext(out0, out1, ct1.logp + ct2.logp, ct1.logq)
 
 
 class RnsGadgetKeySet:

@@ -23,9 +23,10 @@ from typing import Optional
 
 import numpy as np
 
-from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsGadgetKeySet, RnsPoly,
-               bsgs_diagonal_rows, linear_transform, linear_transform_bsgs, linear_transform_bsgs_hoisted,
-               mul_ciphertexts_gadget, rescale_ciphertext, rotate_ciphertext, rotate_ciphertext_hoisted)
+from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsGadgetKeySet, RnsHybridKey,
+               RnsPoly, bsgs_diagonal_rows, linear_transform, linear_transform_bsgs, linear_transform_bsgs_hoisted,
+               mul_ciphertexts_gadget, mul_ciphertexts_hybrid, rescale_ciphertext, rotate_ciphertext,
+               rotate_ciphertext_hoisted, rotate_ciphertext_hybrid)
 
 
 @dataclass
@@ -43,10 +44,22 @@ class CkksEngine:
     reference passes sqrt(error_variance) in key generation (engine.rs:316)
     but error_variance itself in encrypt (engine.rs:92).  Both call sites
     here take ``error_std``, and the caller chooses its value.
+
+    ``special_moduli`` (K primes, none of them a ciphertext modulus) turns on
+    the hybrid key-switch: ``ext_basis`` is then the basis over ``moduli +
+    special_moduli`` the hybrid keys live on and ``basis`` its
+    ``drop_last(K)`` view; everything else works on ``basis`` as before.
     """
 
     def __init__(self, moduli, degree: int, error_std: float = 3.2,
-                 hamming_weight: Optional[int] = None, device: int = 0):
+                 hamming_weight: Optional[int] = None, device: int = 0, special_moduli=None):
+        self.ext_basis = None
+        self.special_moduli = [int(p) for p in special_moduli] if special_moduli is not None else []
+        if self.special_moduli:
+            if isinstance(moduli, RnsBasis):
+                raise ValueError("special_moduli need the ciphertext moduli as a list (the extended basis is the root)")
+            self.ext_basis = RnsBasis(list(moduli) + self.special_moduli, degree, device=device)
+            moduli = self.ext_basis.drop_last(len(self.special_moduli))
         # an existing RnsBasis is shared, as CkksEngine::new(basis.clone(), ..)
         # shares the Arc (engine.rs:36-41): a level-l engine built on a
         # rescaled ciphertext's basis encrypts onto that same basis
@@ -121,6 +134,62 @@ class CkksEngine:
 
     def generate_gadget_rotation_key(self, sk: RnsPoly, rotation: int, rng) -> RnsGadgetKey:
         return self._gadget_key(sk, sk.rotate_slots(rotation), rng, rotation)
+
+    # -- hybrid keys (special primes) -----------------------------------------
+    def _lift(self, poly: RnsPoly, basis: RnsBasis, count: int) -> RnsPoly:
+        """``count`` copies of a small polynomial (a secret, a product of
+        secrets) on ``basis``, from its centred coefficients."""
+        c = np.array(poly.to_coeffs_exact(), dtype=object).reshape(-1)
+        mods = basis.moduli()
+        ch = np.stack([np.array([int(v) % m for v in c], dtype=np.uint64) for m in mods])
+        return RnsPoly.from_channels(np.broadcast_to(ch, (count,) + ch.shape).copy(), basis)
+
+    def _hybrid_key(self, sk: RnsPoly, target: RnsPoly, rng, alpha: int, rotation=None) -> RnsHybridKey:
+        """b_d = -(a_d s) + e_d + G_d for every digit d as one batch of beta
+        polys on ext_basis: limb t of G_d is P s' mod q_t on the limbs of
+        digit d and zero elsewhere (every special limb included)."""
+        if self.ext_basis is None:
+            raise ValueError("hybrid keys need an engine built with special_moduli")
+        alpha = int(alpha)
+        if alpha < 1:
+            raise ValueError("alpha must be at least 1")
+        q = self.basis.moduli()
+        L, K, n = len(q), len(self.special_moduli), self.degree
+        beta = -(-L // alpha)
+        P = 1
+        for p in self.special_moduli:
+            P *= p
+        qd_max = 1
+        for d in range(beta):
+            qd = 1
+            for i in range(d * alpha, min((d + 1) * alpha, L)):
+                qd *= q[i]
+            qd_max = max(qd_max, qd)
+        if P < alpha * qd_max:
+            raise ValueError(f"the special primes are too small for alpha = {alpha}: P has {P.bit_length()} bits, "
+                             f"alpha max Q_d {(alpha * qd_max).bit_length()}")
+        t = target.channels()  # [L][N]: s' mod q_t, coefficient domain
+        plain = np.zeros((beta, L + K, n), dtype=np.uint64)
+        for d in range(beta):
+            for i in range(d * alpha, min((d + 1) * alpha, L)):
+                plain[d, i] = np.array([int(v) * (P % q[i]) % q[i] for v in t[i]], dtype=np.uint64)
+        s_rep = self._lift(sk, self.ext_basis, beta)
+        a = self._uniform(rng, count=beta, basis=self.ext_basis)
+        if isinstance(rng, DeviceRng):
+            e = RnsPoly.sample_gaussian(self.error_std, self.ext_basis, rng, beta)
+        else:
+            e = RnsPoly.from_coeffs(self._gaussian(rng, beta), self.ext_basis)
+        b = -(a * s_rep) + e + RnsPoly.from_channels(plain, self.ext_basis)
+        return RnsHybridKey(a, b, alpha, rotation)
+
+    def generate_hybrid_relin_key(self, sk: RnsPoly, rng, alpha: int) -> RnsHybridKey:
+        return self._hybrid_key(sk, sk * sk, rng, alpha)
+
+    def generate_hybrid_rotation_key(self, sk: RnsPoly, rotation: int, rng, alpha: int) -> RnsHybridKey:
+        return self._hybrid_key(sk, sk.rotate_slots(rotation), rng, alpha, rotation)
+
+    rotate_ciphertext_hybrid = staticmethod(rotate_ciphertext_hybrid)
+    mul_ciphertexts_hybrid = staticmethod(mul_ciphertexts_hybrid)
 
     # -- encryption (engine.rs:84-127) -----------------------------------------
     def encrypt(self, plaintext, pk: PublicKey, rng, logp: int = 0,
