@@ -91,8 +91,8 @@ int rnt_device_count(int* n);
  * "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt", "sfft",
  * "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd",
  * "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
- * "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown"), the launch
- * count and summed device milliseconds since enabling. */
+ * "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown",
+ * "moddown_auto"), the launch count and summed device milliseconds since enabling. */
 int rnt_profile_enable(const rnt_ctx* ctx, int enable);
 int rnt_profile_read(const rnt_ctx* ctx, const char* kernel, uint64_t* launches,
                      double* total_ms);
@@ -460,6 +460,75 @@ int rnt_ct_rotate_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const 
 int rnt_ct_mul_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
                             const rnt_buf* c0p, const rnt_buf* c1p,
                             const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha);
+/* ---- hoisted rotations and the baby-step giant-step transform on hybrid
+ * keys (DESIGN.md "Hoisted hybrid rotations") ------------------------------
+ * Notation as above: C, E, beta = ceil(Lv / alpha), ModUp_d, ModDown; sigma_k =
+ * rotate_slots(., k), one automorphism by g = 5^|k| (times 2N - 1 for k < 0).
+ * The HOISTING FORM of a hybrid rotation key for step k is NTT(sigma_k^-1(a_d)),
+ * NTT(sigma_k^-1(b_d)) over E for d < beta: rnt_key_prepare_hoisted(key_a,
+ * key_b, k) on the beta-poly buffers over E (it works limb by limb, so the
+ * restriction of a hoisting-form key to a lower level is the hoisting form of
+ * the restricted key).  The hoisted hybrid rotation of (c0, c1) by k != 0, with
+ * D_d = ModUp_d(c1) over E:
+ *   out0 = sigma_k(c0 + ModDown(sum_d D_d * sigma_k^-1(key_b[d])))
+ *   out1 = sigma_k(     ModDown(sum_d D_d * sigma_k^-1(key_a[d])))
+ * (negacyclic products over E; canonical outputs, coefficient domain, over C);
+ * k == 0 is the identity and does not read the key.  The ORDER is part of the
+ * definition: ModDown is coefficient-wise but does not commute with negation
+ * (on a negated coefficient the quotient differs by up to K), so sigma_k stands
+ * outside ModDown.  It is also what runs: NTT(D_d) carries no step and is
+ * computed once for every step.  It is a valid rotation -- sigma_k^-1(key)
+ * switches from s to sigma_k^-1(s), the inner pair decrypts c0 + c1 s under
+ * sigma_k^-1(s) and sigma_k of it the rotated message under s, with
+ * rnt_ct_rotate_hybrid's error bound since sigma preserves norms -- but NOT
+ * rnt_ct_rotate_hybrid's words: there ModUp sees sigma_k(c1).
+ *
+ * rnt_ct_rotate_hybrid_hoisted: n_steps such rotations of every ciphertext of
+ * the batch with one ModUp and one forward transform.  c0, c1: B polys over C,
+ * coefficient domain.  out0/out1: n_steps * B polys over C, rotation t of
+ * ciphertext b at poly t B + b; no output aliases an input or the other output.
+ * keys_a/keys_b: n_steps * beta polys over E, step t's key at [t beta, (t + 1)
+ * beta) in the hoisting form for steps[t]; a step-0 slot is ignored and the
+ * buffers may be NULL when every step is 0; steps may be negative or repeated.
+ * Errors: rnt_keyswitch_hybrid's rules and statuses for alpha, degree, device,
+ * moduli prefix, word width and key domain; a key set of another size ->
+ * RNT_ERR_CHANNEL_COUNT (fields: n_steps * beta, got); n_steps == 0, outputs of
+ * the wrong size, aliasing -> RNT_ERR_BAD_ARGUMENT; an NTT-domain ciphertext ->
+ * RNT_ERR_DOMAIN_MISMATCH; a workspace that does not fit the device ->
+ * RNT_ERR_OUT_OF_MEMORY.  A refused call leaves its outputs untouched.  The
+ * library cannot tell a hoisting-form key from an ordinary one: passing the
+ * wrong form gives a wrong, not a rejected, result.  The first call of an (E,
+ * Lv, alpha) triple builds the constants and cannot be recorded. */
+int rnt_ct_rotate_hybrid_hoisted(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                 const int32_t* steps, size_t n_steps,
+                                 const rnt_buf* keys_a, const rnt_buf* keys_b, size_t alpha);
+/* The baby-step giant-step linear transform on hybrid keys.  diag[j n_baby + i]
+ * in the NTT domain over C as rnt_ct_linear_bsgs takes it; baby keys in
+ * hoisting form, giant keys ordinary (rnt_key_prepare), every key on one E with
+ * one alpha, each set laid out as above (n beta polys).
+ *   R_i = the hoisted hybrid rotation of (c0, c1) by b_i (the ciphertext itself
+ *         for b_i = 0)
+ *   V_j = sum_i diag[j n_baby + i] * R_i            (both components, over C)
+ *   Z = { j : g_j = 0 }, NZ = the others
+ *   A0 = sum_{j in NZ} sum_d ModUp_d(sigma_{g_j}(V1_j)) * giant_key_b[j][d]
+ *        (over E); A1 with giant_key_a
+ *   out0 = sum_{j in Z} V0_j + sum_{j in NZ} sigma_{g_j}(V0_j) + ModDown(A0)
+ *   out1 = sum_{j in Z} V1_j                                  + ModDown(A1)
+ * One ModDown per output component however many giants there are (none when NZ
+ * is empty): NOT the words of a composition of rnt_ct_rotate_hybrid and rnt_add
+ * -- a ModDown of a sum is not the sum of ModDowns -- but the same decryption,
+ * the ModDown error entering once instead of |NZ| times.  With n_giant = 1 and
+ * g_0 = 0 it is the diagonal-method transform over hoisted hybrid rotations.
+ * Aliasing as rnt_ct_linear_bsgs (out0 == c0 and out1 == c1 allowed); a stage's
+ * key buffers may be NULL when all its steps are 0; errors as above, and as
+ * rnt_ct_linear_bsgs for the plaintexts; baby and giant keys on different key
+ * bases -> RNT_ERR_BASIS_MISMATCH.  The library cannot tell a hoisting-form
+ * key from an ordinary one. */
+int rnt_ct_linear_bsgs_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                              const int32_t* baby_steps, size_t n_baby,
+                              const int32_t* giant_steps, size_t n_giant, const rnt_buf* diag,
+                              const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
+                              const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b, size_t alpha);
 /* polys [src_first, src_first + count) of src -> [dst_first, ...) of dst (same
  * context; dst takes src's domain, which must equal dst's unless the copy
  * covers all of dst).  A range outside either batch -> RNT_ERR_BAD_ARGUMENT. */

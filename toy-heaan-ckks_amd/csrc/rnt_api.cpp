@@ -97,7 +97,7 @@ const char* const kKernelNames[rnt::K_COUNT] = {
     "col_fwd", "row_fwd", "row_inv", "row_mul", "col_inv", "elementwise", "rescale",
     "automorphism", "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt",
     "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
-    "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown"};
+    "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto"};
 
 // A profiling call failed: clear the runtime's slot, keep the first failure
 // in the profiler, and stop profiling (rnt_profile_read reports it).
@@ -291,6 +291,24 @@ static size_t pool_cap(int device) {  // g_pool_mu held
   const size_t cap = hipMemGetInfo(&free_b, &total_b) == hipSuccess ? total_b / 8 : ((size_t)8 << 30);
   caps.push_back({device, cap});
   return cap;
+}
+
+// A stream about to be destroyed, already synchronised: the idle blocks last
+// used on it are complete, so they drop their events -- an event must not
+// outlive the stream it was last recorded on (the runtime consults that stream
+// when the event is waited for, as pool_take's host wait does while a graph is
+// being recorded).
+static void pool_forget_stream(hipStream_t s) {
+  std::vector<hipEvent_t> gone;
+  {
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    for (PoolBlock& b : g_pool)
+      if (b.s == s && b.ev) {
+        gone.push_back(b.ev);
+        b.ev = nullptr;
+      }
+  }
+  for (hipEvent_t e : gone) cleanup(hipEventDestroy(e), "hipEventDestroy(block of a stream being destroyed)");
 }
 
 static void pool_release(const PoolBlock& w) {  // g_pool_mu NOT held
@@ -567,6 +585,7 @@ rnt::Tables::~Tables() {
     cleanup(hipStreamSynchronize(stream), "hipStreamSynchronize(context teardown)");
   if (own_stream) {
     cleanup(hipStreamSynchronize(own_stream), "hipStreamSynchronize(context teardown)");
+    pool_forget_stream(own_stream);
     cleanup(hipStreamDestroy(own_stream), "hipStreamDestroy(context teardown)");
   }
   for (auto& e : resc_ext) cleanup(hipFree(e.second), "hipFree(context tables)");
@@ -790,6 +809,10 @@ extern "C" int rnt_ctx_create(uint32_t log_n, const uint64_t* moduli, size_t cou
     // RNT_KS_DIAG=0 transforms every (i, j) (A/B)
     t->ks_diag = env_long("RNT_KS_DIAG", 1) != 0;
     t->rot_fuse = (int)env_long("RNT_ROT_FUSE", 1);
+    {
+      const long m = env_long("RNT_MODDOWN_AUTO", 1);
+      t->md_auto = m == 0 || m == 2 ? (int)m : 1;
+    }
     // the whole-plane product and MFMA transforms are the default where they
     // apply (N = 2^16, u32); RNT_PLANE=0 keeps the four-step kernels
     t->plane = env_long("RNT_PLANE", 1) != 0 ? 1 : 0;
@@ -3550,6 +3573,410 @@ extern "C" int rnt_ct_linear_bsgs_hoisted(rnt_buf* out0, rnt_buf* out1, const rn
                                           const rnt_buf* giant_keys_b) {
   return ct_linear_bsgs_body(out0, out1, c0, c1, baby_steps, n_baby, giant_steps, n_giant, diag, baby_keys_a,
                              baby_keys_b, giant_keys_a, giant_keys_b, true);
+}
+
+// ---------------------------------------------------------------------------
+// hoisted rotations and the baby-step giant-step transform on hybrid keys:
+//   out_t = sigma_t(c0 + ModDown(sum_d D_d sigma_t^-1(key_b[t][d]))),
+//           sigma_t(     ModDown(sum_d D_d sigma_t^-1(key_a[t][d])))
+// with D_d = ModUp_d(c1) raised and transformed once for every step
+// ---------------------------------------------------------------------------
+namespace {
+
+// The argument rules of one stage's hybrid key set (n steps, n beta polys over
+// E): hybrid_check's on a one-key view, then the key-count rule of
+// rnt_ct_rotate_hoisted.  *have: the stage has keys (else nothing is checked:
+// every step is 0 and both buffers are NULL).
+int hybrid_set_check(const char* name, const rnt_ctx* C, const int32_t* steps, size_t n_steps,
+                     const rnt_buf* keys_a, const rnt_buf* keys_b, size_t alpha, HybridPlan* pl, bool* have) {
+  size_t nz = 0;
+  for (size_t t = 0; t < n_steps; ++t) nz += steps[t] != 0;
+  *have = nz || keys_a || keys_b;
+  if (!*have) return RNT_OK;
+  if (int rc = check_buf(keys_a, name)) return rc;
+  if (int rc = check_buf(keys_b, name)) return rc;
+  const size_t beta = alpha >= C->L ? 1 : (C->L + alpha - 1) / alpha;
+  rnt_buf va, vb;  // step 0's slot: a key of beta polys for hybrid_check
+  auto view = [&](rnt_buf& v, const rnt_buf* kbuf) {
+    v.ctx = kbuf->ctx;
+    v.n_polys = beta;
+    v.data = kbuf->data;
+    v.in_ntt = kbuf->in_ntt;
+    v.owns = false;
+  };
+  view(va, keys_a);
+  view(vb, keys_b);
+  if (int rc = hybrid_check(name, C, &va, &vb, alpha, pl)) return rc;
+  const size_t want = n_steps * beta;
+  if (n_steps > SIZE_MAX / beta || keys_a->n_polys != want || keys_b->n_polys != want)
+    return fail_fields(RNT_ERR_CHANNEL_COUNT, want, keys_a->n_polys != want ? keys_a->n_polys : keys_b->n_polys,
+                       "%s: the key set must hold one poly per step and digit (%zu)", name, want);
+  return RNT_OK;
+}
+
+rnt::Launch hybrid_launch(const HybridPlan& pl, size_t c) {
+  rnt::Launch k;
+  k.t = pl.E->t.get();
+  k.L = pl.LE;
+  k.B = c;
+  k.s = pl.C->t->stream;
+  return k;
+}
+
+// Whether the tail of a chunk of bc ciphertexts is k_moddown_auto.  Its result
+// planes leave as single words.  Measured (profiles/
+// rotate_hybrid_hoisted_bench.jsonl): with 4 MiB a
+// component (one ciphertext, 2^16 x 16) the fused kernel is the faster tail,
+// 1.03-1.08x; with 16 MiB (2^17 x 32) and with 256 MiB (64 ciphertexts) the
+// three un-fused launches win on eight steps, 1.04x and 1.10x.  Nothing was
+// measured between 4 and 16 MiB: the crossover is put at the smallest size at
+// which the un-fused tail was seen to win, which is a guess, as is the reading
+// that the partial lines stop meeting in the L2s there.
+constexpr size_t kMdAutoBytes = (size_t)16 << 20;
+bool tail_fused(const rnt::Tables* tc, size_t Lv, size_t bc) {
+  if (tc->md_auto != 1) return tc->md_auto == 2;
+  return Lv * bc * tc->n * word_bytes(tc) < kMdAutoBytes;
+}
+
+// The per-step tail: dst = sigma_g(ModDown(A) (+ add)) at limb stride dst_ls,
+// A the coefficient-domain accumulator of c polys over E.  fused: one
+// k_moddown_auto; else k_moddown into TMP, the automorphism launch into TMP +
+// one block and a strided copy (TMP: two blocks of Lv c N words).
+int hybrid_tail(const HybridPlan& pl, size_t c, char* dst, uint64_t dst_ls, const char* A, const void* add,
+                uint64_t add_ls, uint64_t g, char* TMP, bool fused) {
+  const rnt::Tables* tc = pl.C->t.get();
+  const rnt::Launch k = hybrid_launch(pl, c);
+  const uint64_t cls = (uint64_t)c * tc->n;
+  if (fused) {
+    LAUNCH_ON(tc, k.s, rnt::K_MODDOWN_AUTO, rnt::launch_moddown_auto(k, dst, dst_ls, A, cls, add, add_ls, g, pl.hc),
+              "ModDown with automorphism");
+    return RNT_OK;
+  }
+  const size_t wb = word_bytes(tc);
+  char* T2 = TMP + pl.Lv * cls * wb;
+  LAUNCH_ON(tc, k.s, rnt::K_MODDOWN, rnt::launch_moddown(k, TMP, cls, A, cls, add, add_ls, pl.hc), "ModDown");
+  rnt::Launch kc;
+  kc.t = tc;
+  kc.L = pl.Lv;
+  kc.B = c;
+  kc.s = tc->stream;
+  LAUNCH(tc, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, T2, TMP, g), "automorphism");
+  LAUNCH(tc, rnt::K_COPY, rnt::launch_copy_rows(kc.s, dst, dst_ls * wb, T2, cls * wb, cls * wb, pl.Lv),
+         "rotation into its output polys");
+  return RNT_OK;
+}
+
+// The hoisted hybrid sums of one chunk (c polys of c1 at limb stride x1_ls):
+// one ModUp and one forward transform of D ([LE][beta c][N]) on E's tables,
+// then one k_hoist_mac launch per group of kHoistT nonzero steps into ACC
+// (2 kHoistT blocks of [LE][c][N]), both accumulators taken back to the
+// coefficient domain, and finish(t, A0, A1) for every step t of the group:
+// A0 = sum_d D_d sigma_t^-1(key_b[t][d]) over E.
+template <class Finish>
+int hybrid_hoist_chunk(const HybridPlan& pl, size_t c, char* D, char* ACC, const void* x1, uint64_t x1_ls,
+                       const int32_t* steps, size_t n_steps, const rnt_buf* keys_a, const rnt_buf* keys_b,
+                       Finish&& finish) {
+  const rnt::Tables* tc = pl.C->t.get();
+  const size_t n = tc->n, wb = word_bytes(tc);
+  const rnt::Launch k = hybrid_launch(pl, c);
+  const size_t pe = pl.LE * c * n * wb;
+  const uint64_t cls = (uint64_t)c * n;
+  bool any_rot = false;
+  for (size_t t = 0; t < n_steps; ++t) any_rot = any_rot || steps[t] != 0;
+  if (!any_rot) return RNT_OK;
+  LAUNCH_ON(tc, k.s, rnt::K_MODUP, rnt::launch_modup(k, D, x1, x1_ls, pl.hc), "ModUp");
+  rnt::Launch kd = k;
+  kd.B = pl.beta * c;
+  if (int rc = fwd_raw(kd, D, (uint64_t)kd.B * n, tc)) return rc;
+  rnt::Launch km = k;
+  km.Ls = pl.beta;
+  for (size_t t = 0; t < n_steps;) {
+    size_t idx[rnt::kHoistT];
+    void* a0[rnt::kHoistT] = {};
+    void* a1[rnt::kHoistT] = {};
+    const void* ka[rnt::kHoistT] = {};
+    const void* kb[rnt::kHoistT] = {};
+    uint32_t nt = 0;
+    for (; t < n_steps && nt < rnt::kHoistT; ++t) {
+      if (steps[t] == 0) continue;
+      idx[nt] = t;
+      a0[nt] = ACC + 2 * nt * pe;
+      a1[nt] = ACC + (2 * nt + 1) * pe;
+      ka[nt] = (const char*)keys_a->data + t * pl.beta * n * wb;
+      kb[nt] = (const char*)keys_b->data + t * pl.beta * n * wb;
+      ++nt;
+    }
+    if (nt == 0) break;
+    LAUNCH_ON(tc, k.s, rnt::K_HOIST_MAC, rnt::launch_hoist_mac(km, a0, a1, nt, D, ka, kb, limb_stride(keys_a)),
+              "hoisted hybrid key products");
+    for (uint32_t u = 0; u < nt; ++u) {
+      if (int rc = inv_raw(k, a0[u], cls, tc)) return rc;
+      if (int rc = inv_raw(k, a1[u], cls, tc)) return rc;
+      if (int rc = finish(idx[u], (char*)a0[u], (char*)a1[u])) return rc;
+    }
+  }
+  return RNT_OK;
+}
+
+}  // namespace
+
+extern "C" int rnt_ct_rotate_hybrid_hoisted(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                            const int32_t* steps, size_t n_steps, const rnt_buf* keys_a,
+                                            const rnt_buf* keys_b, size_t alpha) {
+  const char* name = "rnt_ct_rotate_hybrid_hoisted";
+  const rnt_buf* all[4] = {out0, out1, c0, c1};
+  for (const rnt_buf* b : all)
+    if (int rc = check_buf(b, name)) return rc;
+  if (n_steps == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: no steps", name);
+  if (!steps) return fail(RNT_ERR_BAD_ARGUMENT, "%s: null steps", name);
+  if (alpha == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: alpha must be at least 1", name);
+  if (int rc = check_same(c0, c1, name)) return rc;
+  if (out0->ctx != c0->ctx || out1->ctx != c0->ctx)
+    return fail(RNT_ERR_BASIS_MISMATCH, "%s: operands belong to different bases", name);
+  const size_t B = c0->n_polys;
+  if (n_steps > SIZE_MAX / std::max<size_t>(B, 1) || out0->n_polys != n_steps * B || out1->n_polys != n_steps * B)
+    return fail(RNT_ERR_BAD_ARGUMENT, "%s: outputs of %zu and %zu polys for %zu steps of %zu", name, out0->n_polys,
+                out1->n_polys, n_steps, B);
+  HybridPlan pl;
+  bool have = false;
+  if (int rc = hybrid_set_check(name, c0->ctx, steps, n_steps, keys_a, keys_b, alpha, &pl, &have)) return rc;
+  if (c0->in_ntt || c1->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the ciphertext must be in coefficient domain", name);
+  if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
+  for (const rnt_buf* in : {c0, c1, keys_a, keys_b})
+    if (in && (out0 == in || out1 == in || out0->data == in->data || out1->data == in->data))
+      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output aliases an input", name);
+  size_t nz = 0;
+  for (size_t t = 0; t < n_steps; ++t) nz += steps[t] != 0;
+  if (int rc = set_device(c0->ctx)) return rc;
+  if (nz)
+    if (int rc = hybrid_prepare(&pl)) return rc;
+  rnt::Launch k = launch_for(c0);
+  const size_t n = k.t->n, wb = word_bytes(k.t), Lv = k.L;
+  const uint64_t full_ls = limb_stride(c0), out_ls = limb_stride(out0), two_n = 2 * (uint64_t)n;
+  const rnt_buf* src[2] = {c0, c1};
+  rnt_buf* out[2] = {out0, out1};
+  // per ciphertext of a chunk: D (LE beta planes), the accumulator pairs of one
+  // k_hoist_mac group (2 tg LE) and, without k_moddown_auto, the tail's two
+  // staging blocks (2 Lv), within the key-switch workspace cap
+  const size_t tg = std::min<size_t>(nz, rnt::kHoistT);
+  size_t bc = nz ? hybrid_chunk(pl, B, 2 * (tg - 1) * pl.LE) : B;
+  const bool fused = tail_fused(k.t, Lv, bc);
+  const size_t tmp_planes = fused ? 0 : 2 * Lv;
+  if (nz && !fused) bc = hybrid_chunk(pl, B, 2 * (tg - 1) * pl.LE + tmp_planes);
+  const size_t pe = pl.LE * bc * n * wb;
+  CallWs ws(out0);
+  if (nz)
+    if (int rc = ws.get(pl.beta * pe + 2 * tg * pe + tmp_planes * bc * n * wb)) return rc;
+  char* D = (char*)ws.p;
+  char* ACC = D + pl.beta * pe;
+  char* TMP = ACC + 2 * tg * pe;
+  for (size_t t = 0; t < n_steps; ++t) {
+    if (steps[t] != 0) continue;
+    for (int o = 0; o < 2; ++o)
+      LAUNCH(k.t, rnt::K_COPY,
+             rnt::launch_copy_rows(k.s, (char*)out[o]->data + t * B * n * wb, out_ls * wb, src[o]->data,
+                                   full_ls * wb, full_ls * wb, Lv),
+             "step-0 copy");
+  }
+  for (size_t p0 = 0; nz && p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    const char* x0 = (const char*)c0->data + p0 * n * wb;
+    auto finish = [&](size_t t, char* A0, char* A1) -> int {
+      const uint64_t g = rotation_exponent(steps[t], two_n);
+      const size_t off = (t * B + p0) * n * wb;
+      if (int rc = hybrid_tail(pl, c, (char*)out0->data + off, out_ls, A0, x0, full_ls, g, TMP, fused)) return rc;
+      return hybrid_tail(pl, c, (char*)out1->data + off, out_ls, A1, nullptr, 0, g, TMP, fused);
+    };
+    if (int rc = hybrid_hoist_chunk(pl, c, D, ACC, (const char*)c1->data + p0 * n * wb, full_ls, steps, n_steps,
+                                    keys_a, keys_b, finish))
+      return rc;
+  }
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
+extern "C" int rnt_ct_linear_bsgs_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                         const int32_t* baby_steps, size_t n_baby, const int32_t* giant_steps,
+                                         size_t n_giant, const rnt_buf* diag, const rnt_buf* baby_keys_a,
+                                         const rnt_buf* baby_keys_b, const rnt_buf* giant_keys_a,
+                                         const rnt_buf* giant_keys_b, size_t alpha) {
+  const char* name = "rnt_ct_linear_bsgs_hybrid";
+  const rnt_buf* all[4] = {out0, out1, c0, c1};
+  for (const rnt_buf* b : all)
+    if (int rc = check_buf(b, name)) return rc;
+  if (int rc = check_buf(diag, name)) return rc;
+  if (n_baby == 0 || n_giant == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: no steps", name);
+  if (!baby_steps || !giant_steps) return fail(RNT_ERR_BAD_ARGUMENT, "%s: null steps", name);
+  if (alpha == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: alpha must be at least 1", name);
+  for (int i = 1; i < 4; ++i)
+    if (int rc = check_same(all[0], all[i], name)) return rc;
+  if (diag->ctx != c0->ctx) return fail(RNT_ERR_BASIS_MISMATCH, "%s: the plaintexts belong to a different basis", name);
+  if (n_baby > SIZE_MAX / n_giant || diag->n_polys != n_baby * n_giant)
+    return fail(RNT_ERR_BAD_ARGUMENT, "%s: %zu plaintexts for %zu x %zu steps", name, diag->n_polys, n_giant, n_baby);
+  HybridPlan plb, plg;
+  bool have_b = false, have_g = false;
+  if (int rc = hybrid_set_check(name, c0->ctx, baby_steps, n_baby, baby_keys_a, baby_keys_b, alpha, &plb, &have_b))
+    return rc;
+  if (int rc = hybrid_set_check(name, c0->ctx, giant_steps, n_giant, giant_keys_a, giant_keys_b, alpha, &plg, &have_g))
+    return rc;
+  if (have_b && have_g && plb.E != plg.E)
+    return fail(RNT_ERR_BASIS_MISMATCH, "%s: the baby and giant keys belong to different key bases", name);
+  if (!diag->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the plaintexts must be in the NTT domain", name);
+  if (c0->in_ntt || c1->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the ciphertext must be in coefficient domain", name);
+  const rnt_buf* ins[7] = {c0, c1, diag, baby_keys_a, baby_keys_b, giant_keys_a, giant_keys_b};
+  if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
+  for (int i = 0; i < 7; ++i) {
+    if ((out0 == ins[i] && i != 0) || (out1 == ins[i] && i != 1))
+      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output aliases an input other than its own component", name);
+  }
+  BsgsPlan plan;
+  try {
+    plan = bsgs_plan(giant_steps, n_giant);
+  } catch (...) {
+    return fail(RNT_ERR_OUT_OF_MEMORY, "host allocation failed");
+  }
+  size_t nzb = 0;
+  for (size_t i = 0; i < n_baby; ++i) nzb += baby_steps[i] != 0;
+  const bool hyb = nzb != 0 || plan.any_rot;
+  HybridPlan pl = have_b ? plb : plg;
+  if (int rc = set_device(c0->ctx)) return rc;
+  if (hyb)
+    if (int rc = hybrid_prepare(&pl)) return rc;
+  rnt::Launch k = launch_for(c0);
+  const size_t Lv = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
+  const size_t n_terms = n_baby * n_giant;
+  const uint64_t full_ls = limb_stride(c0), two_n = 2 * (uint64_t)n;
+  // chunk planes per ciphertext over C: the baby blocks RB (2 n_baby Lv), the
+  // inner sums VB (2 nv Lv), SIG1 | SIG0 | S0 (3 Lv) and, without
+  // k_moddown_auto, the tail's staging (2 Lv); over E: D (LE beta) and the
+  // accumulator pairs -- the baby stage's k_hoist_mac group, then the giant
+  // stage's one A0 / A1 in the same place
+  const size_t tg = std::max<size_t>(std::min<size_t>(nzb, rnt::kHoistT), 1);
+  size_t c_planes = (2 * n_baby + 2 * plan.nv + 3) * Lv;
+  size_t bc = B;
+  bool fused = true;
+  size_t tmp_planes = 0;
+  if (hyb) {
+    bc = hybrid_chunk(pl, B, 2 * (tg - 1) * pl.LE + c_planes);
+    fused = tail_fused(k.t, Lv, bc);
+    if (!fused) {
+      tmp_planes = 2 * Lv;
+      c_planes += tmp_planes;
+      bc = hybrid_chunk(pl, B, 2 * (tg - 1) * pl.LE + c_planes);
+    }
+  } else {
+    bc = std::min(B, std::max<size_t>(k.t->ks_ws_bytes / (c_planes * n * wb), 1));
+  }
+  const size_t pw = Lv * bc * n * wb;
+  const size_t pe = hyb ? pl.LE * bc * n * wb : 0;
+  const size_t dm_bytes = Lv * n_terms * n * wb;
+  CallWs ws(out0);
+  if (int rc = ws.get(dm_bytes + c_planes * bc * n * wb + (hyb ? pl.beta * pe + 2 * tg * pe : 0))) return rc;
+  // the plaintexts in Montgomery form (m^ 2^w mod q), once per call: the inner
+  // sums' Montgomery products are then the canonical products
+  char* dm = (char*)ws.p;
+  rnt::Launch kdm = k;
+  kdm.B = n_terms;
+  LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kdm, 1, dm, diag->data, nullptr, 0, false),
+         "plaintexts to Montgomery form");
+  char* RB = dm + dm_bytes;
+  char* VB = RB + 2 * n_baby * pw;
+  char* SIG1 = VB + 2 * plan.nv * pw;
+  char* SIG0 = SIG1 + pw;
+  char* S0X = SIG0 + pw;
+  char* TMP = S0X + pw;
+  char* D = TMP + tmp_planes * bc * n * wb;
+  char* ACC = D + (hyb ? pl.beta * pe : 0);
+  rnt_buf* out[2] = {out0, out1};
+  for (size_t p0 = 0; p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    rnt::Launch kc = k;
+    kc.B = c;
+    const uint64_t cls = (uint64_t)c * n;
+    const char* x[2] = {(const char*)c0->data + p0 * n * wb, (const char*)c1->data + p0 * n * wb};
+    // baby stage: R_i into RB (block 2 i + component, chunk pitch), NTT domain
+    for (size_t i = 0; i < n_baby; ++i) {
+      if (baby_steps[i] != 0) continue;
+      for (int o = 0; o < 2; ++o) {
+        char* R = RB + (2 * i + o) * pw;
+        if (int rc = copy_rows(kc, R, cls, x[o], full_ls, cls, Lv)) return rc;
+        if (int rc = fwd_raw(kc, R, cls)) return rc;
+      }
+    }
+    if (nzb) {
+      auto finish = [&](size_t i, char* A0, char* A1) -> int {
+        const uint64_t g = rotation_exponent(baby_steps[i], two_n);
+        char* R0 = RB + 2 * i * pw;
+        if (int rc = hybrid_tail(pl, c, R0, cls, A0, x[0], full_ls, g, TMP, fused)) return rc;
+        if (int rc = hybrid_tail(pl, c, R0 + pw, cls, A1, nullptr, 0, g, TMP, fused)) return rc;
+        if (int rc = fwd_raw(kc, R0, cls)) return rc;
+        return fwd_raw(kc, R0 + pw, cls);
+      };
+      if (int rc = hybrid_hoist_chunk(pl, c, D, ACC, x[1], full_ls, baby_steps, n_baby, baby_keys_a, baby_keys_b,
+                                      finish))
+        return rc;
+    }
+    // inner sums, back to coefficients
+    if (int rc = bsgs_inner_sums(kc, plan, VB, RB, pw, dm, n_baby, n_giant)) return rc;
+    for (size_t v = 0; v < 2 * plan.nv; ++v)
+      if (int rc = inv_raw(kc, VB + v * pw, cls)) return rc;
+    // giant stage: sigma(V1_j) -> ModUp -> forward -> products summed into ONE
+    // A0, A1 over E; sigma(V0_j) summed over C into S0, ModDown's addend
+    char* S0 = plan.any_zero ? VB + 2 * plan.zslot * pw : S0X;
+    char* A0 = ACC;
+    char* A1 = ACC + pe;
+    bool first = true;
+    for (size_t j = 0; j < n_giant; ++j) {
+      if (giant_steps[j] == 0) continue;
+      const char* V0 = VB + 2 * plan.slot[j] * pw;
+      const uint64_t g = rotation_exponent(giant_steps[j], two_n);
+      LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG1, V0 + pw, g), "automorphism");
+      if (first && !plan.any_zero) {
+        LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, S0, V0, g), "automorphism");
+      } else {
+        LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG0, V0, g), "automorphism");
+        LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_elementwise(kc, 0, S0, S0, SIG0), "add_assign");
+      }
+      const rnt::Launch ke = hybrid_launch(pl, c);
+      LAUNCH_ON(kc.t, ke.s, rnt::K_MODUP, rnt::launch_modup(ke, D, SIG1, cls, pl.hc), "ModUp");
+      rnt::Launch kd = ke;
+      kd.B = pl.beta * c;
+      if (int rc = fwd_raw(kd, D, (uint64_t)kd.B * n, kc.t)) return rc;
+      rnt::Launch km = ke;
+      km.Ls = pl.beta;
+      void* a0[1] = {A0};
+      void* a1[1] = {A1};
+      const void* ka[1] = {(const char*)giant_keys_a->data + j * pl.beta * n * wb};
+      const void* kb[1] = {(const char*)giant_keys_b->data + j * pl.beta * n * wb};
+      if (first) {
+        LAUNCH_ON(kc.t, ke.s, rnt::K_HOIST_MAC,
+                  rnt::launch_hoist_mac(km, a0, a1, 1, D, ka, kb, limb_stride(giant_keys_a)), "giant key products");
+      } else {
+        LAUNCH_ON(kc.t, ke.s, rnt::K_HOIST_MAC,
+                  rnt::launch_hoist_mac_acc(km, a0, a1, 1, D, ka, kb, limb_stride(giant_keys_a)),
+                  "giant key products (accumulating)");
+      }
+      first = false;
+    }
+    char* dst[2] = {(char*)out[0]->data + p0 * n * wb, (char*)out[1]->data + p0 * n * wb};
+    if (!plan.any_rot) {
+      for (int o = 0; o < 2; ++o)
+        if (int rc = copy_rows(kc, dst[o], full_ls, VB + (2 * plan.zslot + o) * pw, cls, cls, Lv)) return rc;
+    } else {
+      const rnt::Launch ke = hybrid_launch(pl, c);
+      if (int rc = inv_raw(ke, A0, cls, kc.t)) return rc;
+      if (int rc = inv_raw(ke, A1, cls, kc.t)) return rc;
+      const char* Z1 = plan.any_zero ? VB + (2 * plan.zslot + 1) * pw : nullptr;
+      LAUNCH_ON(kc.t, ke.s, rnt::K_MODDOWN, rnt::launch_moddown(ke, dst[0], full_ls, A0, cls, S0, cls, pl.hc),
+                "ModDown");
+      LAUNCH_ON(kc.t, ke.s, rnt::K_MODDOWN, rnt::launch_moddown(ke, dst[1], full_ls, A1, cls, Z1, cls, pl.hc),
+                "ModDown");
+    }
+  }
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
 }
 
 extern "C" int rnt_copy_polys(rnt_buf* dst, size_t dst_first, const rnt_buf* src, size_t src_first,

@@ -111,6 +111,9 @@ struct Tables {
                            // RNT_PLANE=0: the four-step kernels everywhere
   uint32_t dec_jg = 0;     // key-switch decomposition: target limbs per workgroup (0 = auto)
   size_t ks_ws_bytes = (size_t)4096 << 20;  // key-switch scratch cap per chunk (RNT_KS_WS_MB)
+  int md_auto = 1;         // the tail of a hoisted hybrid rotation (RNT_MODDOWN_AUTO): 1 k_moddown_auto where
+                           // a chunk's component is below kMdAutoBytes, else k_moddown, the automorphism
+                           // launch and a strided copy; 0 never k_moddown_auto, 2 always (A/B, tests)
   uint32_t log_n = 0;
   size_t n = 0;
   size_t L = 0;            // channel count of the root basis
@@ -148,7 +151,8 @@ enum KernelId {
   K_COL_FWD, K_ROW_FWD, K_ROW_INV, K_ROW_MUL, K_COL_INV, K_ELEMENTWISE, K_RESCALE,
   K_AUTOMORPHISM, K_KS_DECOMPOSE, K_KS_ROWS, K_TENSOR_ROWS, K_IMPORT, K_EXPORT, K_CRT,
   K_SFFT, K_SAMPLE, K_COPY, K_PLANE_FUSED, K_MF_NTT_FWD, K_MF_NTT_INV, K_WHOLE_FWD, K_WHOLE_INV, K_WHOLE_MUL,
-  K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_MODUP, K_MODDOWN, K_COUNT
+  K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_MODUP, K_MODDOWN,
+  K_MODDOWN_AUTO, K_COUNT
 };
 
 struct Prof {
@@ -376,6 +380,10 @@ constexpr uint32_t kHoistT = 4;
 hipError_t launch_hoist_digits(const Launch& k, void* D, const void* c1, uint64_t src_ls);
 hipError_t launch_hoist_mac(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt, const void* d,
                             const void* const* key_a, const void* const* key_b, uint64_t key_ls);
+// The same sums ADDED to what acc0[t] / acc1[t] hold (k_hoist_mac_acc): the
+// giant stage of rnt_ct_linear_bsgs_hybrid, one A0 / A1 over several launches.
+hipError_t launch_hoist_mac_acc(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt, const void* d,
+                                const void* const* key_a, const void* const* key_b, uint64_t key_ls);
 // Hybrid key-switching (rnt_keyswitch_hybrid).  k.t is the KEY basis' tables,
 // k.L = Lv + K its limbs, k.B the chunk's polys.  launch_modup (k_modup): the
 // Montgomery-form raised digits D[t][d][p] = ModUp_d(x) 2^w mod m_t for t < k.L,
@@ -387,6 +395,11 @@ hipError_t launch_hoist_mac(const Launch& k, void* const* acc0, void* const* acc
 hipError_t launch_modup(const Launch& k, void* D, const void* x, uint64_t src_ls, const HybridConsts& hc);
 hipError_t launch_moddown(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
                           const void* add, uint64_t add_ls, const HybridConsts& hc);
+// launch_moddown_auto (k_moddown_auto): sigma_g of launch_moddown's result (g
+// odd, below 2N), scattered at the output's limb stride; out overlaps neither
+// A nor the addend.
+hipError_t launch_moddown_auto(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
+                               const void* add, uint64_t add_ls, uint64_t g, const HybridConsts& hc);
 // out[l][i] = 2^w mod q_l over [k.L][N]: the Montgomery-form plaintext 1.
 hipError_t launch_mont_one(const Launch& k, void* out);
 // The whole-plane key-switch at 2^10 <= N <= 2^13 (k_ks_whole, one launch,

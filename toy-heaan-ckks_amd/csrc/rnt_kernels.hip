@@ -1990,6 +1990,87 @@ k_hoist_mac(HoistArgs<W> a, const W* __restrict__ d, TabPtrs<W> tp, uint32_t log
   }
 }
 
+// k_hoist_mac with the sums ADDED to what acc0[t] / acc1[t] hold (canonical):
+// the giant stage of rnt_ct_linear_bsgs_hybrid, whose one A0, A1 are summed over
+// several launches.  A kernel of its own, so that k_hoist_mac stays as it is.
+template <class W, bool VEC>
+__global__ void __launch_bounds__(256)
+k_hoist_mac_acc(HoistArgs<W> a, const W* __restrict__ d, TabPtrs<W> tp, uint32_t log_n, uint64_t limb_words,
+                uint64_t key_ls, uint32_t Ls, uint32_t nt) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint32_t j = blockIdx.y;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= limb_words) return;
+  const LimbConst<W> lc = tp.lc[j];
+  const uint64_t N = 1ull << log_n;
+  const W* dp = d + (uint64_t)j * Ls * limb_words + i;
+  const uint64_t ko = (uint64_t)j * key_ls + (i & (N - 1));  // V divides N: one plane
+  const uint64_t g = (uint64_t)j * limb_words + i;
+  W acc0[HOIST_T][V], acc1[HOIST_T][V];
+#pragma unroll
+  for (int t = 0; t < HOIST_T; ++t) {
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc0[t][v] = acc1[t][v] = (W)0;
+    if ((uint32_t)t < nt) {  // (uniform)
+      if constexpr (VEC) {
+        const uint4 r0 = *reinterpret_cast<const uint4*>(a.acc0[t] + g);
+        const uint4 r1 = *reinterpret_cast<const uint4*>(a.acc1[t] + g);
+        __builtin_memcpy(acc0[t], &r0, 16);
+        __builtin_memcpy(acc1[t], &r1, 16);
+      } else {
+        acc0[t][0] = a.acc0[t][g];
+        acc1[t][0] = a.acc1[t][g];
+      }
+    }
+  }
+  for (uint32_t s = 0; s < Ls; ++s) {
+    W xv[V];
+    if constexpr (VEC) {
+      const uint4 xa = *reinterpret_cast<const uint4*>(dp + (uint64_t)s * limb_words);
+      __builtin_memcpy(xv, &xa, 16);
+    } else {
+      xv[0] = dp[(uint64_t)s * limb_words];
+    }
+#pragma unroll
+    for (int t = 0; t < HOIST_T; ++t) {
+      if ((uint32_t)t < nt) {  // (uniform)
+        const W* bq = a.key_b[t] + ko + (uint64_t)s * N;
+        const W* aq = a.key_a[t] + ko + (uint64_t)s * N;
+        W bv[V], av[V];
+        if constexpr (VEC) {
+          const uint4 b4 = *reinterpret_cast<const uint4*>(bq);
+          const uint4 a4 = *reinterpret_cast<const uint4*>(aq);
+          __builtin_memcpy(bv, &b4, 16);
+          __builtin_memcpy(av, &a4, 16);
+        } else {
+          bv[0] = bq[0];
+          av[0] = aq[0];
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          acc0[t][v] = add_mod<W>(acc0[t][v], mont_mul<W>(xv[v], bv[v], lc.q, lc.qinv), lc.q);
+          acc1[t][v] = add_mod<W>(acc1[t][v], mont_mul<W>(xv[v], av[v], lc.q, lc.qinv), lc.q);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < HOIST_T; ++t) {
+    if ((uint32_t)t < nt) {
+      if constexpr (VEC) {
+        uint4 r0, r1;
+        __builtin_memcpy(&r0, acc0[t], 16);
+        __builtin_memcpy(&r1, acc1[t], 16);
+        *reinterpret_cast<uint4*>(a.acc0[t] + g) = r0;
+        *reinterpret_cast<uint4*>(a.acc1[t] + g) = r1;
+      } else {
+        a.acc0[t][g] = acc0[t][0];
+        a.acc1[t][g] = acc1[t][0];
+      }
+    }
+  }
+}
+
 // 16-byte (VEC) or one-word access of V words at p.
 template <class W, bool VEC, int V>
 __device__ __forceinline__ void ld_vec(W (&o)[V], const W* p) {
@@ -2152,6 +2233,100 @@ k_moddown(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A, uint64_
       for (int v = 0; v < V; ++v) r[v] = add_mod<W>(r[v], dv[v], q);
     }
     st_vec<W, VEC, V>(out + (uint64_t)j * out_ls + i, r);
+  }
+}
+
+__device__ __forceinline__ uint64_t xcd_gid();
+
+// k_moddown followed by sigma_g of the result (g odd), written at the output's
+// own limb stride: the per-step tail of the hoisted hybrid rotation, out =
+// sigma_g(ModDown(A) (+ add)).  Position i of a plane lands at t mod N with
+// t = i g mod 2N, negated mod q_j when t >= N (zero stays zero).  A SCATTER:
+// the K special planes, A_j and the addend stay 16-byte vector streams and only
+// the Lv result planes are written a word at a time.  A gather would read the
+// K + Lv (+ Lv addend) input planes a word at a time -- (K + 2 Lv) / Lv times
+// the element-granular instructions, the K special ones again for every run of
+// a split grid -- and put their latency in front of the arithmetic, where a
+// store retires behind it.  g is odd, so i -> i g mod 2N is a bijection of the
+// positions: every output word is written exactly once, no ordering needed.
+// xcd_gid()'s deal gives every XCD whole polys, so the partial lines of a
+// result plane (N words, at most 1 MiB) meet in ONE L2 before they leave it.
+// The output must not overlap A or the addend.
+template <class W, bool VEC, int KMAX>
+__global__ void __launch_bounds__(256)
+k_moddown_auto(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A, uint64_t a_ls,
+               const W* __restrict__ add, uint64_t add_ls, TabPtrs<W> tp, const W* __restrict__ pinv,
+               const W* __restrict__ pinvp, const W* __restrict__ pq, const W* __restrict__ pqp,
+               const W* __restrict__ Pinv, const W* __restrict__ Pinvp, uint64_t limb_words, uint32_t log_n,
+               uint32_t g, uint32_t Lv, uint32_t K, uint32_t jper) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint64_t i = xcd_gid() * V;
+  if (i >= limb_words) return;
+  const uint32_t j0 = blockIdx.y * jper;
+  const uint32_t j1 = j0 + jper < Lv ? j0 + jper : Lv;
+  const uint32_t N = 1u << log_n;
+  const uint32_t pos = (uint32_t)i & (N - 1);  // V divides N: one plane
+  uint64_t dst[V];
+  bool neg[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const uint32_t t = ((pos + (uint32_t)v) * g) & (2 * N - 1);  // (mod 2^32 first: 2N divides it)
+    neg[v] = t >= N;
+    dst[v] = (i - pos) + (t & (N - 1));
+  }
+  const W* sp = A + (uint64_t)Lv * a_ls + i;
+  W z[KMAX > 0 ? KMAX : 1][V];
+  if constexpr (KMAX > 0) {
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      if ((uint32_t)k < K) {  // (uniform)
+        W av[V];
+        ld_vec<W, VEC, V>(av, sp + (uint64_t)k * a_ls);
+        const W p = tp.lc[Lv + k].q, c = pinv[k], cp = pinvp[k];
+#pragma unroll
+        for (int v = 0; v < V; ++v) z[k][v] = shoup_mul<W>(av[v], c, cp, p);
+      }
+    }
+  }
+  for (uint32_t j = j0; j < j1; ++j) {
+    const W q = tp.lc[j].q;
+    W cv[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) cv[v] = (W)0;
+    if constexpr (KMAX > 0) {
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+        if ((uint32_t)k < K) {
+          const W c = pq[(uint64_t)k * Lv + j], cp = pqp[(uint64_t)k * Lv + j];
+#pragma unroll
+          for (int v = 0; v < V; ++v) cv[v] = add_mod<W>(cv[v], shoup_mul<W>(z[k][v], c, cp, q), q);
+        }
+      }
+    } else {
+      for (uint32_t k = 0; k < K; ++k) {
+        W av[V];
+        ld_vec<W, VEC, V>(av, sp + (uint64_t)k * a_ls);
+        const W p = tp.lc[Lv + k].q, ci = pinv[k], cip = pinvp[k];
+        const W c = pq[(uint64_t)k * Lv + j], cp = pqp[(uint64_t)k * Lv + j];
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+          cv[v] = add_mod<W>(cv[v], shoup_mul<W>(shoup_mul<W>(av[v], ci, cip, p), c, cp, q), q);
+      }
+    }
+    W av[V], r[V];
+    ld_vec<W, VEC, V>(av, A + (uint64_t)j * a_ls + i);
+    const W c = Pinv[j], cp = Pinvp[j];
+#pragma unroll
+    for (int v = 0; v < V; ++v) r[v] = shoup_mul<W>(av[v] - cv[v] + q, c, cp, q);  // a - conv + q in (0, 2q)
+    if (add != nullptr) {  // (uniform)
+      W dv[V];
+      ld_vec<W, VEC, V>(dv, add + (uint64_t)j * add_ls + i);
+#pragma unroll
+      for (int v = 0; v < V; ++v) r[v] = add_mod<W>(r[v], dv[v], q);
+    }
+    W* op = out + (uint64_t)j * out_ls;
+#pragma unroll
+    for (int v = 0; v < V; ++v) op[dst[v]] = neg[v] && r[v] != 0 ? (W)(q - r[v]) : r[v];
   }
 }
 
@@ -2652,7 +2827,7 @@ static hipError_t hoist_digits_t(const Launch& k, void* D, const void* c1, uint6
 template <class W>
 static hipError_t hoist_mac_t(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt,
                               const void* d, const void* const* key_a, const void* const* key_b,
-                              uint64_t key_ls) {
+                              uint64_t key_ls, bool accum) {
   const uint64_t N = 1ull << k.t->log_n;
   const uint64_t limb_words = (uint64_t)k.B * N;
   const size_t Ls = k.src_limbs();
@@ -2674,10 +2849,14 @@ static hipError_t hoist_mac_t(const Launch& k, void* const* acc0, void* const* a
   const uint64_t bx = (per + 255) / 256;
   if (bx > 0x7fffffffull || k.L > 65535) return hipErrorInvalidConfiguration;
   const dim3 grid((unsigned)bx, (unsigned)k.L);
-#define RNT_HM(VEC)                                                                              \
-  hipLaunchKernelGGL((k_hoist_mac<W, VEC>), grid, dim3(256), 0, k.s, a, (const W*)d,             \
+#define RNT_HM(KERNEL, VEC)                                                                      \
+  hipLaunchKernelGGL((KERNEL<W, VEC>), grid, dim3(256), 0, k.s, a, (const W*)d,                  \
                      tab_ptrs<W>(k.t), k.t->log_n, limb_words, key_ls, (uint32_t)Ls, nt)
-  if (vec) RNT_HM(true); else RNT_HM(false);
+  if (accum) {
+    if (vec) RNT_HM(k_hoist_mac_acc, true); else RNT_HM(k_hoist_mac_acc, false);
+  } else {
+    if (vec) RNT_HM(k_hoist_mac, true); else RNT_HM(k_hoist_mac, false);
+  }
 #undef RNT_HM
   return hipGetLastError();
 }
@@ -2748,6 +2927,42 @@ static hipError_t moddown_t(const Launch& k, void* out, uint64_t out_ls, const v
   else RNT_MD_K(0);
 #undef RNT_MD_K
 #undef RNT_MD
+  return hipGetLastError();
+}
+
+// g odd, below 2N.  The stores are single words: only A and the addend decide
+// the 16-byte form.  Grid x a multiple of 8 (xcd_gid()).
+template <class W>
+static hipError_t moddown_auto_t(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
+                                 const void* add, uint64_t add_ls, uint64_t g, const HybridConsts& hc) {
+  const uint64_t N = 1ull << k.t->log_n;
+  const uint64_t limb_words = (uint64_t)k.B * N;
+  if (hc.Lv == 0 || hc.K == 0 || k.L != (size_t)hc.Lv + hc.K || k.L > k.t->L || out_ls < limb_words ||
+      a_ls < limb_words || (add && add_ls < limb_words) || (g & 1) == 0 || g >= 2 * N)
+    return hipErrorInvalidValue;
+  if (limb_words == 0) return hipSuccess;
+  constexpr int V = 16 / (int)sizeof(W);
+  const bool vec = N % V == 0 && a_ls % V == 0 && (!add || add_ls % V == 0) &&
+                   ((uintptr_t)A | (uintptr_t)add) % 16 == 0 && (uintptr_t)out % sizeof(W) == 0;
+  const uint64_t per = vec ? limb_words / V : limb_words;
+  const uint64_t bx = ((per + 255) / 256 + 7) & ~7ull;
+  if (bx > 0x7fffffffull) return hipErrorInvalidConfiguration;
+  const uint64_t runs = std::min<uint64_t>(hc.Lv, std::max<uint64_t>(kSplitBlocks / bx, 1));
+  const uint32_t jper = (uint32_t)((hc.Lv + runs - 1) / runs);
+  const dim3 grid((unsigned)bx, (unsigned)((hc.Lv + jper - 1) / jper));
+#define RNT_MA(VEC, KMAX)                                                                               \
+  hipLaunchKernelGGL((k_moddown_auto<W, VEC, KMAX>), grid, dim3(256), 0, k.s, (W*)out, out_ls,           \
+                     (const W*)A, a_ls, (const W*)add, add_ls, tab_ptrs<W>(k.t), (const W*)hc.pinv,      \
+                     (const W*)hc.pinvp, (const W*)hc.pq, (const W*)hc.pqp, (const W*)hc.Pinv,           \
+                     (const W*)hc.Pinvp, limb_words, k.t->log_n, (uint32_t)g, hc.Lv, hc.K, jper)
+#define RNT_MA_K(KMAX) do { if (vec) RNT_MA(true, KMAX); else RNT_MA(false, KMAX); } while (0)
+  // (no 16-limb tier: with the destination offsets beside 16 z_k it spills
+  // scalar registers; more than 8 special primes take the recomputing form)
+  if (hc.K <= 4) RNT_MA_K(4);
+  else if (hc.K <= 8) RNT_MA_K(8);
+  else RNT_MA_K(0);
+#undef RNT_MA_K
+#undef RNT_MA
   return hipGetLastError();
 }
 
@@ -3354,8 +3569,13 @@ hipError_t launch_hoist_digits(const Launch& k, void* D, const void* c1, uint64_
 }
 hipError_t launch_hoist_mac(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt, const void* d,
                             const void* const* key_a, const void* const* key_b, uint64_t key_ls) {
-  RNT_WIDE(hoist_mac_t<uint32_t>(k, acc0, acc1, nt, d, key_a, key_b, key_ls),
-           hoist_mac_t<uint64_t>(k, acc0, acc1, nt, d, key_a, key_b, key_ls));
+  RNT_WIDE(hoist_mac_t<uint32_t>(k, acc0, acc1, nt, d, key_a, key_b, key_ls, false),
+           hoist_mac_t<uint64_t>(k, acc0, acc1, nt, d, key_a, key_b, key_ls, false));
+}
+hipError_t launch_hoist_mac_acc(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt, const void* d,
+                                const void* const* key_a, const void* const* key_b, uint64_t key_ls) {
+  RNT_WIDE(hoist_mac_t<uint32_t>(k, acc0, acc1, nt, d, key_a, key_b, key_ls, true),
+           hoist_mac_t<uint64_t>(k, acc0, acc1, nt, d, key_a, key_b, key_ls, true));
 }
 hipError_t launch_modup(const Launch& k, void* D, const void* x, uint64_t src_ls, const HybridConsts& hc) {
   RNT_WIDE(modup_t<uint32_t>(k, D, x, src_ls, hc), modup_t<uint64_t>(k, D, x, src_ls, hc));
@@ -3364,6 +3584,11 @@ hipError_t launch_moddown(const Launch& k, void* out, uint64_t out_ls, const voi
                           const void* add, uint64_t add_ls, const HybridConsts& hc) {
   RNT_WIDE(moddown_t<uint32_t>(k, out, out_ls, A, a_ls, add, add_ls, hc),
            moddown_t<uint64_t>(k, out, out_ls, A, a_ls, add, add_ls, hc));
+}
+hipError_t launch_moddown_auto(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
+                               const void* add, uint64_t add_ls, uint64_t g, const HybridConsts& hc) {
+  RNT_WIDE(moddown_auto_t<uint32_t>(k, out, out_ls, A, a_ls, add, add_ls, g, hc),
+           moddown_auto_t<uint64_t>(k, out, out_ls, A, a_ls, add, add_ls, g, hc));
 }
 hipError_t launch_mont_one(const Launch& k, void* out) {
   RNT_WIDE(mont_one_t<uint32_t>(k, out), mont_one_t<uint64_t>(k, out));

@@ -37,6 +37,10 @@ __all__ = [
     "keyswitch_hybrid",
     "rotate_ciphertext_hybrid",
     "mul_ciphertexts_hybrid",
+    "RnsHybridKeySet",
+    "rotate_ciphertext_hybrid_hoisted",
+    "linear_transform_hybrid",
+    "linear_transform_bsgs_hybrid",
     "Ciphertext",
     "generate_primes",
     "is_ntt_friendly_prime",
@@ -670,7 +674,10 @@ class RnsHybridKey:
     ``b`` are RnsPoly batches of ``beta = ceil(L / alpha)`` polys on the
     EXTENDED basis ``q_0..q_{L-1}, p_0..p_{K-1}``, made NTT-resident here
     (rnt_key_prepare).  ``alpha`` is the digit size the key was generated
-    for and ``rotation`` the step of a rotation key."""
+    for and ``rotation`` the step of a rotation key.  ``hoisted`` says which
+    form the key is in: the ordinary prepared one, or (after
+    :meth:`prepare_hoisted`) the hoisting form of the hoisted hybrid
+    rotations."""
 
     def __init__(self, a: RnsPoly, b: RnsPoly, alpha: int, rotation: Optional[int] = None):
         if int(alpha) < 1:
@@ -681,7 +688,21 @@ class RnsHybridKey:
         self.b = b
         self.alpha = int(alpha)
         self.rotation = rotation
+        self.hoisted = False
         check(load().rnt_key_prepare(a.handle, b.handle))
+
+    def prepare_hoisted(self) -> "RnsHybridKey":
+        """Turn this rotation key into its hoisting form
+        ``NTT(sigma_k^-1(key))`` over the extended basis, k the key's
+        ``rotation`` (rnt_key_prepare_hoisted), in place.  The ordinary form
+        is gone: a caller that needs both keeps a second key."""
+        if self.rotation is None:
+            raise ValueError("prepare_hoisted: not a rotation key (no rotation step)")
+        if self.hoisted:
+            raise ValueError("prepare_hoisted: the key is in hoisting form already")
+        check(load().rnt_key_prepare_hoisted(self.a.handle, self.b.handle, int(self.rotation)))
+        self.hoisted = True
+        return self
 
     @classmethod
     def from_channels(cls, a_channels, b_channels, ext_basis: RnsBasis, alpha: int,
@@ -695,7 +716,8 @@ class RnsHybridKey:
         ``q_0..q_{L'-1}, p_0..p_{K-1}``; the result holds the first
         ``ceil(L'/alpha)`` polys on the kept limbs (the digit boundaries do not
         move).  Set-up: the polys make one host round trip, in the NTT domain
-        (a limb's transform does not depend on the others)."""
+        (a limb's transform does not depend on the others; the hoisting form
+        is computed per limb too, so the result keeps the key's form)."""
         full = self.a.basis.moduli()
         low = ext_basis_lv.moduli()
         lv = 0
@@ -716,13 +738,16 @@ class RnsHybridKey:
         for p in (self.a, self.b):
             ch = p.channels_of(0, n_polys)[:, keep, :]
             halves.append(RnsPoly.from_channels(ch, ext_basis_lv, in_ntt_domain=True))
-        return RnsHybridKey(halves[0], halves[1], self.alpha, self.rotation)
+        out = RnsHybridKey(halves[0], halves[1], self.alpha, self.rotation)
+        out.hoisted = self.hoisted
+        return out
 
 
 def keyswitch_hybrid(d: RnsPoly, key: RnsHybridKey) -> tuple[RnsPoly, RnsPoly]:
     """The hybrid key-switch sums of a coefficient-domain batch
     (rnt_keyswitch_hybrid): ``acc0 + acc1 s = d s' + small``."""
     _require_class(key, RnsHybridKey, "keyswitch_hybrid")
+    _require_form(key, False, "keyswitch_hybrid")
     acc0, acc1 = d._like(), d._like()
     check(load().rnt_keyswitch_hybrid(acc0.handle, acc1.handle, d.handle, key.a.handle, key.b.handle, key.alpha))
     return acc0, acc1
@@ -732,6 +757,7 @@ def rotate_ciphertext_hybrid(ct: Ciphertext, rotk: RnsHybridKey) -> Ciphertext:
     """rotate_ciphertext with the hybrid key-switch (rnt_ct_rotate_hybrid):
     the same rotation with less noise, not the gadget call's words."""
     _require_class(rotk, RnsHybridKey, "rotate_ciphertext_hybrid")
+    _require_form(rotk, False, "rotate_ciphertext_hybrid")
     out0, out1 = ct.c0._like(), ct.c0._like()
     check(load().rnt_ct_rotate_hybrid(out0.handle, out1.handle, ct.c0.handle, ct.c1.handle,
                                       int(rotk.rotation or 0), rotk.a.handle, rotk.b.handle, rotk.alpha))
@@ -746,6 +772,119 @@ def mul_ciphertexts_hybrid(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsHybridKey) 
     check(load().rnt_ct_mul_relin_hybrid(out0.handle, out1.handle, ct1.c0.handle, ct1.c1.handle,
                                          ct2.c0.handle, ct2.c1.handle, rlk.a.handle, rlk.b.handle, rlk.alpha))
     return Ciphertext(out0, out1, ct1.logp + ct2.logp, ct1.logq)
+
+
+class RnsHybridKeySet:
+    """The hybrid rotation keys of several steps, packed on the device as
+    rnt_ct_rotate_hybrid_hoisted and rnt_ct_linear_bsgs_hybrid read them:
+    step t's ``beta`` key polys at ``[t beta, (t + 1) beta)`` of ``a`` / ``b``
+    on the extended basis (rnt_copy_polys, no host round trip).  ``keys[t]``
+    is an :class:`RnsHybridKey` whose ``rotation`` is the step, or None for a
+    step of 0 (its slot stays zero and is never read).  The keys share one
+    extended basis, one ``alpha`` and one form (``hoisted``); a set without
+    any key serves both forms and needs ``alpha``."""
+
+    def __init__(self, keys: Sequence[Optional[RnsHybridKey]], alpha: Optional[int] = None):
+        keys = list(keys)
+        if not keys:
+            raise ValueError("RnsHybridKeySet: no steps")
+        real = [k for k in keys if k is not None]
+        for k in real:
+            if not isinstance(k, RnsHybridKey):
+                raise ValueError(f"RnsHybridKeySet: needs RnsHybridKey entries, got {type(k).__name__}")
+        if len({bool(k.hoisted) for k in real}) > 1:
+            raise ValueError("RnsHybridKeySet: a mix of hoisting-form and ordinary keys")
+        if len({k.alpha for k in real} | ({int(alpha)} if alpha is not None else set())) > 1:
+            raise ValueError("RnsHybridKeySet: the keys were generated for different alpha")
+        if not real and alpha is None:
+            raise ValueError("RnsHybridKeySet: a set of step-0 terms needs alpha")
+        self.hoisted = bool(real[0].hoisted) if real else False
+        self.alpha = real[0].alpha if real else int(alpha)
+        self.steps = [0 if k is None else int(k.rotation or 0) for k in keys]
+        self.basis = real[0].a.basis if real else None
+        self.a = self.b = None
+        if real:
+            beta = real[0].a.n_polys
+            for k in real:
+                if k.a.basis is not self.basis and k.a.basis.moduli() != self.basis.moduli():
+                    raise ValueError("RnsHybridKeySet: the keys are on different extended bases")
+                if k.a.n_polys != beta:
+                    raise ValueError("RnsHybridKeySet: the keys hold different digit counts")
+            self.a = RnsPoly(self.basis, len(keys) * beta)
+            self.b = RnsPoly(self.basis, len(keys) * beta)
+            # (zero-filled: a zero poly is zero in both domains)
+            self.a.to_ntt_domain()
+            self.b.to_ntt_domain()
+            for t, k in enumerate(keys):
+                if k is not None:
+                    self.a.copy_polys(k.a, t * beta, 0, beta)
+                    self.b.copy_polys(k.b, t * beta, 0, beta)
+
+    def __len__(self) -> int:
+        return len(self.steps)
+
+
+def _require_hybrid_set(keyset, hoisted: bool, what: str) -> None:
+    if not isinstance(keyset, RnsHybridKeySet):
+        raise ValueError(f"{what}: needs an RnsHybridKeySet, got {type(keyset).__name__}")
+    if keyset.a is not None:
+        _require_form(keyset, hoisted, what)
+
+
+def rotate_ciphertext_hybrid_hoisted(ct: Ciphertext, keyset: RnsHybridKeySet,
+                                     out: Optional[Ciphertext] = None) -> Ciphertext:
+    """The hoisted hybrid rotations of every ciphertext of the batch by each
+    of ``keyset.steps`` with one ModUp and one forward transform
+    (rnt_ct_rotate_hybrid_hoisted): a batch of ``n_steps * B``, rotation t of
+    ciphertext b at poly ``t * B + b``.  ``keyset`` is in hoisting form.
+    Valid rotations with ``rotate_ciphertext_hybrid``'s noise, not its
+    words."""
+    _require_hybrid_set(keyset, True, "rotate_ciphertext_hybrid_hoisted")
+    basis = ct.c0.basis
+    n_out = len(keyset.steps) * ct.c0.n_polys
+    if out is None:
+        out = Ciphertext(RnsPoly(basis, n_out, _uninit=True), RnsPoly(basis, n_out, _uninit=True), ct.logp, ct.logq)
+    steps = (ctypes.c_int32 * len(keyset.steps))(*keyset.steps)
+    check(load().rnt_ct_rotate_hybrid_hoisted(out.c0.handle, out.c1.handle, ct.c0.handle, ct.c1.handle, steps,
+                                              len(keyset.steps), keyset.a.handle if keyset.a is not None else None,
+                                              keyset.b.handle if keyset.b is not None else None, keyset.alpha))
+    return out
+
+
+def linear_transform_bsgs_hybrid(ct: Ciphertext, diag: RnsPoly, baby_keyset: RnsHybridKeySet,
+                                 giant_keyset: RnsHybridKeySet, out: Optional[Ciphertext] = None) -> Ciphertext:
+    """:func:`linear_transform_bsgs` on hybrid keys
+    (rnt_ct_linear_bsgs_hybrid): the baby rotations hoisted (``baby_keyset``
+    in hoisting form), the giant rotations (``giant_keyset`` ordinary) summed
+    over the extended basis and divided by P once.  ``diag`` as
+    :func:`linear_transform_bsgs` takes it; ``out`` may be ``ct``."""
+    _require_hybrid_set(baby_keyset, True, "linear_transform_bsgs_hybrid (baby keys)")
+    _require_hybrid_set(giant_keyset, False, "linear_transform_bsgs_hybrid (giant keys)")
+    if baby_keyset.alpha != giant_keyset.alpha:
+        raise ValueError("linear_transform_bsgs_hybrid: the two key sets were generated for different alpha")
+    basis = ct.c0.basis
+    if out is None:
+        out = Ciphertext(ct.c0._like(basis), ct.c0._like(basis), ct.logp, ct.logq)
+    baby = (ctypes.c_int32 * len(baby_keyset.steps))(*baby_keyset.steps)
+    giant = (ctypes.c_int32 * len(giant_keyset.steps))(*giant_keyset.steps)
+
+    def h(p):
+        return p.handle if p is not None else None
+
+    check(load().rnt_ct_linear_bsgs_hybrid(out.c0.handle, out.c1.handle, ct.c0.handle, ct.c1.handle, baby,
+                                           len(baby_keyset.steps), giant, len(giant_keyset.steps), diag.handle,
+                                           h(baby_keyset.a), h(baby_keyset.b), h(giant_keyset.a), h(giant_keyset.b),
+                                           baby_keyset.alpha))
+    return out
+
+
+def linear_transform_hybrid(ct: Ciphertext, diag: RnsPoly, keyset: RnsHybridKeySet,
+                            out: Optional[Ciphertext] = None) -> Ciphertext:
+    """``sum_t diag[t] * R_t`` over the hoisted hybrid rotations ``R_t`` of
+    ``ct`` by ``keyset.steps``: :func:`linear_transform_bsgs_hybrid` with the
+    single giant step 0."""
+    _require_hybrid_set(keyset, True, "linear_transform_hybrid")
+    return linear_transform_bsgs_hybrid(ct, diag, keyset, RnsHybridKeySet([None], keyset.alpha), out)
 
 
 class RnsGadgetKeySet:

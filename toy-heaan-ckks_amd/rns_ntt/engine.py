@@ -24,9 +24,10 @@ from typing import Optional
 import numpy as np
 
 from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsGadgetKeySet, RnsHybridKey,
-               RnsPoly, bsgs_diagonal_rows, linear_transform, linear_transform_bsgs, linear_transform_bsgs_hoisted,
+               RnsHybridKeySet, RnsPoly, bsgs_diagonal_rows, linear_transform, linear_transform_bsgs,
+               linear_transform_bsgs_hoisted, linear_transform_bsgs_hybrid, linear_transform_hybrid,
                mul_ciphertexts_gadget, mul_ciphertexts_hybrid, rescale_ciphertext, rotate_ciphertext,
-               rotate_ciphertext_hoisted, rotate_ciphertext_hybrid)
+               rotate_ciphertext_hoisted, rotate_ciphertext_hybrid, rotate_ciphertext_hybrid_hoisted)
 
 
 @dataclass
@@ -190,6 +191,45 @@ class CkksEngine:
 
     rotate_ciphertext_hybrid = staticmethod(rotate_ciphertext_hybrid)
     mul_ciphertexts_hybrid = staticmethod(mul_ciphertexts_hybrid)
+
+    def generate_hybrid_rotation_key_set(self, sk: RnsPoly, steps, rng, alpha: int,
+                                         hoisted: bool = False) -> RnsHybridKeySet:
+        """One hybrid rotation key per step, packed for the hoisted hybrid
+        calls (no key for a step of 0); with ``hoisted`` every key in its
+        hoisting form, for ``rotate_hoisted_hybrid``, ``linear_transform_hybrid``
+        and the baby keys of ``linear_transform_bsgs_hybrid``."""
+        keys = [None if int(s) == 0 else self.generate_hybrid_rotation_key(sk, int(s), rng, alpha) for s in steps]
+        if hoisted:
+            for k in keys:
+                if k is not None:
+                    k.prepare_hoisted()
+        return RnsHybridKeySet(keys, alpha)
+
+    @staticmethod
+    def rotate_hoisted_hybrid(ct: Ciphertext, keyset: RnsHybridKeySet) -> Ciphertext:
+        """Every ciphertext of the batch rotated by each of the key set's
+        steps with one ModUp: a batch of ``n_steps * B``, rotation t of
+        ciphertext b at ``t * B + b``."""
+        return rotate_ciphertext_hybrid_hoisted(ct, keyset)
+
+    @staticmethod
+    def linear_transform_hybrid(ct: Ciphertext, diag_plaintexts: Plaintext, keyset: RnsHybridKeySet) -> Ciphertext:
+        """``sum_k diag_k * rotate(ct, k)`` over the (hoisting-form) key set's
+        steps on hybrid keys; logp grows by the diagonals' scale."""
+        out = linear_transform_hybrid(ct, diag_plaintexts.poly, keyset)
+        out.logp = ct.logp + diag_plaintexts.scale_bits
+        return out
+
+    @staticmethod
+    def linear_transform_bsgs_hybrid(ct: Ciphertext, diag_plaintexts: Plaintext, baby_keyset: RnsHybridKeySet,
+                                     giant_keyset: RnsHybridKeySet) -> Ciphertext:
+        """``linear_transform_bsgs`` on hybrid keys (baby keys in hoisting
+        form, giant keys ordinary; ``encode_diagonals_bsgs`` gives the
+        plaintexts): one ModUp for all the babies, one ModDown for all the
+        giants; logp grows by the diagonals' scale."""
+        out = linear_transform_bsgs_hybrid(ct, diag_plaintexts.poly, baby_keyset, giant_keyset)
+        out.logp = ct.logp + diag_plaintexts.scale_bits
+        return out
 
     # -- encryption (engine.rs:84-127) -----------------------------------------
     def encrypt(self, plaintext, pk: PublicKey, rng, logp: int = 0,
