@@ -92,7 +92,7 @@ int rnt_device_count(int* n);
  * "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd",
  * "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
  * "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown",
- * "moddown_auto"), the launch count and summed device milliseconds since enabling. */
+ * "moddown_auto", "moddown_rescale"), the launch count and summed device milliseconds since enabling. */
 int rnt_profile_enable(const rnt_ctx* ctx, int enable);
 int rnt_profile_read(const rnt_ctx* ctx, const char* kernel, uint64_t* launches,
                      double* total_ms);
@@ -538,6 +538,45 @@ int rnt_copy_polys(rnt_buf* dst, size_t dst_first, const rnt_buf* src, size_t sr
  * dropped basis. */
 int rnt_ct_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0,
                    const rnt_buf* c1);
+/* ---- the hybrid calls that close a level (DESIGN.md "Hybrid multiply and
+ * linear transform with the rescale") ---------------------------------------
+ * rnt_ct_mul_relin_rescale_hybrid is DEFINED as rnt_ct_mul_relin_hybrid
+ * followed by rnt_ct_rescale, word for word: with r = ModDown(A) + d the level-Lv
+ * result of the former (last limb r_last),
+ *   out_j = (r_j - [r_last]_{q_j}) (q_last mod q_j)^-1 mod q_j,  j < Lv - 1,
+ * canonical, coefficient domain.  r is never written: the seeds d0, d1 enter the
+ * key products in the NTT domain (ModDown(A + P d) = ModDown(A) + d exactly,
+ * since P d vanishes on the special limbs) and one kernel does ModDown and the
+ * rescale.  c0, c1, c0p, c1p: B polys over C (Lv limbs), coefficient domain;
+ * out0, out1: B polys on ONE shared context that is drop_last(1) of C, so no
+ * output can be an input.
+ * Errors: out0 == out1 -> RNT_ERR_BAD_ARGUMENT; inputs on different contexts
+ * -> RNT_ERR_BASIS_MISMATCH, of different batch sizes -> RNT_ERR_BAD_ARGUMENT;
+ * rnt_keyswitch_hybrid's rules and statuses for alpha (0 -> RNT_ERR_BAD_ARGUMENT),
+ * degree, device, moduli prefix, word width, the key's poly count
+ * (RNT_ERR_CHANNEL_COUNT, fields: beta, got) and a coefficient-domain key
+ * (RNT_ERR_DOMAIN_MISMATCH); an NTT-domain input -> RNT_ERR_DOMAIN_MISMATCH;
+ * then rnt_ct_mul_relin_rescale's output rules: a one-limb ciphertext ->
+ * RNT_ERR_INVALID_MOD_DROP (fields: 1, Lv); an output whose context is not
+ * drop_last(1) of C, or outputs on two contexts -> RNT_ERR_BASIS_MISMATCH; an
+ * output of another batch size -> RNT_ERR_BAD_ARGUMENT.  A refused call leaves
+ * its outputs untouched.  Recordable after one plain run of the (E, Lv, alpha)
+ * triple, like the other hybrid calls. */
+int rnt_ct_mul_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                    const rnt_buf* c0p, const rnt_buf* c1p,
+                                    const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha);
+/* rnt_ct_linear_bsgs_hybrid followed by rnt_ct_rescale, word for word: the same
+ * arguments, the outputs as above (B polys on one shared drop_last(1) of C, so
+ * none aliases an input).  With a nonzero giant step the two closing ModDowns
+ * and the rescale are one kernel each; with none (the diagonal method) there is
+ * no ModDown and the rescale kernel reads the sums.  Errors: those of
+ * rnt_ct_linear_bsgs_hybrid for steps, plaintexts, keys, alpha and domains, then
+ * the output rules above with their statuses and fields. */
+int rnt_ct_linear_bsgs_hybrid_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                      const int32_t* baby_steps, size_t n_baby,
+                                      const int32_t* giant_steps, size_t n_giant, const rnt_buf* diag,
+                                      const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
+                                      const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b, size_t alpha);
 
 /* ---- limb-sharded building blocks ------------------------ */
 /* A rank owning a contiguous run of the global basis' limbs holds every

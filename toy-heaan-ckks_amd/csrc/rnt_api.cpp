@@ -97,7 +97,8 @@ const char* const kKernelNames[rnt::K_COUNT] = {
     "col_fwd", "row_fwd", "row_inv", "row_mul", "col_inv", "elementwise", "rescale",
     "automorphism", "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt",
     "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
-    "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto"};
+    "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto",
+    "moddown_rescale"};
 
 // A profiling call failed: clear the runtime's slot, keep the first failure
 // in the profiler, and stop profiling (rnt_profile_read reports it).
@@ -2929,6 +2930,7 @@ int hybrid_prepare(HybridPlan* pl) {
   hd.hc.pinv = at(lay.pinv), hd.hc.pinvp = at(lay.pinvp);
   hd.hc.pq = at(lay.pq), hd.hc.pqp = at(lay.pqp);
   hd.hc.Pinv = at(lay.Pinv), hd.hc.Pinvp = at(lay.Pinvp);
+  hd.hc.Pw = at(lay.Pw), hd.hc.Pwp = at(lay.Pwp);
   hd.hc.Lv = (uint32_t)pl->Lv, hd.hc.K = (uint32_t)pl->K;
   hd.hc.alpha = (uint32_t)pl->alpha, hd.hc.beta = (uint32_t)pl->beta;
   te->hyb_cache.push_back(hd);
@@ -2985,6 +2987,51 @@ int hybrid_chunk_run(const HybridPlan& pl, size_t c, char* ws, const void* x, ui
   if (int rc = inv_raw(k, A1, cls, tc)) return rc;
   LAUNCH_ON(tc, k.s, rnt::K_MODDOWN, rnt::launch_moddown(k, out0, out_ls, A0, cls, add0, add_ls, pl.hc), "ModDown");
   LAUNCH_ON(tc, k.s, rnt::K_MODDOWN, rnt::launch_moddown(k, out1, out_ls, A1, cls, add1, add_ls, pl.hc), "ModDown");
+  return RNT_OK;
+}
+
+// The tensor of the hybrid multiplies for one chunk (kc.B polys, inputs at
+// limb stride in_ls): d0^, d1^ (NTT domain, scaled by 2^-w) and the
+// coefficient-domain d2, each at limb stride cls.  T: the four-step path's
+// column outputs (four chunk blocks), the matrix-core path's scratch (one).
+int hybrid_tensor(const rnt::Launch& kc, bool whole, bool mf, char* const* T, char* D0, char* D1, char* D2,
+                  uint64_t cls, const char* c0, const char* c1, const char* c0p, const char* c1p, uint64_t in_ls) {
+  if (whole) {
+    LAUNCH(kc.t, rnt::K_TENSOR_WHOLE, rnt::launch_tensor_whole(kc, D0, D1, D2, cls, c0, c1, c0p, c1p, in_ls),
+           "tensor whole");
+  } else if (mf) {
+    LAUNCH(kc.t, rnt::K_MF_TENSOR, rnt::launch_mf_tensor(kc, D0, D1, D2, cls, c0, c1, c0p, c1p, in_ls, T[0]),
+           "MFMA tensor");
+  } else {
+    LAUNCH(kc.t, rnt::K_COL_FWD, rnt::launch_col_fwd(kc, T[0], c0, T[1], c1, in_ls, cls), "tensor column");
+    LAUNCH(kc.t, rnt::K_COL_FWD, rnt::launch_col_fwd(kc, T[2], c0p, T[3], c1p, in_ls, cls), "tensor column");
+    LAUNCH(kc.t, rnt::K_TENSOR_ROWS, rnt::launch_tensor_rows(kc, D0, D1, D2, T[0], T[1], T[2], T[3], cls), "tensor rows");
+    LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, D2, cls, D2, cls, 1, nullptr), "d2 inverse");
+  }
+  return RNT_OK;
+}
+
+// Whether an NTT-domain plane of the ciphertext context's transforms is, on a
+// limb both bases hold, a plane of the key basis': limb j is the same modulus
+// and degree (hybrid_check), so the same psi (find_psi is a function of (q, N))
+// and the same twiddles; the word width is the same (hybrid_check); and
+// fwd_raw / inv_raw choose their kernels from (plane, wide, log_n) alone -- mf
+// is set exactly where mf_supported() holds.  What is left is `plane`, read
+// from the environment when a root context is created.
+bool hybrid_same_transforms(const HybridPlan& pl) { return pl.C->t->plane == pl.E->t->plane; }
+
+// The output rules of a call that ends in a rescale (rnt_ct_mul_relin_rescale's).
+int rescaled_outputs_check(const rnt_buf* out0, const rnt_buf* out1, const rnt_buf* c0) {
+  const size_t L = c0->ctx->L;
+  if (L < 2)  // poly.rs:191-197
+    return fail_fields(RNT_ERR_INVALID_MOD_DROP, 1, L, "invalid mod-drop count 1 for %zu channels", L);
+  for (const rnt_buf* o : {out0, out1}) {
+    if (o->ctx->t != c0->ctx->t || o->ctx->L != L - 1)
+      return fail(RNT_ERR_BASIS_MISMATCH, "rescale: output basis is not drop_last(1) of the input's");
+    if (o->n_polys != c0->n_polys) return fail(RNT_ERR_BAD_ARGUMENT, "rescale: batch sizes differ");
+  }
+  if (out0->ctx != out1->ctx)  // engine.rs:272-274: one shared new basis
+    return fail(RNT_ERR_BASIS_MISMATCH, "rescale_ciphertext: outputs must share one basis");
   return RNT_OK;
 }
 
@@ -3115,20 +3162,8 @@ extern "C" int rnt_ct_mul_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_b
     const uint64_t cls = (uint64_t)c * n;
     const size_t po = p0 * n * wb;
     auto off = [&](const rnt_buf* b) { return (const char*)b->data + po; };
-    if (whole) {
-      LAUNCH(kc.t, rnt::K_TENSOR_WHOLE,
-             rnt::launch_tensor_whole(kc, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls),
-             "tensor whole");
-    } else if (mf) {
-      LAUNCH(kc.t, rnt::K_MF_TENSOR,
-             rnt::launch_mf_tensor(kc, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls, T[0]),
-             "MFMA tensor");
-    } else {
-      LAUNCH(kc.t, rnt::K_COL_FWD, rnt::launch_col_fwd(kc, T[0], off(c0), T[1], off(c1), full_ls, cls), "tensor column");
-      LAUNCH(kc.t, rnt::K_COL_FWD, rnt::launch_col_fwd(kc, T[2], off(c0p), T[3], off(c1p), full_ls, cls), "tensor column");
-      LAUNCH(kc.t, rnt::K_TENSOR_ROWS, rnt::launch_tensor_rows(kc, D0, D1, D2, T[0], T[1], T[2], T[3], cls), "tensor rows");
-      LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, D2, cls, D2, cls, 1, nullptr), "d2 inverse");
-    }
+    if (int rc = hybrid_tensor(kc, whole, mf, T, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls))
+      return rc;
     for (char* Dx : {D0, D1}) {  // INV(d^ 2^-w) 2^w = d, canonical
       if (int rc = inv_raw(kc, Dx, cls)) return rc;
       LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 1, Dx, Dx, nullptr, 0, false), "seed unscale");
@@ -3136,6 +3171,112 @@ extern "C" int rnt_ct_mul_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_b
     if (int rc = hybrid_chunk_run(pl, c, HW, D2, cls, key_a, key_b, (char*)out0->data + po, (char*)out1->data + po,
                                   full_ls, D0, D1, cls))
       return rc;
+  }
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
+// rnt_ct_mul_relin_hybrid followed by rnt_ct_rescale, word for word.  Per
+// chunk: the tensor writes d0^ 2^-w, d1^ 2^-w into the first Lv limbs of the
+// accumulators A0, A1 themselves; k_modup and the forward transform of d2's
+// digits; k_hoist_mac_seed, whose sums start from those seeds times P 2^w (so
+// A = sum + P d in the NTT domain, ModDown(A) = ModDown(sum) + d); two inverses
+// over the key basis; two k_moddown_rescale launches into the outputs.  No
+// seed inverse, no unscale pass, no addend, no level-Lv product in memory.
+// Where the two contexts' transforms may differ (hybrid_same_transforms) the
+// seeds take rnt_ct_mul_relin_hybrid's way -- inverse, unscale, ModDown's
+// addends -- and only the tail is fused.
+extern "C" int rnt_ct_mul_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                               const rnt_buf* c0p, const rnt_buf* c1p, const rnt_buf* key_a,
+                                               const rnt_buf* key_b, size_t alpha) {
+  const char* name = "rnt_ct_mul_relin_rescale_hybrid";
+  const rnt_buf* all[6] = {out0, out1, c0, c1, c0p, c1p};
+  for (const rnt_buf* b : all)
+    if (int rc = check_buf(b, name)) return rc;
+  if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
+  for (int i = 3; i < 6; ++i)
+    if (int rc = check_same(c0, all[i], name)) return rc;
+  HybridPlan pl;
+  if (int rc = hybrid_check(name, c0->ctx, key_a, key_b, alpha, &pl)) return rc;
+  if (c0->in_ntt || c1->in_ntt || c0p->in_ntt || c1p->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: inputs must be in coefficient domain", name);
+  if (int rc = rescaled_outputs_check(out0, out1, c0)) return rc;
+  if (int rc = set_device(c0->ctx)) return rc;
+  if (int rc = hybrid_prepare(&pl)) return rc;
+  rnt::Launch k = launch_for(c0);
+  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
+  const bool seeded = hybrid_same_transforms(pl);
+  const bool whole = rnt::tensor_whole_ok(k.t);
+  const bool mf = !whole && use_mf(k);
+  const size_t nt = whole ? 0 : mf ? 1 : 4;
+  const size_t nd = seeded ? 1 : 3;  // d2 (and, un-seeded, d0 and d1) over the ciphertext limbs
+  const size_t bc = hybrid_chunk(pl, B, (nt + nd) * L);
+  const size_t chunk_words = L * bc * n;
+  // ws: [T0..T3] | D2 | [D0 | D1] | the chunk's D, A0, A1
+  CallWs cws(out0);
+  if (int rc = cws.get(std::max<size_t>(((nt + nd) * chunk_words + hybrid_planes(pl) * bc * n) * wb, 16))) return rc;
+  char* ws = (char*)cws.p;
+  char* T[4];
+  for (int i = 0; i < 4; ++i) T[i] = ws + i * chunk_words * wb;
+  char* D2 = ws + nt * chunk_words * wb;
+  char* HW = D2 + nd * chunk_words * wb;
+  const rnt::Tables* tc = pl.C->t.get();
+  const void* rinv = rnt::resc_inv_row(tc, L - 1, 0);
+  const void* rinvp = rnt::resc_inv_row(tc, L - 1, 1);
+  const uint64_t full_ls = limb_stride(c0), out_ls = limb_stride(out0);
+  for (size_t p0 = 0; p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    rnt::Launch kc = k;
+    kc.B = c;
+    const uint64_t cls = (uint64_t)c * n;
+    const size_t po = p0 * n * wb;
+    auto off = [&](const rnt_buf* b) { return (const char*)b->data + po; };
+    rnt::Launch ke;
+    ke.t = pl.E->t.get();
+    ke.L = pl.LE;
+    ke.B = c;
+    ke.s = tc->stream;
+    char* D = HW;
+    char* A0 = D + pl.LE * pl.beta * c * n * wb;
+    char* A1 = A0 + pl.LE * c * n * wb;
+    char* D0 = seeded ? A0 : D2 + chunk_words * wb;
+    char* D1 = seeded ? A1 : D0 + chunk_words * wb;
+    if (int rc = hybrid_tensor(kc, whole, mf, T, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls))
+      return rc;
+    if (!seeded)
+      for (char* Dx : {D0, D1}) {  // INV(d^ 2^-w) 2^w = d, canonical
+        if (int rc = inv_raw(kc, Dx, cls)) return rc;
+        LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 1, Dx, Dx, nullptr, 0, false), "seed unscale");
+      }
+    LAUNCH_ON(tc, ke.s, rnt::K_MODUP, rnt::launch_modup(ke, D, D2, cls, pl.hc), "ModUp");
+    rnt::Launch kd = ke;
+    kd.B = pl.beta * c;
+    if (int rc = fwd_raw(kd, D, (uint64_t)kd.B * n, tc)) return rc;
+    rnt::Launch km = ke;
+    km.Ls = pl.beta;
+    if (seeded) {
+      LAUNCH_ON(tc, ke.s, rnt::K_HOIST_MAC,
+                rnt::launch_hoist_mac_seed(km, A0, A1, D, key_a->data, key_b->data, limb_stride(key_a), A1, A0, cls,
+                                           pl.hc),
+                "hybrid key products (seeded)");
+    } else {
+      void* a0[1] = {A0};
+      void* a1[1] = {A1};
+      const void* ka[1] = {key_a->data};
+      const void* kb[1] = {key_b->data};
+      LAUNCH_ON(tc, ke.s, rnt::K_HOIST_MAC, rnt::launch_hoist_mac(km, a0, a1, 1, D, ka, kb, limb_stride(key_a)),
+                "hybrid key products");
+    }
+    if (int rc = inv_raw(ke, A0, cls, tc)) return rc;
+    if (int rc = inv_raw(ke, A1, cls, tc)) return rc;
+    LAUNCH_ON(tc, ke.s, rnt::K_MODDOWN_RESCALE,
+              rnt::launch_moddown_rescale(ke, (char*)out0->data + po, out_ls, A0, cls, seeded ? nullptr : D0, cls, rinv,
+                                          rinvp, pl.hc),
+              "ModDown and rescale");
+    LAUNCH_ON(tc, ke.s, rnt::K_MODDOWN_RESCALE,
+              rnt::launch_moddown_rescale(ke, (char*)out1->data + po, out_ls, A1, cls, seeded ? nullptr : D1, cls, rinv,
+                                          rinvp, pl.hc),
+              "ModDown and rescale");
   }
   out0->in_ntt = out1->in_ntt = 0;
   return RNT_OK;
@@ -3796,12 +3937,16 @@ extern "C" int rnt_ct_rotate_hybrid_hoisted(rnt_buf* out0, rnt_buf* out1, const 
   return RNT_OK;
 }
 
-extern "C" int rnt_ct_linear_bsgs_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
-                                         const int32_t* baby_steps, size_t n_baby, const int32_t* giant_steps,
-                                         size_t n_giant, const rnt_buf* diag, const rnt_buf* baby_keys_a,
-                                         const rnt_buf* baby_keys_b, const rnt_buf* giant_keys_a,
-                                         const rnt_buf* giant_keys_b, size_t alpha) {
-  const char* name = "rnt_ct_linear_bsgs_hybrid";
+// rnt_ct_linear_bsgs_hybrid (rescale false) and rnt_ct_linear_bsgs_hybrid_rescale
+// (true): the same stages; with `rescale` the outputs are on drop_last(1) of
+// the ciphertext's context and the tail is the rescaling one -- with a nonzero
+// giant step the two final ModDowns are k_moddown_rescale with the same
+// addends, without one k_rescale reads the sums (no fusion there).
+static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt_buf* out1,
+                                      const rnt_buf* c0, const rnt_buf* c1, const int32_t* baby_steps, size_t n_baby,
+                                      const int32_t* giant_steps, size_t n_giant, const rnt_buf* diag,
+                                      const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
+                                      const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b, size_t alpha) {
   const rnt_buf* all[4] = {out0, out1, c0, c1};
   for (const rnt_buf* b : all)
     if (int rc = check_buf(b, name)) return rc;
@@ -3809,8 +3954,12 @@ extern "C" int rnt_ct_linear_bsgs_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt
   if (n_baby == 0 || n_giant == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: no steps", name);
   if (!baby_steps || !giant_steps) return fail(RNT_ERR_BAD_ARGUMENT, "%s: null steps", name);
   if (alpha == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: alpha must be at least 1", name);
-  for (int i = 1; i < 4; ++i)
-    if (int rc = check_same(all[0], all[i], name)) return rc;
+  if (rescale) {
+    if (int rc = check_same(c0, c1, name)) return rc;
+  } else {
+    for (int i = 1; i < 4; ++i)
+      if (int rc = check_same(all[0], all[i], name)) return rc;
+  }
   if (diag->ctx != c0->ctx) return fail(RNT_ERR_BASIS_MISMATCH, "%s: the plaintexts belong to a different basis", name);
   if (n_baby > SIZE_MAX / n_giant || diag->n_polys != n_baby * n_giant)
     return fail(RNT_ERR_BAD_ARGUMENT, "%s: %zu plaintexts for %zu x %zu steps", name, diag->n_polys, n_giant, n_baby);
@@ -3825,6 +3974,8 @@ extern "C" int rnt_ct_linear_bsgs_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt
   if (!diag->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the plaintexts must be in the NTT domain", name);
   if (c0->in_ntt || c1->in_ntt)
     return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the ciphertext must be in coefficient domain", name);
+  if (rescale)
+    if (int rc = rescaled_outputs_check(out0, out1, c0)) return rc;
   const rnt_buf* ins[7] = {c0, c1, diag, baby_keys_a, baby_keys_b, giant_keys_a, giant_keys_b};
   if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
   for (int i = 0; i < 7; ++i) {
@@ -3962,21 +4113,59 @@ extern "C" int rnt_ct_linear_bsgs_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt
     }
     char* dst[2] = {(char*)out[0]->data + p0 * n * wb, (char*)out[1]->data + p0 * n * wb};
     if (!plan.any_rot) {
-      for (int o = 0; o < 2; ++o)
-        if (int rc = copy_rows(kc, dst[o], full_ls, VB + (2 * plan.zslot + o) * pw, cls, cls, Lv)) return rc;
+      for (int o = 0; o < 2; ++o) {
+        const char* V = VB + (2 * plan.zslot + o) * pw;
+        if (rescale) {
+          LAUNCH(kc.t, rnt::K_RESCALE, rnt::launch_rescale_strided(kc, dst[o], limb_stride(out[o]), V, cls), "rescale");
+        } else if (int rc = copy_rows(kc, dst[o], full_ls, V, cls, cls, Lv)) {
+          return rc;
+        }
+      }
     } else {
       const rnt::Launch ke = hybrid_launch(pl, c);
       if (int rc = inv_raw(ke, A0, cls, kc.t)) return rc;
       if (int rc = inv_raw(ke, A1, cls, kc.t)) return rc;
       const char* Z1 = plan.any_zero ? VB + (2 * plan.zslot + 1) * pw : nullptr;
-      LAUNCH_ON(kc.t, ke.s, rnt::K_MODDOWN, rnt::launch_moddown(ke, dst[0], full_ls, A0, cls, S0, cls, pl.hc),
-                "ModDown");
-      LAUNCH_ON(kc.t, ke.s, rnt::K_MODDOWN, rnt::launch_moddown(ke, dst[1], full_ls, A1, cls, Z1, cls, pl.hc),
-                "ModDown");
+      if (rescale) {
+        const void* rinv = rnt::resc_inv_row(kc.t, Lv - 1, 0);
+        const void* rinvp = rnt::resc_inv_row(kc.t, Lv - 1, 1);
+        LAUNCH_ON(kc.t, ke.s, rnt::K_MODDOWN_RESCALE,
+                  rnt::launch_moddown_rescale(ke, dst[0], limb_stride(out[0]), A0, cls, S0, cls, rinv, rinvp, pl.hc),
+                  "ModDown and rescale");
+        LAUNCH_ON(kc.t, ke.s, rnt::K_MODDOWN_RESCALE,
+                  rnt::launch_moddown_rescale(ke, dst[1], limb_stride(out[1]), A1, cls, Z1, cls, rinv, rinvp, pl.hc),
+                  "ModDown and rescale");
+      } else {
+        LAUNCH_ON(kc.t, ke.s, rnt::K_MODDOWN, rnt::launch_moddown(ke, dst[0], full_ls, A0, cls, S0, cls, pl.hc),
+                  "ModDown");
+        LAUNCH_ON(kc.t, ke.s, rnt::K_MODDOWN, rnt::launch_moddown(ke, dst[1], full_ls, A1, cls, Z1, cls, pl.hc),
+                  "ModDown");
+      }
     }
   }
   out0->in_ntt = out1->in_ntt = 0;
   return RNT_OK;
+}
+
+extern "C" int rnt_ct_linear_bsgs_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                         const int32_t* baby_steps, size_t n_baby, const int32_t* giant_steps,
+                                         size_t n_giant, const rnt_buf* diag, const rnt_buf* baby_keys_a,
+                                         const rnt_buf* baby_keys_b, const rnt_buf* giant_keys_a,
+                                         const rnt_buf* giant_keys_b, size_t alpha) {
+  return ct_linear_bsgs_hybrid_body("rnt_ct_linear_bsgs_hybrid", false, out0, out1, c0, c1, baby_steps, n_baby,
+                                    giant_steps, n_giant, diag, baby_keys_a, baby_keys_b, giant_keys_a, giant_keys_b,
+                                    alpha);
+}
+
+extern "C" int rnt_ct_linear_bsgs_hybrid_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                                 const int32_t* baby_steps, size_t n_baby,
+                                                 const int32_t* giant_steps, size_t n_giant, const rnt_buf* diag,
+                                                 const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
+                                                 const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b,
+                                                 size_t alpha) {
+  return ct_linear_bsgs_hybrid_body("rnt_ct_linear_bsgs_hybrid_rescale", true, out0, out1, c0, c1, baby_steps, n_baby,
+                                    giant_steps, n_giant, diag, baby_keys_a, baby_keys_b, giant_keys_a, giant_keys_b,
+                                    alpha);
 }
 
 extern "C" int rnt_copy_polys(rnt_buf* dst, size_t dst_first, const rnt_buf* src, size_t src_first,

@@ -155,7 +155,7 @@ inline uint64_t neg_free_qinv(uint64_t q, unsigned wbits) {
 // product is taken mod its target.  Returns false when two moduli share a factor.
 struct HybridLayout {
   size_t Lv, K, alpha, beta, LE;
-  size_t yinv, yinvp, conv, convp, pinv, pinvp, pq, pqp, Pinv, Pinvp, total;
+  size_t yinv, yinvp, conv, convp, pinv, pinvp, pq, pqp, Pinv, Pinvp, Pw, Pwp, total;
   HybridLayout(size_t Lv_, size_t K_, size_t alpha_)
       : Lv(Lv_), K(K_), alpha(alpha_), beta((Lv_ + alpha_ - 1) / alpha_), LE(Lv_ + K_) {
     size_t o = 0;
@@ -169,6 +169,8 @@ struct HybridLayout {
     pqp = o, o += K * Lv;
     Pinv = o, o += Lv;
     Pinvp = o, o += Lv;
+    Pw = o, o += Lv;  // (appended: the offsets above are what they were)
+    Pwp = o, o += Lv;
     total = o;
   }
 };
@@ -218,6 +220,9 @@ inline bool hybrid_constants(const uint64_t* m, const HybridLayout& h, unsigned 
     const uint64_t inv = invmod(s, m[j]);
     if (inv == 0) return false;
     pair(h.Pinv + j, h.Pinvp + j, inv, m[j]);
+    // P 2^w mod q_j: k_hoist_mac_seed's factor of an NTT-domain seed d^ 2^-w
+    const uint64_t rw = (uint64_t)((((u128)1) << wbits) % m[j]);
+    pair(h.Pw + j, h.Pwp + j, mulmod(s, rw, m[j]), m[j]);
   }
   return true;
 }

@@ -91,6 +91,8 @@ struct HybridConsts {
   const void* pqp = nullptr;
   const void* Pinv = nullptr;   // [Lv]  P^-1 mod q_j
   const void* Pinvp = nullptr;
+  const void* Pw = nullptr;     // [Lv]  P 2^w mod q_j (k_hoist_mac_seed)
+  const void* Pwp = nullptr;
   uint32_t Lv = 0, K = 0, alpha = 0, beta = 0;
 };
 struct HybridDev {
@@ -152,7 +154,7 @@ enum KernelId {
   K_AUTOMORPHISM, K_KS_DECOMPOSE, K_KS_ROWS, K_TENSOR_ROWS, K_IMPORT, K_EXPORT, K_CRT,
   K_SFFT, K_SAMPLE, K_COPY, K_PLANE_FUSED, K_MF_NTT_FWD, K_MF_NTT_INV, K_WHOLE_FWD, K_WHOLE_INV, K_WHOLE_MUL,
   K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_MODUP, K_MODDOWN,
-  K_MODDOWN_AUTO, K_COUNT
+  K_MODDOWN_AUTO, K_MODDOWN_RESCALE, K_COUNT
 };
 
 struct Prof {
@@ -400,6 +402,25 @@ hipError_t launch_moddown(const Launch& k, void* out, uint64_t out_ls, const voi
 // A nor the addend.
 hipError_t launch_moddown_auto(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
                                const void* add, uint64_t add_ls, uint64_t g, const HybridConsts& hc);
+// launch_moddown_rescale (k_moddown_rescale): launch_moddown's result rescaled
+// by its last limb without reaching memory -- out_j = (r_j - [r_{Lv-1}]_{q_j})
+// rinv[j] for j < Lv - 1, r = ModDown(A) (+ add); rinv / rinvp are the row
+// resc_inv_row(ciphertext tables, Lv - 1, 0 / 1) launch_rescale reads.  The
+// words are those of launch_moddown followed by launch_rescale.  Lv >= 2.
+hipError_t launch_moddown_rescale(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
+                                  const void* add, uint64_t add_ls, const void* rinv, const void* rinvp,
+                                  const HybridConsts& hc);
+// launch_hoist_mac_seed (k_hoist_mac_seed): launch_hoist_mac for one step whose
+// sums start, on the limbs j < hc.Lv, from seed_b[j] (P 2^w mod q_j) and
+// seed_a[j] (P 2^w mod q_j) and from 0 on the special limbs; the seeds are
+// NTT-domain d^ 2^-w over the ciphertext limbs at limb stride seed_ls, so the
+// accumulators are those of A + P d.
+hipError_t launch_hoist_mac_seed(const Launch& k, void* acc0, void* acc1, const void* d, const void* key_a,
+                                 const void* key_b, uint64_t key_ls, const void* seed_a, const void* seed_b,
+                                 uint64_t seed_ls, const HybridConsts& hc);
+// launch_rescale with limb strides: k.B polys of k.L input limbs at in_ls, the
+// k.L - 1 output limbs at out_ls (a chunk of a batch on either side).
+hipError_t launch_rescale_strided(const Launch& k, void* out, uint64_t out_ls, const void* in, uint64_t in_ls);
 // out[l][i] = 2^w mod q_l over [k.L][N]: the Montgomery-form plaintext 1.
 hipError_t launch_mont_one(const Launch& k, void* out);
 // The whole-plane key-switch at 2^10 <= N <= 2^13 (k_ks_whole, one launch,

@@ -2236,6 +2236,164 @@ k_moddown(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A, uint64_
   }
 }
 
+// One limb of k_moddown for a lane: r = (A_j - sum_k z_k (P/p_k mod q_j)) P^-1
+// (+ add_j) mod q_j, canonical -- the statements of k_moddown's loop body, for
+// k_moddown_rescale, which needs them at two places.
+template <class W, bool VEC, int KMAX, int V>
+__device__ __forceinline__ void moddown_limb(W (&r)[V], uint32_t j, const W (&z)[KMAX > 0 ? KMAX : 1][V],
+                                             const W* __restrict__ A, uint64_t a_ls, const W* add, uint64_t add_ls,
+                                             const TabPtrs<W>& tp, const W* __restrict__ pinv,
+                                             const W* __restrict__ pinvp, const W* __restrict__ pq,
+                                             const W* __restrict__ pqp, const W* __restrict__ Pinv,
+                                             const W* __restrict__ Pinvp, uint64_t i, uint32_t Lv, uint32_t K) {
+  const W q = tp.lc[j].q;
+  W cv[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) cv[v] = (W)0;
+  if constexpr (KMAX > 0) {
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      if ((uint32_t)k < K) {  // (uniform)
+        const W c = pq[(uint64_t)k * Lv + j], cp = pqp[(uint64_t)k * Lv + j];
+#pragma unroll
+        for (int v = 0; v < V; ++v) cv[v] = add_mod<W>(cv[v], shoup_mul<W>(z[k][v], c, cp, q), q);
+      }
+    }
+  } else {
+    const W* sp = A + (uint64_t)Lv * a_ls + i;
+    for (uint32_t k = 0; k < K; ++k) {
+      W av[V];
+      ld_vec<W, VEC, V>(av, sp + (uint64_t)k * a_ls);
+      const W p = tp.lc[Lv + k].q, ci = pinv[k], cip = pinvp[k];
+      const W c = pq[(uint64_t)k * Lv + j], cp = pqp[(uint64_t)k * Lv + j];
+#pragma unroll
+      for (int v = 0; v < V; ++v)
+        cv[v] = add_mod<W>(cv[v], shoup_mul<W>(shoup_mul<W>(av[v], ci, cip, p), c, cp, q), q);
+    }
+  }
+  W av[V];
+  ld_vec<W, VEC, V>(av, A + (uint64_t)j * a_ls + i);
+  const W c = Pinv[j], cp = Pinvp[j];
+#pragma unroll
+  for (int v = 0; v < V; ++v) r[v] = shoup_mul<W>(av[v] - cv[v] + q, c, cp, q);  // a - conv + q in (0, 2q)
+  if (add != nullptr) {  // (uniform)
+    W dv[V];
+    ld_vec<W, VEC, V>(dv, add + (uint64_t)j * add_ls + i);
+#pragma unroll
+    for (int v = 0; v < V; ++v) r[v] = add_mod<W>(r[v], dv[v], q);
+  }
+}
+
+// k_moddown followed by k_rescale, the level-Lv result never written: a lane
+// takes its z_k once, r_last = limb Lv - 1 of ModDown(A) (+ add), canonical,
+// and stores for every limb j < Lv - 1 of its run
+//   out_j = (r_j - [r_last]_{q_j}) (q_last mod q_j)^-1 mod q_j
+// with r_j as k_moddown computes it, [r_last]_{q_j} reduced as k_rescale reduces
+// it (Shoup product by 1) and rinv / rinvp the row of the ciphertext basis'
+// rescale table k_rescale reads: the words of the two kernels in sequence.
+// blockIdx.y takes a run of jper of the Lv - 1 output limbs; every run
+// recomputes z_k and r_last (K + 1 planes read again, hits of the cache).
+template <class W, bool VEC, int KMAX>
+__global__ void __launch_bounds__(256)
+k_moddown_rescale(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A, uint64_t a_ls, const W* add,
+                  uint64_t add_ls, TabPtrs<W> tp, const W* __restrict__ pinv, const W* __restrict__ pinvp,
+                  const W* __restrict__ pq, const W* __restrict__ pqp, const W* __restrict__ Pinv,
+                  const W* __restrict__ Pinvp, const W* __restrict__ rinv, const W* __restrict__ rinvp,
+                  uint64_t limb_words, uint32_t Lv, uint32_t K, uint32_t jper) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= limb_words) return;
+  const uint32_t last = Lv - 1;
+  const uint32_t j0 = blockIdx.y * jper;
+  const uint32_t j1 = j0 + jper < last ? j0 + jper : last;
+  W z[KMAX > 0 ? KMAX : 1][V];
+  if constexpr (KMAX > 0) {
+    const W* sp = A + (uint64_t)Lv * a_ls + i;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      if ((uint32_t)k < K) {  // (uniform)
+        W av[V];
+        ld_vec<W, VEC, V>(av, sp + (uint64_t)k * a_ls);
+        const W p = tp.lc[Lv + k].q, c = pinv[k], cp = pinvp[k];
+#pragma unroll
+        for (int v = 0; v < V; ++v) z[k][v] = shoup_mul<W>(av[v], c, cp, p);
+      }
+    }
+  }
+  W rl[V];
+  moddown_limb<W, VEC, KMAX, V>(rl, last, z, A, a_ls, add, add_ls, tp, pinv, pinvp, pq, pqp, Pinv, Pinvp, i, Lv, K);
+  for (uint32_t j = j0; j < j1; ++j) {
+    W r[V], o[V];
+    moddown_limb<W, VEC, KMAX, V>(r, j, z, A, a_ls, add, add_ls, tp, pinv, pinvp, pq, pqp, Pinv, Pinvp, i, Lv, K);
+    const LimbConst<W> lc = tp.lc[j];
+    const W inv = rinv[j], invp = rinvp[j];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const W cl = shoup_mul<W>(rl[v], (W)1, lc.one_p, lc.q);  // canonical r_last mod q_j, as k_rescale's
+      o[v] = shoup_mul<W>(sub_mod<W>(r[v], cl, lc.q), inv, invp, lc.q);
+    }
+    st_vec<W, VEC, V>(out + (uint64_t)j * out_ls + i, o);
+  }
+}
+
+// k_hoist_mac for one step whose sums start from a seed: on a ciphertext limb
+// j < Lv, acc0 from seed_b[j] c_j and acc1 from seed_a[j] c_j with c_j = P 2^w
+// mod q_j (Pw / Pwp, Shoup); on a special limb from 0 (the branch on
+// blockIdx.y is uniform).  The seeds are the tensor's d0^ 2^-w, d1^ 2^-w (NTT
+// domain, limb stride seed_ls), so seed c_j = NTT(P d) on limb j and the sums
+// are the accumulators of A + P d, whose ModDown is ModDown(A) + d: the seeds
+// need no inverse transform and ModDown no addend.  One accumulator pair, not
+// HOIST_T: the multiply has one key.  A kernel of its own, so that k_hoist_mac
+// stays as it is.  A lane reads its seed vectors before it stores the sums at
+// the same (limb, position), so with seed_ls = limb_words the seeds may lie in
+// the accumulators' own first Lv limbs (seed_b == out0, seed_a == out1: no
+// __restrict__ on the four).
+template <class W, bool VEC>
+__global__ void __launch_bounds__(256)
+k_hoist_mac_seed(W* out0, W* out1, const W* __restrict__ key_b,
+                 const W* __restrict__ key_a, const W* __restrict__ d, const W* seed_b,
+                 const W* seed_a, uint64_t seed_ls, const W* __restrict__ Pw,
+                 const W* __restrict__ Pwp, TabPtrs<W> tp, uint32_t log_n, uint64_t limb_words, uint64_t key_ls,
+                 uint32_t Ls, uint32_t Lv) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint32_t j = blockIdx.y;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= limb_words) return;
+  const LimbConst<W> lc = tp.lc[j];
+  const uint64_t N = 1ull << log_n;
+  const W* dp = d + (uint64_t)j * Ls * limb_words + i;
+  const uint64_t ko = (uint64_t)j * key_ls + (i & (N - 1));  // V divides N: one plane
+  W acc0[V], acc1[V];
+  if (j < Lv) {  // (uniform)
+    W s0[V], s1[V];
+    ld_vec<W, VEC, V>(s0, seed_b + (uint64_t)j * seed_ls + i);
+    ld_vec<W, VEC, V>(s1, seed_a + (uint64_t)j * seed_ls + i);
+    const W c = Pw[j], cp = Pwp[j];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      acc0[v] = shoup_mul<W>(s0[v], c, cp, lc.q);
+      acc1[v] = shoup_mul<W>(s1[v], c, cp, lc.q);
+    }
+  } else {
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc0[v] = acc1[v] = (W)0;
+  }
+  for (uint32_t s = 0; s < Ls; ++s) {
+    W xv[V], bv[V], av[V];
+    ld_vec<W, VEC, V>(xv, dp + (uint64_t)s * limb_words);
+    ld_vec<W, VEC, V>(bv, key_b + ko + (uint64_t)s * N);
+    ld_vec<W, VEC, V>(av, key_a + ko + (uint64_t)s * N);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      acc0[v] = add_mod<W>(acc0[v], mont_mul<W>(xv[v], bv[v], lc.q, lc.qinv), lc.q);
+      acc1[v] = add_mod<W>(acc1[v], mont_mul<W>(xv[v], av[v], lc.q, lc.qinv), lc.q);
+    }
+  }
+  const uint64_t g = (uint64_t)j * limb_words + i;
+  st_vec<W, VEC, V>(out0 + g, acc0);
+  st_vec<W, VEC, V>(out1 + g, acc1);
+}
+
 __device__ __forceinline__ uint64_t xcd_gid();
 
 // k_moddown followed by sigma_g of the result (g odd), written at the output's
@@ -2930,6 +3088,72 @@ static hipError_t moddown_t(const Launch& k, void* out, uint64_t out_ls, const v
   return hipGetLastError();
 }
 
+// The runs of the split are over the Lv - 1 output limbs.
+template <class W>
+static hipError_t moddown_rescale_t(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
+                                    const void* add, uint64_t add_ls, const void* rinv, const void* rinvp,
+                                    const HybridConsts& hc) {
+  const uint64_t N = 1ull << k.t->log_n;
+  const uint64_t limb_words = (uint64_t)k.B * N;
+  if (hc.Lv < 2 || hc.K == 0 || k.L != (size_t)hc.Lv + hc.K || k.L > k.t->L || out_ls < limb_words ||
+      a_ls < limb_words || (add && add_ls < limb_words) || !rinv || !rinvp)
+    return hipErrorInvalidValue;
+  if (limb_words == 0) return hipSuccess;
+  constexpr int V = 16 / (int)sizeof(W);
+  const bool vec = N % V == 0 && out_ls % V == 0 && a_ls % V == 0 && (!add || add_ls % V == 0) &&
+                   ((uintptr_t)out | (uintptr_t)A | (uintptr_t)add) % 16 == 0;
+  const uint64_t per = vec ? limb_words / V : limb_words;
+  const uint64_t bx = (per + 255) / 256;
+  if (bx > 0x7fffffffull) return hipErrorInvalidConfiguration;
+  const uint64_t lo = hc.Lv - 1;
+  const uint64_t runs = std::min<uint64_t>(lo, std::max<uint64_t>(kSplitBlocks / bx, 1));
+  const uint32_t jper = (uint32_t)((lo + runs - 1) / runs);
+  const dim3 grid((unsigned)bx, (unsigned)((lo + jper - 1) / jper));
+#define RNT_MR(VEC, KMAX)                                                                              \
+  hipLaunchKernelGGL((k_moddown_rescale<W, VEC, KMAX>), grid, dim3(256), 0, k.s, (W*)out, out_ls,       \
+                     (const W*)A, a_ls, (const W*)add, add_ls, tab_ptrs<W>(k.t), (const W*)hc.pinv,     \
+                     (const W*)hc.pinvp, (const W*)hc.pq, (const W*)hc.pqp, (const W*)hc.Pinv,          \
+                     (const W*)hc.Pinvp, (const W*)rinv, (const W*)rinvp, limb_words, hc.Lv, hc.K, jper)
+#define RNT_MR_K(KMAX) do { if (vec) RNT_MR(true, KMAX); else RNT_MR(false, KMAX); } while (0)
+  if (hc.K <= 4) RNT_MR_K(4);
+  else if (hc.K <= 8) RNT_MR_K(8);
+  else if (hc.K <= 16) RNT_MR_K(16);
+  else RNT_MR_K(0);
+#undef RNT_MR_K
+#undef RNT_MR
+  return hipGetLastError();
+}
+
+template <class W>
+static hipError_t hoist_mac_seed_t(const Launch& k, void* acc0, void* acc1, const void* d, const void* key_a,
+                                   const void* key_b, uint64_t key_ls, const void* seed_a, const void* seed_b,
+                                   uint64_t seed_ls, const HybridConsts& hc) {
+  const uint64_t N = 1ull << k.t->log_n;
+  const uint64_t limb_words = (uint64_t)k.B * N;
+  const size_t Ls = k.src_limbs();
+  if (Ls == 0 || key_ls < Ls * N || hc.Lv == 0 || k.L != (size_t)hc.Lv + hc.K || k.L > k.t->L ||
+      seed_ls < limb_words || !seed_a || !seed_b || !hc.Pw || !hc.Pwp)
+    return hipErrorInvalidValue;
+  if (limb_words == 0) return hipSuccess;
+  constexpr int V = 16 / (int)sizeof(W);
+  const uintptr_t align = (uintptr_t)d | (uintptr_t)key_a | (uintptr_t)key_b | (uintptr_t)acc0 | (uintptr_t)acc1 |
+                          (uintptr_t)seed_a | (uintptr_t)seed_b;
+  // 16-byte accesses: whole vectors within a plane, every plane and block 16-byte aligned
+  const bool vec = N % V == 0 && key_ls % V == 0 && seed_ls % V == 0 && align % 16 == 0;
+  const uint64_t per = vec ? limb_words / V : limb_words;
+  const uint64_t bx = (per + 255) / 256;
+  if (bx > 0x7fffffffull || k.L > 65535) return hipErrorInvalidConfiguration;
+  const dim3 grid((unsigned)bx, (unsigned)k.L);
+#define RNT_HS(VEC)                                                                                      \
+  hipLaunchKernelGGL((k_hoist_mac_seed<W, VEC>), grid, dim3(256), 0, k.s, (W*)acc0, (W*)acc1,            \
+                     (const W*)key_b, (const W*)key_a, (const W*)d, (const W*)seed_b, (const W*)seed_a,  \
+                     seed_ls, (const W*)hc.Pw, (const W*)hc.Pwp, tab_ptrs<W>(k.t), k.t->log_n,           \
+                     limb_words, key_ls, (uint32_t)Ls, hc.Lv)
+  if (vec) RNT_HS(true); else RNT_HS(false);
+#undef RNT_HS
+  return hipGetLastError();
+}
+
 // g odd, below 2N.  The stores are single words: only A and the addend decide
 // the 16-byte form.  Grid x a multiple of 8 (xcd_gid()).
 template <class W>
@@ -3032,6 +3256,20 @@ static hipError_t rescale_t(const Launch& k, void* out, const void* in) {
   hipLaunchKernelGGL((k_rescale<W>), dim3(grid_for(pw, 256)), dim3(256), 0, k.s, (W*)out,
                      (const W*)in, (const W*)in + last * pw, tp.resc + last * tp.Lroot,
                      tp.rescp + last * tp.Lroot, tp, pw, pw, pw, (uint32_t)last);
+  return hipGetLastError();
+}
+
+// rescale_t at limb strides of its own on either side (k.B polys per limb).
+template <class W>
+static hipError_t rescale_strided_t(const Launch& k, void* out, uint64_t out_ls, const void* in, uint64_t in_ls) {
+  const uint64_t pw = (uint64_t)k.B << k.t->log_n;
+  if (k.L == 0 || k.L > k.t->L || out_ls < pw || in_ls < pw) return hipErrorInvalidValue;
+  if (pw * (k.L - 1) == 0) return hipSuccess;
+  const TabPtrs<W> tp = tab_ptrs<W>(k.t);
+  const uint64_t last = k.L - 1;
+  hipLaunchKernelGGL((k_rescale<W>), dim3(grid_for(pw, 256)), dim3(256), 0, k.s, (W*)out,
+                     (const W*)in, (const W*)in + last * in_ls, tp.resc + last * tp.Lroot,
+                     tp.rescp + last * tp.Lroot, tp, in_ls, out_ls, pw, (uint32_t)last);
   return hipGetLastError();
 }
 
@@ -3589,6 +3827,21 @@ hipError_t launch_moddown_auto(const Launch& k, void* out, uint64_t out_ls, cons
                                const void* add, uint64_t add_ls, uint64_t g, const HybridConsts& hc) {
   RNT_WIDE(moddown_auto_t<uint32_t>(k, out, out_ls, A, a_ls, add, add_ls, g, hc),
            moddown_auto_t<uint64_t>(k, out, out_ls, A, a_ls, add, add_ls, g, hc));
+}
+hipError_t launch_moddown_rescale(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
+                                  const void* add, uint64_t add_ls, const void* rinv, const void* rinvp,
+                                  const HybridConsts& hc) {
+  RNT_WIDE(moddown_rescale_t<uint32_t>(k, out, out_ls, A, a_ls, add, add_ls, rinv, rinvp, hc),
+           moddown_rescale_t<uint64_t>(k, out, out_ls, A, a_ls, add, add_ls, rinv, rinvp, hc));
+}
+hipError_t launch_hoist_mac_seed(const Launch& k, void* acc0, void* acc1, const void* d, const void* key_a,
+                                 const void* key_b, uint64_t key_ls, const void* seed_a, const void* seed_b,
+                                 uint64_t seed_ls, const HybridConsts& hc) {
+  RNT_WIDE(hoist_mac_seed_t<uint32_t>(k, acc0, acc1, d, key_a, key_b, key_ls, seed_a, seed_b, seed_ls, hc),
+           hoist_mac_seed_t<uint64_t>(k, acc0, acc1, d, key_a, key_b, key_ls, seed_a, seed_b, seed_ls, hc));
+}
+hipError_t launch_rescale_strided(const Launch& k, void* out, uint64_t out_ls, const void* in, uint64_t in_ls) {
+  RNT_WIDE(rescale_strided_t<uint32_t>(k, out, out_ls, in, in_ls), rescale_strided_t<uint64_t>(k, out, out_ls, in, in_ls));
 }
 hipError_t launch_mont_one(const Launch& k, void* out) {
   RNT_WIDE(mont_one_t<uint32_t>(k, out), mont_one_t<uint64_t>(k, out));

@@ -41,6 +41,8 @@ __all__ = [
     "rotate_ciphertext_hybrid_hoisted",
     "linear_transform_hybrid",
     "linear_transform_bsgs_hybrid",
+    "mul_ciphertexts_hybrid_rescale",
+    "linear_transform_bsgs_hybrid_rescale",
     "Ciphertext",
     "generate_primes",
     "is_ntt_friendly_prime",
@@ -1058,6 +1060,48 @@ def mul_ciphertexts_gadget_rescale(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsGad
     check(load().rnt_ct_mul_relin_rescale(out0.handle, out1.handle, ct1.c0.handle, ct1.c1.handle,
                                           ct2.c0.handle, ct2.c1.handle, rlk.a.handle, rlk.b.handle))
     return Ciphertext(out0, out1, ct1.logp + ct2.logp - bits_dropped, ct1.logq - bits_dropped)
+
+
+def mul_ciphertexts_hybrid_rescale(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsHybridKey) -> Ciphertext:
+    """mul_ciphertexts_hybrid then rescale_ciphertext as one op
+    (rnt_ct_mul_relin_rescale_hybrid): equal word for word to the two calls;
+    the un-rescaled product never reaches memory."""
+    _require_class(rlk, RnsHybridKey, "mul_ciphertexts_hybrid_rescale")
+    assert ct1.logq == ct2.logq, "logq mismatch in hybrid multiplication"
+    q_last = ct1.c0.basis.moduli()[-1]
+    bits_dropped = q_last.bit_length()
+    new_basis = ct1.c0.basis.drop_last(1)
+    out0, out1 = ct1.c0._like(new_basis), ct1.c0._like(new_basis)
+    check(load().rnt_ct_mul_relin_rescale_hybrid(out0.handle, out1.handle, ct1.c0.handle, ct1.c1.handle,
+                                                 ct2.c0.handle, ct2.c1.handle, rlk.a.handle, rlk.b.handle,
+                                                 rlk.alpha))
+    return Ciphertext(out0, out1, ct1.logp + ct2.logp - bits_dropped, ct1.logq - bits_dropped)
+
+
+def linear_transform_bsgs_hybrid_rescale(ct: Ciphertext, diag: RnsPoly, baby_keyset: RnsHybridKeySet,
+                                         giant_keyset: RnsHybridKeySet) -> Ciphertext:
+    """:func:`linear_transform_bsgs_hybrid` then rescale_ciphertext as one op
+    (rnt_ct_linear_bsgs_hybrid_rescale): equal word for word to the two
+    calls, the closing ModDowns and the rescale in one kernel each."""
+    _require_hybrid_set(baby_keyset, True, "linear_transform_bsgs_hybrid_rescale (baby keys)")
+    _require_hybrid_set(giant_keyset, False, "linear_transform_bsgs_hybrid_rescale (giant keys)")
+    if baby_keyset.alpha != giant_keyset.alpha:
+        raise ValueError("linear_transform_bsgs_hybrid_rescale: the two key sets were generated for different alpha")
+    q_last = ct.c0.basis.moduli()[-1]
+    bits_dropped = q_last.bit_length()
+    new_basis = ct.c0.basis.drop_last(1)
+    out0, out1 = ct.c0._like(new_basis), ct.c0._like(new_basis)
+    baby = (ctypes.c_int32 * len(baby_keyset.steps))(*baby_keyset.steps)
+    giant = (ctypes.c_int32 * len(giant_keyset.steps))(*giant_keyset.steps)
+
+    def h(p):
+        return p.handle if p is not None else None
+
+    check(load().rnt_ct_linear_bsgs_hybrid_rescale(out0.handle, out1.handle, ct.c0.handle, ct.c1.handle, baby,
+                                                   len(baby_keyset.steps), giant, len(giant_keyset.steps),
+                                                   diag.handle, h(baby_keyset.a), h(baby_keyset.b),
+                                                   h(giant_keyset.a), h(giant_keyset.b), baby_keyset.alpha))
+    return Ciphertext(out0, out1, ct.logp - bits_dropped, ct.logq - bits_dropped)
 
 
 def rescale_ciphertext(ct: Ciphertext) -> Ciphertext:

@@ -157,6 +157,9 @@ SIGNATURES = {
     "rnt_ct_rotate_hybrid_hoisted": (c_int, [_P, _P, _P, _P, POINTER(c_int32), c_size_t, _P, _P, c_size_t]),
     "rnt_ct_linear_bsgs_hybrid": (c_int, [_P, _P, _P, _P, POINTER(c_int32), c_size_t, POINTER(c_int32), c_size_t,
                                           _P, _P, _P, _P, _P, c_size_t]),
+    "rnt_ct_mul_relin_rescale_hybrid": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_size_t]),
+    "rnt_ct_linear_bsgs_hybrid_rescale": (c_int, [_P, _P, _P, _P, POINTER(c_int32), c_size_t, POINTER(c_int32),
+                                                  c_size_t, _P, _P, _P, _P, _P, c_size_t]),
     "rnt_copy_polys": (c_int, [_P, c_size_t, _P, c_size_t, c_size_t]),
     "rnt_ct_rescale": (c_int, [_P, _P, _P, _P]),
     "rnt_encode": (c_int, [_P, c_void_p, c_size_t, c_uint32]),

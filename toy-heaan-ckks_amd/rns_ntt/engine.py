@@ -25,8 +25,9 @@ import numpy as np
 
 from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsGadgetKeySet, RnsHybridKey,
                RnsHybridKeySet, RnsPoly, bsgs_diagonal_rows, linear_transform, linear_transform_bsgs,
-               linear_transform_bsgs_hoisted, linear_transform_bsgs_hybrid, linear_transform_hybrid,
-               mul_ciphertexts_gadget, mul_ciphertexts_hybrid, rescale_ciphertext, rotate_ciphertext,
+               linear_transform_bsgs_hoisted, linear_transform_bsgs_hybrid, linear_transform_bsgs_hybrid_rescale,
+               linear_transform_hybrid, mul_ciphertexts_gadget, mul_ciphertexts_hybrid,
+               mul_ciphertexts_hybrid_rescale, rescale_ciphertext, rotate_ciphertext,
                rotate_ciphertext_hoisted, rotate_ciphertext_hybrid, rotate_ciphertext_hybrid_hoisted)
 
 
@@ -191,6 +192,7 @@ class CkksEngine:
 
     rotate_ciphertext_hybrid = staticmethod(rotate_ciphertext_hybrid)
     mul_ciphertexts_hybrid = staticmethod(mul_ciphertexts_hybrid)
+    mul_ciphertexts_hybrid_rescale = staticmethod(mul_ciphertexts_hybrid_rescale)
 
     def generate_hybrid_rotation_key_set(self, sk: RnsPoly, steps, rng, alpha: int,
                                          hoisted: bool = False) -> RnsHybridKeySet:
@@ -229,6 +231,17 @@ class CkksEngine:
         giants; logp grows by the diagonals' scale."""
         out = linear_transform_bsgs_hybrid(ct, diag_plaintexts.poly, baby_keyset, giant_keyset)
         out.logp = ct.logp + diag_plaintexts.scale_bits
+        return out
+
+    @staticmethod
+    def linear_transform_bsgs_hybrid_rescale(ct: Ciphertext, diag_plaintexts: Plaintext,
+                                             baby_keyset: RnsHybridKeySet,
+                                             giant_keyset: RnsHybridKeySet) -> Ciphertext:
+        """``linear_transform_bsgs_hybrid`` then ``rescale_ciphertext`` as one
+        op, word for word: logp grows by the diagonals' scale and drops, with
+        logq, by the bits of the limb rescaled away."""
+        out = linear_transform_bsgs_hybrid_rescale(ct, diag_plaintexts.poly, baby_keyset, giant_keyset)
+        out.logp += diag_plaintexts.scale_bits
         return out
 
     # -- encryption (engine.rs:84-127) -----------------------------------------
