@@ -52,6 +52,25 @@ def check_mul(c, key=None, ka=None, kb=None, Be=None):
     return fused
 
 
+def check_bsgs_rescale(c, polys=(0,)):
+    """The fused transform of a BsgsCase against the device composition on
+    every poly and against the yardstick on ``polys``."""
+    rn = c.rn
+    fused = rn.linear_transform_bsgs_hybrid_rescale(c.ct, c.d, c.bset, c.gset)
+    comp = rn.rescale_ciphertext(c.run())
+    for o in (fused.c0, fused.c1):
+        assert not o.is_ntt_domain() and o.n_polys == c.B and o.basis.channel_count() == c.Lv - 1
+    assert fused.c0.basis is fused.c1.basis and fused.logq == comp.logq
+    assert np.array_equal(fused.c0.channels(), comp.c0.channels()), "out0 differs from the composition"
+    assert np.array_equal(fused.c1.channels(), comp.c1.channels()), "out1 differs from the composition"
+    for p in polys:
+        r0, r1 = bsgs_hybrid_rescale_ref(c.Bc, c.Be, c.c0[p], c.c1[p], c.baby, c.giant, c.diag, c.bkeys, c.gkeys,
+                                         c.alpha)
+        assert np.array_equal(fused.c0.channels_of(p)[0], r0), f"out0 of poly {p} differs from the yardstick"
+        assert np.array_equal(fused.c1.channels_of(p)[0], r1), f"out1 of poly {p} differs from the yardstick"
+    return fused
+
+
 # log_n, Lv, K, alpha, B, bits, ws_mb, edge
 SHAPES = [
     (8, 3, 2, 2, 3, 31, None, False),    # small four-step grid, partial last digit
@@ -133,19 +152,8 @@ def test_bsgs_rescale_parity(gpu, log_n, giant):
     """[0, g]: the addend Z1 present; [g1, g2]: no step-0 giant (Z1 absent, S0
     from the first automorphism); [0]: no ModDown tail, k_rescale on the sums
     (linear_transform_hybrid's case)."""
-    rn = gpu
-    c = BsgsCase(rn, log_n, 3, 2, 2, 2, 31, baby=BABY, giant=giant, seed=len(giant) + giant[0])
-    fused = rn.linear_transform_bsgs_hybrid_rescale(c.ct, c.d, c.bset, c.gset)
-    comp = rn.rescale_ciphertext(c.run())
-    for o in (fused.c0, fused.c1):
-        assert not o.is_ntt_domain() and o.n_polys == c.B and o.basis.channel_count() == c.Lv - 1
-    assert fused.c0.basis is fused.c1.basis and fused.logq == comp.logq
-    assert np.array_equal(fused.c0.channels(), comp.c0.channels()), "out0 differs from the composition"
-    assert np.array_equal(fused.c1.channels(), comp.c1.channels()), "out1 differs from the composition"
-    if log_n == 8:
-        r0, r1 = bsgs_hybrid_rescale_ref(c.Bc, c.Be, c.c0[0], c.c1[0], c.baby, c.giant, c.diag, c.bkeys, c.gkeys,
-                                         c.alpha)
-        assert np.array_equal(fused.c0.channels_of(0)[0], r0) and np.array_equal(fused.c1.channels_of(0)[0], r1)
+    c = BsgsCase(gpu, log_n, 3, 2, 2, 2, 31, baby=BABY, giant=giant, seed=len(giant) + giant[0])
+    check_bsgs_rescale(c, polys=(0,) if log_n == 8 else ())
 
 
 def test_bsgs_rescale_chunked(gpu, monkeypatch):

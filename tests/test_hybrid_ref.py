@@ -13,8 +13,13 @@ from hybrid_ref import (crt_centered, digit_limbs, hybrid_key_plain, keyswitch_h
                         modup_ref, n_digits, restrict_key)
 
 N = 32
-# (Lv, K, bits)
-RINGS = [(3, 2, 31), (4, 2, 31), (3, 2, 61), (5, 1, 31)]
+# (Lv, K, bits); the last six are the rings of tests/test_gpu_hybrid_tiers.py's
+# register tiers (Lv = alpha + 1, K = alpha at alpha = 5, 9, 17)
+RINGS = [(3, 2, 31), (4, 2, 31), (3, 2, 61), (5, 1, 31),
+         (6, 5, 31), (10, 9, 31), (18, 17, 31), (6, 5, 61), (10, 9, 61), (18, 17, 61)]
+# (alpha, K, bits) of the GPU tier matrix: both edges of every register tier of
+# k_modup / k_moddown and the generic form, with Lv = alpha + 1
+TIERS = [(a, a, bits) for a in (4, 5, 8, 9, 16, 17) for bits in (31, 61)]
 
 
 def _moduli(Lv, K, bits, n=N):
@@ -35,7 +40,7 @@ def test_modup_is_the_residue_plus_a_small_multiple_of_the_digit_modulus(Lv, K, 
     rng = np.random.default_rng(1)
     x = orc.uniform_poly(mod[:Lv], N, rng)
     x[:, 0] = [m - 1 for m in mod[:Lv]]  # the largest residues too
-    for alpha in sorted({1, 2, Lv}):
+    for alpha in sorted({1, 2, Lv} | {a for a in (5, 9, 17) if a < Lv}):
         for d in range(n_digits(Lv, alpha)):
             I = list(digit_limbs(Lv, alpha, d))
             Qd = 1
@@ -53,6 +58,14 @@ def test_modup_is_the_residue_plus_a_small_multiple_of_the_digit_modulus(Lv, K, 
                 assert r == 0 and 0 <= u < len(I), (alpha, d, c, u, r)
 
 
+def _below(rng, M):
+    """A draw from [0, M) whose bits reach the top of M (M of any size)."""
+    v = 0
+    for _ in range(M.bit_length() // 62 + 2):
+        v = (v << 62) | int(rng.integers(0, 1 << 62))
+    return v % M
+
+
 @pytest.mark.parametrize("Lv,K,bits", RINGS)
 def test_moddown_divides_by_p(Lv, K, bits):
     """A = P m + r with 0 <= r < P: the fast conversion of [A]_P is r + v P with
@@ -65,8 +78,8 @@ def test_moddown_divides_by_p(Lv, K, bits):
     P = 1
     for p in mod[Lv:]:
         P *= p
-    ms = [int(rng.integers(0, 1 << 62)) * int(rng.integers(0, 1 << 62)) % Q for _ in range(N)]
-    rs = [int(rng.integers(0, 1 << 62)) * int(rng.integers(0, 1 << 62)) % P for _ in range(N)]
+    ms = [_below(rng, Q) for _ in range(N)]
+    rs = [_below(rng, P) for _ in range(N)]
     ms[0], rs[0] = Q - 1, P - 1
     ms[1], rs[1] = 0, 0
     A = np.array([[(P * m + r) % int(q) for m, r in zip(ms, rs)] for q in mod], dtype=np.uint64)
@@ -76,6 +89,37 @@ def test_moddown_divides_by_p(Lv, K, bits):
         v = (ms[c] - got[c]) % Q
         assert 0 <= v < K, (c, v)
     assert got[1] == 0
+
+
+@pytest.mark.parametrize("alpha,K,bits", TIERS)
+def test_plain_key_of_one_switches_to_the_input(alpha, K, bits):
+    """key_b = the plaintexts G_d of the target 1 (limb t of G_d is [P]_{q_t}
+    on the digit's own limbs, zero elsewhere), key_a = 0: A0 = P x on the
+    ciphertext limbs and 0 on the special ones, so z = 0 and the key-switch
+    returns (x, 0) exactly -- for a random x and for the all-(q - 1) one.  The
+    GPU tier tests assert the same identity on the device."""
+    Lv = alpha + 1
+    mod = _moduli(Lv, K, bits)
+    Be = orc.Basis(mod, N)
+    one = np.zeros((Lv, N), dtype=np.uint64)
+    one[:, 0] = 1
+    key_b = hybrid_key_plain(mod, Lv, alpha, one)
+    assert key_b.shape == (2, Lv + K, N)
+    P = 1
+    for p in mod[Lv:]:
+        P *= p
+    for d in range(2):  # one-hot rows: [P]_{q_t} at coefficient 0 of the digit's limbs, zero elsewhere
+        want = np.zeros((Lv + K, N), dtype=np.uint64)
+        for t in digit_limbs(Lv, alpha, d):
+            want[t, 0] = P % mod[t]
+        assert np.array_equal(key_b[d], want)
+    key_a = np.zeros_like(key_b)
+    rng = np.random.default_rng(3 * alpha + bits)
+    x = orc.uniform_poly(mod[:Lv], N, rng)
+    top = np.broadcast_to(np.array(mod[:Lv], dtype=np.uint64)[:, None] - np.uint64(1), (Lv, N)).copy()
+    for v in (x, top):
+        acc0, acc1 = keyswitch_hybrid_ref(Be, Lv, v, key_a, key_b, alpha)
+        assert np.array_equal(acc0, v) and not acc1.any()
 
 
 def _log2(v):
