@@ -35,9 +35,20 @@
 //   T = (C_0 + 2^8 C_1) + 2^16 (C_2 + 2^8 C_3),  |T| < 2^46,
 //   r' = (T + m q) / 2^32,  m = T (-q^-1) mod 2^32  (signed Montgomery),
 // gives r' = sum_k W[j][k] x_k mod q in (-q/2 - 2^14, q/2 + 2^14), which packs
-// again (the +0x80808080 rides in the reduction's 64-bit addend).  About 7
-// VALU instructions per word per pass (10 with a twist) instead of 22 for
-// four radix-2 CT stages; the MFMAs (4 per 256 words) run beside them.
+// again (the +0x80808080 rides in the reduction's 64-bit addend).
+// A pass that ends in a twist t (forward passes 1, 2: the twist the next
+// pass's F needs; inverse passes 3, 2) reduces twice, r' then r' t' with
+// t' = centred(t 2^32 mod q) (mont<true>), or -- folded, RNT_MF_FOLD3 /
+// RNT_MF_FOLD4 -- once: with lo = C_0 + 2^8 C_1, hi = C_2 + 2^8 C_3,
+//   x = (lo tA + hi tB + m q) / 2^32,  tA = centred(t),  tB = centred(t 2^16)
+// is congruent to r' t' 2^-32, |lo tA + hi tB| < 2^59.1 and |x| < 0.563 q
+// (recomb_tw), which packs as well.
+// Counted in the gfx950 code (profiles/mf_twist_fold_isa.txt): 7 VALU
+// instructions per word for a pass's recombination (6 where the word is not
+// packed again), 10 with a two-step twist, 7 with a folded one; k_mf_mul, 12
+// passes a product, runs 9.9 per word per pass all told (10.65 with every
+// twist in two steps), instead of 22 for four radix-2 CT stages; the MFMAs
+// (4 per 256 words) run beside them.
 //
 // ---- layouts -----------------------------------------------------------------
 // One 1024-thread workgroup per (poly, limb) plane, 64 words a thread as 16
@@ -112,7 +123,41 @@ constexpr int kTw3i = kTw4i + 16384;      // [w][c][g]: inverse pass 2 twist, Q3
 // offsets before it stay as they were: moving them cost hipcc SGPRs and
 // 170 bytes a lane of spills in k_mf_mul)
 constexpr int S_F4S = (kTw3i + 1024 + 255) / 256;
-constexpr int kLimb = (S_F4S + 1) * 256;
+// RNT_MF_FOLD3 / RNT_MF_FOLD4: the twist after a pass folded into its digit
+// recombination (recomb_tw), for the passes whose twists come from the small
+// tables (pass_p2, ipass_p3: kTw3f, kTw3i) and from the large ones (pass_p3,
+// ipass_p4: kTw4f, kTw4i).  A folded family reads two plain (non-Montgomery)
+// tables, A = centred(t) and B = centred(t 2^16), in the order of its single
+// table and in regions of their own past S_F4S (again so that no offset
+// before them moves), B one table's length past A: both loads of a tile share
+// the lane offset and differ by a constant in the scalar offset.  The single
+// table of a folded family is left unwritten (but kTw3f: kFold3Fwd).
+// Measured (profiles/ab_mf_twist_fold.txt, the poly-mul, same box): fold 3
+// +2.0..2.5%, fold 4 -1.2..-2.0% alone and -0.8..-1.0% on top of fold 3 (the
+// second read of a 256 KiB table with an entry per lane costs more than the
+// three VALU instructions a word it saves), so fold 3 is on and fold 4 off.
+#ifndef RNT_MF_FOLD3
+#define RNT_MF_FOLD3 1
+#endif
+#ifndef RNT_MF_FOLD4
+#define RNT_MF_FOLD4 0
+#endif
+constexpr bool kFold3 = RNT_MF_FOLD3 != 0, kFold4 = RNT_MF_FOLD4 != 0;
+constexpr int kFoldBase = (S_F4S + 1) * 256;
+constexpr int kTwB3 = 1024, kTwB4 = 16384;  // A -> B distance of a family (its table length)
+constexpr int kTw3fA = kFoldBase, kTw3iA = kTw3fA + 2 * kTwB3;
+constexpr int kFold4Base = kFoldBase + (kFold3 ? 4 * kTwB3 : 0);
+constexpr int kTw4fA = kFold4Base, kTw4iA = kTw4fA + 2 * kTwB4;
+constexpr int kLimb = kFold4Base + (kFold4 ? 4 * kTwB4 : 0);
+// where the passes read their twists (the A table when folded)
+constexpr int kTw3iR = kFold3 ? kTw3iA : kTw3i;
+constexpr int kTw4fR = kFold4 ? kTw4fA : kTw4f, kTw4iR = kFold4 ? kTw4iA : kTw4i;
+// The standalone forward (k_mf_ntt<false>) keeps the two-step twist after
+// pass 1 and reads kTw3f, which is therefore always written: it spills
+// nothing, and with that twist folded it spilled 20 bytes a lane over the
+// pass's second half in every order of the loads tried (the forwards of
+// k_mf_mul and k_mf_tensor do fold it, and spill less than before).
+constexpr bool kFold3Fwd = false;
 // LDS: the P1 <-> P2 exchange (128 KiB: half a plane per round) and the
 // inverse's stash (10 KiB a wave); one workgroup per CU either way
 constexpr size_t kLdsBytes = (size_t)160 * 1024;
@@ -224,6 +269,60 @@ __device__ __forceinline__ int32_t mont(int32_t a, int32_t b, const Mc& m) {
   const uint32_t mm = (uint32_t)p * m.nqinv;
   const int64_t v = (int64_t)(int32_t)mm * m.q + p;
   return (int32_t)(v >> 32);
+}
+// Recombination and twist in one reduction: with T = lo + 2^16 hi the digit
+// sums' word (lo = C_0 + 2^8 C_1, hi = C_2 + 2^8 C_3) and t the twist,
+// (lo twA + hi twB) 2^-32 = T t 2^-32 mod q for twA = centred(t), twB =
+// centred(t 2^16) -- the word recomb<false> then mont<true> by
+// centred(t 2^32) give, as another representative of the same residue --
+// + 0x80808080 (then ^ K32 packs it).  |lo|, |hi| <= 2^28 + 2^20 and |twA|,
+// |twB| <= q/2 give |p| < 2^59.1 and
+//   |x| < (2^28 + 2^20) q / 2^32 + q/2 + 1 < 0.563 q,
+// inside the packed range (mf_build checks it per prime;
+// tests/test_mf_twist_fold.py is the integer model).  The bias K rides in
+// the first multiply-add's addend as in mont<true>; both are asm for the
+// reason given there.  (It takes the halves, not the four digit sums: the
+// caller forms them before it loads the twists, twist4.)
+__device__ __forceinline__ int32_t recomb_tw(int32_t lo, int32_t hi, int32_t twA, int32_t twB, const Mc& m) {
+  int64_t p0, p;
+  uint64_t cc;
+  asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(p0), "=s"(cc) : "v"(lo), "v"(twA), "s"(m.K));
+  asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(p), "=s"(cc) : "v"(hi), "v"(twB), "v"(p0));
+  const uint32_t mm = (uint32_t)p * m.nqinv;
+  const int64_t v = (int64_t)(int32_t)mm * m.q + p;
+  return (int32_t)(v >> 32);
+}
+// A folded pass's tile: its four output words, packed, into o.  The B
+// twists load here (scalar offset tsb), and with LATE the A twists too (tsa;
+// else ta holds them), once the sixteen digit sums have shrunk to the eight
+// halves: the digit sums' registers take them.  Loaded ahead of the tile
+// beside ta, the B twists cost every kernel 16 to 52 bytes a lane of spills;
+// with both loaded here k_mf_mul and the inverse transform spill nothing
+// (20 bytes a lane each before).
+template <bool LATE>
+__device__ __forceinline__ void twist4(uint32_t (&o)[4], const v4i (&D)[4], v4i ta, Rsrc tab, uint32_t tvo,
+                                       uint32_t tsa, uint32_t tsb, const Mc& m) {
+  int32_t lo[4], hi[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    lo[i] = D[0][i] + (int32_t)((uint32_t)D[1][i] << 8);
+    hi[i] = D[2][i] + (int32_t)((uint32_t)D[3][i] << 8);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (LATE) ta = bld(tab, tvo, tsa);
+  const v4i tb = bld(tab, tvo, tsb);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) o[i] = (uint32_t)recomb_tw(lo[i], hi[i], ta[i], tb[i], m) ^ K32;
+}
+// The scalar offset of a folded pass's B table (DIST v4i past its A table at
+// tso), as an opaque value: of the plain sums tso + constant hipcc keeps one
+// per tile in SGPRs from one transform of a kernel to the next (the same
+// wave, so the same sums), spilled to the lanes of a VGPR the passes need.
+template <int DIST>
+__device__ __forceinline__ uint32_t tw_b(uint32_t tso) {
+  uint32_t v = tso + (uint32_t)DIST * 16u;
+  asm volatile("" : "+s"(v));
+  return v;
 }
 // The end of one tile's work: hipcc would otherwise hoist later tiles'
 // MFMAs and loads above it and keep their digit sums live (spills).
@@ -571,10 +670,11 @@ __device__ __forceinline__ void pass_p1(uint32_t (&x1)[64], const v4i (&M)[4], v
   }
 }
 // pass 1 (per-wave matrix) on P2 chunks [C0, C0 + 8), then the pass-2 twist
-// (TW: the table in P2 positions).
-template <int C0>
+// (the table in P2 positions; FOLD: its A table, the twist folded).
+template <int C0, bool FOLD>
 __device__ __forceinline__ void pass_p2(uint32_t (&x2)[64], const v4i (&M)[4], Rsrc tab, uint32_t tvo, uint32_t tso,
                                         const Mc& m) {
+  const uint32_t tsb = FOLD ? tw_b<kTwB3>(tso) : tso;
   const v4i z = {0, 0, 0, 0};
 #pragma unroll
   for (int c = C0; c < C0 + 8; ++c) {
@@ -583,14 +683,22 @@ __device__ __forceinline__ void pass_p2(uint32_t (&x2)[64], const v4i (&M)[4], R
 #pragma unroll
     for (int i = 0; i < 4; ++i) b[i] = (int)x2[4 * c + i];
     // (the twists of a 16 KiB table: cache hits, loaded at the tile -- a
-    // tile-ahead prefetch measured 4 more spilled registers)
-    const v4i tv = bld(tab, tvo, tso + (uint32_t)c * 16u);
+    // tile-ahead prefetch measured 4 more spilled registers; folded, both
+    // tables' load after it, twist4)
+    const v4i tv = FOLD ? z : bld(tab, tvo, tso + (uint32_t)c * 16u);
     v4i D[4];
     tile<false, false>(D, M, b, z);
+    if constexpr (FOLD) {
+      uint32_t o[4];
+      twist4<true>(o, D, tv, tab, tvo, tso + (uint32_t)c * 16u, tsb + (uint32_t)c * 16u, m);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int32_t r = recomb<false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
-      x2[4 * c + i] = (uint32_t)mont<true>(r, tv[i], m) ^ K32;
+      for (int i = 0; i < 4; ++i) x2[4 * c + i] = o[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int32_t r = recomb<false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
+        x2[4 * c + i] = (uint32_t)mont<true>(r, tv[i], m) ^ K32;
+      }
     }
     pin4(x2[4 * c + 0], x2[4 * c + 1], x2[4 * c + 2], x2[4 * c + 3]);
     tile_fence();
@@ -599,6 +707,7 @@ __device__ __forceinline__ void pass_p2(uint32_t (&x2)[64], const v4i (&M)[4], R
 // pass 2 (F, data as A: P3 -> P4 positions), then the pass-3 twist.
 __device__ __forceinline__ void pass_p3(uint32_t (&x)[64], const v4i (&M)[4], Rsrc tab, uint32_t tvo, uint32_t tso,
                                         const Mc& m) {
+  const uint32_t tsb = kFold4 ? tw_b<kTwB4>(tso) : tso;
   const v4i z = {0, 0, 0, 0};
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
@@ -609,10 +718,17 @@ __device__ __forceinline__ void pass_p3(uint32_t (&x)[64], const v4i (&M)[4], Rs
     const v4i tv = bld(tab, tvo, tso + (uint32_t)c * 1024u);
     v4i D[4];
     tile<true, false>(D, M, a, z);
+    if constexpr (kFold4) {
+      uint32_t o[4];
+      twist4<false>(o, D, tv, tab, tvo, 0, tsb + (uint32_t)c * 1024u, m);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int32_t r = recomb<false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
-      x[p3(c, i)] = (uint32_t)mont<true>(r, tv[i], m) ^ K32;
+      for (int i = 0; i < 4; ++i) x[p3(c, i)] = o[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int32_t r = recomb<false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
+        x[p3(c, i)] = (uint32_t)mont<true>(r, tv[i], m) ^ K32;
+      }
     }
     pin4(x[p3(c, 0)], x[p3(c, 1)], x[p3(c, 2)], x[p3(c, 3)]);
     tile_fence();
@@ -665,6 +781,7 @@ __device__ __forceinline__ v4i stash_get(uint32_t addr, int c) {
 template <bool PK = false>
 __device__ __forceinline__ void ipass_p4(uint32_t (&x)[64], const v4i (&M)[4], v4i comp, v4i tv, Rsrc tab,
                                          uint32_t tvo, uint32_t tso, const Mc& m, uint32_t* lds, const Th& h) {
+  const uint32_t tsb = kFold4 ? tw_b<kTwB4>(tso) : tso;
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
     mf_prio<RNT_MF_IPRIO != 0>(c);
@@ -677,10 +794,17 @@ __device__ __forceinline__ void ipass_p4(uint32_t (&x)[64], const v4i (&M)[4], v
       tile<true, false>(D, M, a, v4i{0, 0, 0, 0});
     else
       tile<true, true>(D, M, a, comp);
+    if constexpr (kFold4) {
+      uint32_t o[4];
+      twist4<false>(o, D, tv, tab, tvo, 0, tsb + (uint32_t)c * 1024u, m);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int32_t r = recomb<false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
-      x[p3(c, i)] = (uint32_t)mont<true>(r, tv[i], m) ^ K32;
+      for (int i = 0; i < 4; ++i) x[p3(c, i)] = o[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int32_t r = recomb<false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
+        x[p3(c, i)] = (uint32_t)mont<true>(r, tv[i], m) ^ K32;
+      }
     }
     if (c < kStash)
       stash_put(stash_addr(lds, h), c, x[p3(c, 0)], x[p3(c, 1)], x[p3(c, 2)], x[p3(c, 3)]);
@@ -693,6 +817,7 @@ __device__ __forceinline__ void ipass_p4(uint32_t (&x)[64], const v4i (&M)[4], v
 // inverse pass 2 (F^-1 in Q3), then its twist; packed output.
 __device__ __forceinline__ void ipass_p3(uint32_t (&x)[64], const v4i (&M)[4], Rsrc tab, uint32_t tvo, uint32_t tso,
                                          const Mc& m, uint32_t* lds, const Th& h) {
+  const uint32_t tsb = kFold3 ? tw_b<kTwB3>(tso) : tso;
   const v4i z = {0, 0, 0, 0};
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
@@ -704,13 +829,20 @@ __device__ __forceinline__ void ipass_p3(uint32_t (&x)[64], const v4i (&M)[4], R
 #pragma unroll
       for (int i = 0; i < 4; ++i) b[i] = (int)x[p3(c, i)];
     }
-    const v4i tv = bld(tab, tvo, tso + (uint32_t)c * 64u);
+    const v4i tv = kFold3 ? z : bld(tab, tvo, tso + (uint32_t)c * 64u);
     v4i D[4];
     tile<false, false>(D, M, b, z);
+    if constexpr (kFold3) {
+      uint32_t o[4];
+      twist4<true>(o, D, tv, tab, tvo, tso + (uint32_t)c * 64u, tsb + (uint32_t)c * 64u, m);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int32_t r = recomb<false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
-      x[p3(c, i)] = (uint32_t)mont<true>(r, tv[i], m) ^ K32;
+      for (int i = 0; i < 4; ++i) x[p3(c, i)] = o[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int32_t r = recomb<false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
+        x[p3(c, i)] = (uint32_t)mont<true>(r, tv[i], m) ^ K32;
+      }
     }
     pin4(x[p3(c, 0)], x[p3(c, 1)], x[p3(c, 2)], x[p3(c, 3)]);
     tile_fence();
@@ -831,13 +963,14 @@ struct NoEpi {
 // the LDS at byte PBASE + wave * PSTRIDE from SYNCX to the P2 -> P3 swap,
 // instead of being spilled to scratch memory (whose write-back is HBM
 // traffic); the caller guarantees no other wave touches that LDS then.
+// F3: pass 1's twist folded (not in the standalone forward, kFold3Fwd).
 template <int NPARK, uint32_t PBASE, uint32_t PSTRIDE>
 __device__ __forceinline__ uint32_t park_addr(const uint32_t* lds, const Th& h) {
   static_assert(NPARK * 1024 <= (int)PSTRIDE && PBASE + 16 * PSTRIDE <= kLdsBytes, "park area");
   return (uint32_t)(uintptr_t)lds + PBASE + h.w * PSTRIDE + h.lam() * 16u;
 }
 template <bool SYNC1, int F4 = S_F4, bool Q4 = false, bool SYNCX = false, int NPARK = 0, uint32_t PBASE = 0,
-          uint32_t PSTRIDE = 0, class EPI = NoEpi>
+          uint32_t PSTRIDE = 0, bool F3 = kFold3, class EPI = NoEpi>
 __device__ __forceinline__ void fwd(uint32_t (&x2)[64], Rsrc src, uint32_t* lds, const Th& h, const Tabs& T,
                                     const EPI& epi = EPI{}) {
   // the first pass's operands load ahead of the plane (cache hits, needed
@@ -854,7 +987,7 @@ __device__ __forceinline__ void fwd(uint32_t (&x2)[64], Rsrc src, uint32_t* lds,
   MF_STAMP(2);
   if constexpr (SYNC1) __syncthreads();
   uint32_t wb[4], rb[4];
-  const uint32_t t3v = h.g() * 256u, t3s = (uint32_t)(kTw3f + h.w * 64) * 16u;
+  const uint32_t t3v = h.g() * 256u, t3s = (uint32_t)((F3 ? kTw3fA : kTw3f) + h.w * 64) * 16u;
   if constexpr (Q4) {
     p1_bases4(wb, h);
     x_write_p1q<0>(x1, lds, wb);
@@ -872,7 +1005,7 @@ __device__ __forceinline__ void fwd(uint32_t (&x2)[64], Rsrc src, uint32_t* lds,
     p1_bases4(wb, h);
     x_write_p1q<2>(x1, lds, wb);
     load_mat(M, T.tab, S_F2 + h.w, lo);
-    pass_p2<0>(x2, M, T.tab, t3v, t3s, m);
+    pass_p2<0, F3>(x2, M, T.tab, t3v, t3s, m);
     __syncthreads();
     p2_bases4(rb, h);
     x_read_p2q<2>(x2, lds, rb);
@@ -896,7 +1029,7 @@ __device__ __forceinline__ void fwd(uint32_t (&x2)[64], Rsrc src, uint32_t* lds,
   p1_bases(wb, h);
   x_write_p1<1>(x1, lds, wb);
   load_mat(M, T.tab, S_F2 + h.w, lo);
-  pass_p2<0>(x2, M, T.tab, t3v, t3s, m);
+  pass_p2<0, F3>(x2, M, T.tab, t3v, t3s, m);
   MF_STAMP(6);
   __syncthreads();
   MF_STAMP(7);
@@ -908,7 +1041,7 @@ __device__ __forceinline__ void fwd(uint32_t (&x2)[64], Rsrc src, uint32_t* lds,
 #pragma unroll
   for (int c = 0; c < NPARK; ++c)
     stash_put(park_addr<NPARK, PBASE, PSTRIDE>(lds, h), c, x2[4 * c], x2[4 * c + 1], x2[4 * c + 2], x2[4 * c + 3]);
-  pass_p2<8>(x2, M, T.tab, t3v, t3s, m);
+  pass_p2<8, F3>(x2, M, T.tab, t3v, t3s, m);
   MF_STAMP(8);
 #pragma unroll
   for (int c = 0; c < NPARK; ++c) {
@@ -918,7 +1051,7 @@ __device__ __forceinline__ void fwd(uint32_t (&x2)[64], Rsrc src, uint32_t* lds,
   }
   swap_p2p3(x2);
   load_mat(M, T.tab, S_F3, lo);
-  pass_p3(x2, M, T.tab, lo, (uint32_t)(kTw4f + h.w * 1024) * 16u, m);
+  pass_p3(x2, M, T.tab, lo, (uint32_t)(kTw4fR + h.w * 1024) * 16u, m);
   MF_STAMP(9);
   load_mat(M, T.tab, F4, lo);
   pass_p4(x2, M, m, epi);
@@ -941,7 +1074,7 @@ __device__ __forceinline__ void inv_x(uint32_t (&x2)[64], Rsrc pr, uint32_t* lds
   v4i M[4];
   load_mat(M, T.tab, S_I4, lo);
   const v4i comp = bld(T.tab, lo, (uint32_t)kCompI4 * 16u);
-  const uint32_t t4s = (uint32_t)(kTw4i + h.w * 1024) * 16u;
+  const uint32_t t4s = (uint32_t)(kTw4iR + h.w * 1024) * 16u;
   const v4i tv0 = bld(T.tab, lo, t4s);
   if constexpr (LOAD) {
 #pragma unroll
@@ -955,7 +1088,7 @@ __device__ __forceinline__ void inv_x(uint32_t (&x2)[64], Rsrc pr, uint32_t* lds
   }
   ipass_p4<PK>(x2, M, comp, tv0, T.tab, lo, t4s, m, lds, h);
   load_mat(M, T.tab, S_I3, lo);
-  ipass_p3(x2, M, T.tab, h.g() * 16u, (uint32_t)(kTw3i + h.w * 64) * 16u, m, lds, h);
+  ipass_p3(x2, M, T.tab, h.g() * 16u, (uint32_t)(kTw3iR + h.w * 64) * 16u, m, lds, h);
   swap_q3p2(x2);
   load_mat(M, T.tab, S_I2 + h.w, lo);
   uint32_t wb[4], rb[4];
@@ -983,156 +1116,6 @@ __device__ __forceinline__ void inv(Rsrc pr, uint32_t* lds, const Th& h, const T
   inv_x<true>(x2, pr, lds, h, T);
 }
 
-// ---- two virtual waves a wave (k_mf_mul2) -----------------------------------
-// fwd and inv_x for a 512-thread workgroup whose wave p carries the sixteen-
-// wave layout's waves 2p (ha, xa) and 2p + 1 (hb, xb): every pass runs once
-// for each, the barriers once for both.  The per-wave state of the 1024-thread
-// layout (x, a^, the VGPRs of the working set) is then held by half as many
-// threads, and the register file left over keeps a^ tiles on the CU.
-template <bool SYNC1, int F4, bool Q4, bool SYNCX, int NPARK, uint32_t PBASE, uint32_t PSTRIDE, class EA, class EB>
-__device__ __forceinline__ void fwd2(uint32_t (&xa)[64], uint32_t (&xb)[64], Rsrc src, uint32_t* lds, const Th& ha,
-                                     const Th& hb, const Tabs& T, const EA& epa, const EB& epb) {
-  const Mc& m = T.m;
-  const uint32_t lo = ha.lam() * 16u;
-  v4i M[4];
-  load_mat(M, T.tab, S_F1, lo);
-  const v4i comp = bld(T.tab, lo, (uint32_t)kCompF1 * 16u);
-  uint32_t x1a[64], x1b[64];
-  load_p1(x1a, src, ha);
-  load_p1(x1b, src, hb);
-  pass_p1<0, true>(x1a, M, comp, m);
-  pass_p1<0, true>(x1b, M, comp, m);
-  if constexpr (SYNC1) __syncthreads();
-  uint32_t wb[4], rb[4];
-  const uint32_t t3v = ha.g() * 256u;
-  auto t3s = [](const Th& h) { return (uint32_t)(kTw3f + h.w * 64) * 16u; };
-  if constexpr (Q4) {
-    p1_bases4(wb, ha); x_write_p1q<0>(x1a, lds, wb);
-    p1_bases4(wb, hb); x_write_p1q<0>(x1b, lds, wb);
-    pass_p1<8, true>(x1a, M, comp, m);
-    pass_p1<8, true>(x1b, M, comp, m);
-    __syncthreads();
-    p2_bases4(rb, ha); x_read_p2q<0>(xa, lds, rb);
-    p2_bases4(rb, hb); x_read_p2q<0>(xb, lds, rb);
-    __syncthreads();
-    p1_bases4(wb, ha); x_write_p1q<1>(x1a, lds, wb);
-    p1_bases4(wb, hb); x_write_p1q<1>(x1b, lds, wb);
-    __syncthreads();
-    p2_bases4(rb, ha); x_read_p2q<1>(xa, lds, rb);
-    p2_bases4(rb, hb); x_read_p2q<1>(xb, lds, rb);
-    __syncthreads();
-    p1_bases4(wb, ha); x_write_p1q<2>(x1a, lds, wb);
-    p1_bases4(wb, hb); x_write_p1q<2>(x1b, lds, wb);
-    load_mat(M, T.tab, S_F2 + ha.w, lo);
-    pass_p2<0>(xa, M, T.tab, t3v, t3s(ha), m);
-    load_mat(M, T.tab, S_F2 + hb.w, lo);
-    pass_p2<0>(xb, M, T.tab, t3v, t3s(hb), m);
-    __syncthreads();
-    p2_bases4(rb, ha); x_read_p2q<2>(xa, lds, rb);
-    p2_bases4(rb, hb); x_read_p2q<2>(xb, lds, rb);
-    __syncthreads();
-    p1_bases4(wb, ha); x_write_p1q<3>(x1a, lds, wb);
-    p1_bases4(wb, hb); x_write_p1q<3>(x1b, lds, wb);
-    __syncthreads();
-    p2_bases4(rb, ha); x_read_p2q<3>(xa, lds, rb);
-    p2_bases4(rb, hb); x_read_p2q<3>(xb, lds, rb);
-  } else {
-    p1_bases(wb, ha); x_write_p1<0>(x1a, lds, wb);
-    p1_bases(wb, hb); x_write_p1<0>(x1b, lds, wb);
-    pass_p1<8, true>(x1a, M, comp, m);
-    pass_p1<8, true>(x1b, M, comp, m);
-    __syncthreads();
-    p2_bases(rb, ha); x_read_p2<0>(xa, lds, rb);
-    p2_bases(rb, hb); x_read_p2<0>(xb, lds, rb);
-    __syncthreads();
-    p1_bases(wb, ha); x_write_p1<1>(x1a, lds, wb);
-    p1_bases(wb, hb); x_write_p1<1>(x1b, lds, wb);
-    load_mat(M, T.tab, S_F2 + ha.w, lo);
-    pass_p2<0>(xa, M, T.tab, t3v, t3s(ha), m);
-    load_mat(M, T.tab, S_F2 + hb.w, lo);
-    pass_p2<0>(xb, M, T.tab, t3v, t3s(hb), m);
-    __syncthreads();
-    p2_bases(rb, ha); x_read_p2<1>(xa, lds, rb);
-    p2_bases(rb, hb); x_read_p2<1>(xb, lds, rb);
-  }
-  if constexpr (SYNCX) __syncthreads();
-  static_assert(NPARK == 0 || SYNCX, "the park area is free only past SYNCX");
-#pragma unroll
-  for (int c = 0; c < NPARK; ++c) {
-    stash_put(park_addr<NPARK, PBASE, PSTRIDE>(lds, ha), c, xa[4 * c], xa[4 * c + 1], xa[4 * c + 2], xa[4 * c + 3]);
-    stash_put(park_addr<NPARK, PBASE, PSTRIDE>(lds, hb), c, xb[4 * c], xb[4 * c + 1], xb[4 * c + 2], xb[4 * c + 3]);
-  }
-  load_mat(M, T.tab, S_F2 + ha.w, lo);
-  pass_p2<8>(xa, M, T.tab, t3v, t3s(ha), m);
-  load_mat(M, T.tab, S_F2 + hb.w, lo);
-  pass_p2<8>(xb, M, T.tab, t3v, t3s(hb), m);
-#pragma unroll
-  for (int c = 0; c < NPARK; ++c) {
-    const v4i va = stash_get(park_addr<NPARK, PBASE, PSTRIDE>(lds, ha), c);
-    const v4i vb = stash_get(park_addr<NPARK, PBASE, PSTRIDE>(lds, hb), c);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      xa[4 * c + i] = (uint32_t)va[i];
-      xb[4 * c + i] = (uint32_t)vb[i];
-    }
-  }
-  swap_p2p3(xa);
-  swap_p2p3(xb);
-  load_mat(M, T.tab, S_F3, lo);
-  pass_p3(xa, M, T.tab, lo, (uint32_t)(kTw4f + ha.w * 1024) * 16u, m);
-  pass_p3(xb, M, T.tab, lo, (uint32_t)(kTw4f + hb.w * 1024) * 16u, m);
-  load_mat(M, T.tab, F4, lo);
-  pass_p4(xa, M, m, epa);
-  pass_p4(xb, M, m, epb);
-}
-
-// inv_x<false, true> for two virtual waves: the product (packed signed form,
-// P4 positions) in xa / xb to the canonical coefficients stored at pr.
-__device__ __forceinline__ void inv2(uint32_t (&xa)[64], uint32_t (&xb)[64], Rsrc pr, uint32_t* lds, const Th& ha,
-                                     const Th& hb, const Tabs& T) {
-  const Mc& m = T.m;
-  const uint32_t lo = ha.lam() * 16u;
-  v4i M[4];
-  load_mat(M, T.tab, S_I4, lo);
-  const v4i comp = {0, 0, 0, 0};  // (PK: no input bias)
-  auto t4s = [](const Th& h) { return (uint32_t)(kTw4i + h.w * 1024) * 16u; };
-  __syncthreads();  // ipass_p4's stash reuses the LDS of the last exchange and the a^ tiles
-  ipass_p4<true>(xa, M, comp, bld(T.tab, lo, t4s(ha)), T.tab, lo, t4s(ha), m, lds, ha);
-  ipass_p4<true>(xb, M, comp, bld(T.tab, lo, t4s(hb)), T.tab, lo, t4s(hb), m, lds, hb);
-  load_mat(M, T.tab, S_I3, lo);
-  ipass_p3(xa, M, T.tab, ha.g() * 16u, (uint32_t)(kTw3i + ha.w * 64) * 16u, m, lds, ha);
-  ipass_p3(xb, M, T.tab, hb.g() * 16u, (uint32_t)(kTw3i + hb.w * 64) * 16u, m, lds, hb);
-  swap_q3p2(xa);
-  swap_q3p2(xb);
-  uint32_t wb[4], rb[4];
-  uint32_t x1a[64], x1b[64];
-  load_mat(M, T.tab, S_I2 + ha.w, lo);
-  ipass_p2<0>(xa, M, m);
-  load_mat(M, T.tab, S_I2 + hb.w, lo);
-  ipass_p2<0>(xb, M, m);
-  __syncthreads();  // every wave's stash reads are done
-  p2_bases(rb, ha); x_write_p2<0>(xa, lds, rb);
-  p2_bases(rb, hb); x_write_p2<0>(xb, lds, rb);
-  load_mat(M, T.tab, S_I2 + ha.w, lo);
-  ipass_p2<8>(xa, M, m);
-  load_mat(M, T.tab, S_I2 + hb.w, lo);
-  ipass_p2<8>(xb, M, m);
-  __syncthreads();
-  p1_bases(wb, ha); x_read_p1<0>(x1a, lds, wb);
-  p1_bases(wb, hb); x_read_p1<0>(x1b, lds, wb);
-  __syncthreads();
-  p2_bases(rb, ha); x_write_p2<1>(xa, lds, rb);
-  p2_bases(rb, hb); x_write_p2<1>(xb, lds, rb);
-  load_mat(M, T.tab, S_I1, lo);
-  ipass_p1<0>(x1a, M, m, pr, ha);
-  ipass_p1<0>(x1b, M, m, pr, hb);
-  __syncthreads();
-  p1_bases(wb, ha); x_read_p1<1>(x1a, lds, wb);
-  p1_bases(wb, hb); x_read_p1<1>(x1b, lds, wb);
-  ipass_p1<8>(x1a, M, m, pr, ha);
-  ipass_p1<8>(x1b, M, m, pr, hb);
-}
-
 }  // namespace mf
 
 // Standalone transforms in place (rnt_ntt_fwd / rnt_ntt_inv at N = 2^16),
@@ -1155,7 +1138,7 @@ k_mf_ntt(uint32_t* __restrict__ data, const void* __restrict__ mft, const LimbCo
     // the last pass stores each tile, canonical, in the device order (in
     // place: every wave read its words of the plane before the first
     // exchange's barrier)
-    fwd<false>(x, pr, lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) {
+    fwd<false, S_F4, false, false, 0, 0, 0, kFold3 && kFold3Fwd>(x, pr, lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) {
       bst<kStreamAux>(v4i{(int)canon(r[0], T.m.q), (int)canon(r[1], T.m.q), (int)canon(r[2], T.m.q), (int)canon(r[3], T.m.q)}, pr,
           p4_lane(h), p4_soff(h, cc));
     });
@@ -1322,15 +1305,6 @@ k_mf_tensor(uint32_t* __restrict__ d0, uint32_t* __restrict__ d1, uint32_t* __re
 #ifndef RNT_MF_MUL_MEAS_SKIP
 #define RNT_MF_MUL_MEAS_SKIP (RNT_MF_MUL_MEAS ? 16 - kMulLdsTiles : 0)
 #endif
-// RNT_MF_MUL_V2: rnt_mul at 2^16 runs k_mf_mul2 (512 threads, two virtual
-// waves a wave) instead of k_mf_mul.  Off: bit-identical, but two waves a
-// SIMD measured 11% slower at the same power (7.08 against 6.27 ms, the clock
-// 17% higher: issue-bound, not power-bound), and the registers it frees hold
-// about one a^ tile a virtual wave (+1.5%), not the ten that cost k_mf_mul
-// 7.8% (profiles/r06/ab_mf_mul2.txt, ab_mf_mul_ahat_ceiling.txt)
-#ifndef RNT_MF_MUL_V2
-#define RNT_MF_MUL_V2 0
-#endif
 constexpr int kMulLdsTiles = RNT_MF_MUL_Q4 ? 6 : 2;  // a^ tiles per wave kept in the LDS (k_mf_mul)
 constexpr uint32_t kMulLdsBase = RNT_MF_MUL_Q4 ? (1u << 14) : (1u << 15);  // words
 static_assert(kMulLdsBase * 4 + (size_t)kMulLdsTiles * 16 * 1024 <= mf::kLdsBytes, "in the LDS");
@@ -1399,80 +1373,6 @@ k_mf_mul(uint32_t* c, const uint32_t* a, const uint32_t* b, uint64_t ls, uint32_
     pin4(xx[p3(cc, 0)], xx[p3(cc, 1)], xx[p3(cc, 2)], xx[p3(cc, 3)]);
   });
   inv_x<false, true>(x, rsrc(c + o, kN * 4u), lds, h, T);
-}
-
-// RNT_MF_MUL2_REG: a^ tiles a virtual wave keeps in registers (k_mf_mul2):
-// tiles 10 - REG .. 9 (10 .. 15 stay in the LDS as in k_mf_mul; the first
-// 10 - REG go through the scratch slot)
-#ifndef RNT_MF_MUL2_REG
-#define RNT_MF_MUL2_REG 6
-#endif
-#ifndef RNT_MF_MUL2_PARK
-#define RNT_MF_MUL2_PARK 0
-#endif
-// k_mf_mul with 512 threads, each wave the two virtual waves 2p, 2p + 1 of
-// k_mf_mul's sixteen-wave layout (mf::fwd2 / inv2): the same plane
-// positions, LDS layout, tables and scratch slot indexing, so the same words
-// out; RNT_MF_MUL2_REG of the ten a^ tiles a virtual wave sent through the
-// scratch slot stay in registers instead.
-__global__ void __launch_bounds__(mf::kT / 2, 1)
-k_mf_mul2(uint32_t* c, const uint32_t* a, const uint32_t* b, uint64_t ls, uint32_t* __restrict__ scratch,
-          uint32_t slots, const void* __restrict__ mft, const LimbConst<uint32_t>* __restrict__ lcs) {
-  using namespace mf;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  uint32_t* lds = (uint32_t*)smem_raw;
-  // virtual thread ids: wave p's lane l is thread 128p + l of wave 2p and
-  // 128p + 64 + l of wave 2p + 1
-  const uint32_t tv = 2u * threadIdx.x - (threadIdx.x & 63u);
-  const Th ha(tv), hb(tv + 64u);
-  const uint32_t poly = blockIdx.x, l = blockIdx.y;
-  const uint64_t o = (uint64_t)l * ls + (uint64_t)poly * kN;
-  const LimbConst<uint32_t> lc = lcs[l];
-  const Tabs T = tabs_of(mft, lc, l);
-  uint64_t so;
-  if (slots) {
-    const uint32_t xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20) & 7u;          // hwreg(HW_REG_XCC_ID)
-    const uint32_t cu = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 8) & 0xffu;  // hwreg(HW_REG_HW_ID)[15:8]
-    so = (uint64_t)((xcc << 8) | cu) << 16;
-  } else {
-    so = (uint64_t)(poly + l * gridDim.x) << 16;
-  }
-  const Rsrc RS = rsrc(scratch + so, kN * 4u);
-  constexpr int R = RNT_MF_MUL2_REG;
-  static_assert(R >= 0 && R <= 16 - kMulLdsTiles, "a^ register tiles");
-  constexpr int MEM = 16 - kMulLdsTiles - R;  // tiles 0 .. MEM-1 through the slot
-  v4i ra[R > 0 ? R : 1], rbv[R > 0 ? R : 1];
-  auto hat = [&](const Th& h, int t) -> v4i& {
-    return ((v4i*)(lds + kMulLdsBase) + h.w * (kMulLdsTiles * 64) + h.lam())[t * 64];
-  };
-  uint32_t xa[64], xb[64];
-  auto put = [&](const Th& h, v4i (&reg)[R > 0 ? R : 1], int cc, const int32_t (&r)[4]) {
-    const v4i v = {r[0], r[1], r[2], r[3]};
-    if (cc >= 16 - kMulLdsTiles)
-      hat(h, cc - (16 - kMulLdsTiles)) = v;
-    else if (cc >= MEM)
-      reg[cc - MEM] = v;
-    else
-      bst(v, RS, p4_lane(h), p4_soff(h, cc));
-  };
-  constexpr int NP = RNT_MF_MUL2_PARK;
-  fwd2<false, S_F4S, false, true, NP, kMulLdsBase * 4, kMulLdsTiles * 1024>(
-      xa, xb, rsrc(a + o, kN * 4u), lds, ha, hb, T,
-      [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) { put(ha, ra, cc, r); },
-      [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) { put(hb, rbv, cc, r); });
-  auto mul = [&](const Th& h, v4i (&reg)[R > 0 ? R : 1], int cc, const int32_t (&r)[4], uint32_t (&xx)[64]) {
-    const v4i ah = cc >= 16 - kMulLdsTiles ? hat(h, cc - (16 - kMulLdsTiles))
-                   : cc >= MEM             ? reg[cc - MEM]
-                                           : bld(RS, p4_lane(h), p4_soff(h, cc));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) xx[p3(cc, i)] = (uint32_t)mont<true>(ah[i], r[i], T.m) ^ K32;  // (as k_mf_mul)
-    pin4(xx[p3(cc, 0)], xx[p3(cc, 1)], xx[p3(cc, 2)], xx[p3(cc, 3)]);
-  };
-  fwd2<false, S_F4, true, (NP > 0), NP, 0, 4096>(
-      xa, xb, rsrc(b + o, kN * 4u), lds, ha, hb, T,
-      [&](int cc, const int32_t (&r)[4], uint32_t (&xx)[64]) { mul(ha, ra, cc, r, xx); },
-      [&](int cc, const int32_t (&r)[4], uint32_t (&xx)[64]) { mul(hb, rbv, cc, r, xx); });
-  inv2(xa, xb, rsrc(c + o, kN * 4u), lds, ha, hb, T);
 }
 
 // ---------------------------------------------------------------------------
@@ -1546,6 +1446,13 @@ int mf_build(Tables* t, std::string* err) {
       const double rb = (double)q / 2 + 16384.0;
       if (rb * rb / 4294967296.0 + (double)q / 2 + 1 >= (double)0x7F7F7F7Fu) {
         *err = "MFMA tables: the product bound exceeds the packed digit range for this prime";
+        return -1;
+      }
+      // the same for a folded pass's output (recomb_tw): digit-sum halves
+      // |lo|, |hi| <= 2^28 + 2^20 times twists |tw| <= q/2
+      if ((kFold3 || kFold4) &&
+          (268435456.0 + 1048576.0) * (double)q / 4294967296.0 + (double)q / 2 + 1 >= (double)0x7F7F7F7Fu) {
+        *err = "MFMA tables: the folded twist bound exceeds the packed digit range for this prime";
         return -1;
       }
     }
@@ -1629,35 +1536,47 @@ int mf_build(Tables* t, std::string* err) {
           c4[lam * 4 + i] = ci[lam & 15];
         }
     }
-    // twists (Montgomery form, centred)
-    auto mr = [&](uint64_t v) { return centred(mulmod(v, R, q), q); };
+    // twists, centred: Montgomery form t 2^32 in a family's single table, or,
+    // folded, plain t in its A table and t 2^16 in its B table (same order)
+    const uint64_t s16 = (1ull << 16) % q;
+    auto put = [&](int32_t* tab, bool fold, int dist, size_t idx, uint64_t tv) {
+      if (fold) {
+        tab[idx] = centred(tv, q);
+        tab[(size_t)dist * 4 + idx] = centred(mulmod(tv, s16, q), q);
+      } else {
+        tab[idx] = centred(mulmod(tv, R, q), q);
+      }
+    };
     int32_t* t3f = lt + (size_t)kTw3f * 4;
-    int32_t* t3i = lt + (size_t)kTw3i * 4;
+    int32_t* t3fa = lt + (size_t)kTw3fA * 4;
+    int32_t* t3i = lt + (size_t)kTw3iR * 4;
     for (int w = 0; w < 16; ++w)
       for (int g = 0; g < 4; ++g)
         for (int c = 0; c < 16; ++c)
           for (int i = 0; i < 4; ++i) {
             const int U3 = (w << 4) | (i << 2) | g;
-            t3f[((w * 4 + g) * 16 + c) * 4 + i] = mr(powmod(tw[2048 + 8 * U3], (uint64_t)c, q));
+            const uint64_t tv = powmod(tw[2048 + 8 * U3], (uint64_t)c, q);
+            put(t3f, false, 0, ((w * 4 + g) * 16 + c) * 4 + i, tv);
+            if (kFold3) put(t3fa, true, kTwB3, ((w * 4 + g) * 16 + c) * 4 + i, tv);
           }
     for (int w = 0; w < 16; ++w)
       for (int c = 0; c < 16; ++c)
         for (int g = 0; g < 4; ++g)
           for (int i = 0; i < 4; ++i) {
             const int U3 = (w << 4) | c;
-            t3i[((w * 16 + c) * 4 + g) * 4 + i] = mr(powmod(itw[2048 + 8 * U3], (uint64_t)(4 * g + i), q));
+            put(t3i, kFold3, kTwB3, ((w * 16 + c) * 4 + g) * 4 + i, powmod(itw[2048 + 8 * U3], (uint64_t)(4 * g + i), q));
           }
-    int32_t* t4f = lt + (size_t)kTw4f * 4;
-    int32_t* t4i = lt + (size_t)kTw4i * 4;
+    int32_t* t4f = lt + (size_t)kTw4fR * 4;
+    int32_t* t4i = lt + (size_t)kTw4iR * 4;
     for (int w = 0; w < 16; ++w)
       for (int c = 0; c < 16; ++c)
         for (int lam = 0; lam < 64; ++lam)
           for (int i = 0; i < 4; ++i) {
             const int g = lam >> 4, nn = lam & 15;
             const int Uf = (w << 8) | (c << 4) | nn;
-            t4f[((w * 16 + c) * 64 + lam) * 4 + i] = mr(powmod(tw[32768 + 8 * Uf], (uint64_t)(4 * g + i), q));
+            put(t4f, kFold4, kTwB4, ((w * 16 + c) * 64 + lam) * 4 + i, powmod(tw[32768 + 8 * Uf], (uint64_t)(4 * g + i), q));
             const int Ui = (w << 8) | (c << 4) | (4 * g + i);
-            t4i[((w * 16 + c) * 64 + lam) * 4 + i] = mr(powmod(itw[32768 + 8 * Ui], (uint64_t)nn, q));
+            put(t4i, kFold4, kTwB4, ((w * 16 + c) * 64 + lam) * 4 + i, powmod(itw[32768 + 8 * Ui], (uint64_t)nn, q));
           }
   }
   // t->mf is set only once the tables are on the device: a failed build
@@ -1705,15 +1624,14 @@ hipError_t launch_mf_tensor(const Launch& k, void* d0, void* d1, void* d2, uint6
 hipError_t launch_mf_mul(const Launch& k, void* c, const void* a, const void* b, uint64_t ls, void* scratch) {
   if (k.B == 0 || k.L == 0) return hipSuccess;
   if (k.B > 0x7fffffffull || k.L > 65535) return hipErrorInvalidConfiguration;
-  const void* fn = RNT_MF_MUL_V2 ? (const void*)k_mf_mul2 : (const void*)k_mf_mul;
+  const void* fn = (const void*)k_mf_mul;
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf::kLdsBytes);
   if (e != hipSuccess) return e;
   uint32_t slots = (uint64_t)k.B * k.L >= kPlaneSlots ? 1u : 0u;  // plane_scratch_planes
   const void* mft = k.t->mf;
   const LimbConst<uint32_t>* lcs = (const LimbConst<uint32_t>*)k.t->lconst;
   void* args[] = {&c, &a, &b, &ls, &scratch, &slots, &mft, &lcs};
-  return hipLaunchKernel(fn, dim3((unsigned)k.B, (unsigned)k.L), dim3(RNT_MF_MUL_V2 ? mf::kT / 2 : mf::kT), args,
-                         mf::kLdsBytes, k.s);
+  return hipLaunchKernel(fn, dim3((unsigned)k.B, (unsigned)k.L), dim3(mf::kT), args, mf::kLdsBytes, k.s);
 }
 
 #ifdef RNT_MF_TRACE
