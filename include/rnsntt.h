@@ -128,6 +128,18 @@ int rnt_ctx_destroy(rnt_ctx* ctx);
 /* RnsBasis::drop_last (basis.rs:121-134): a prefix view sharing the
  * parent's device tables (no table copy). */
 int rnt_ctx_drop_last(const rnt_ctx* ctx, size_t drop_count, rnt_ctx** out);
+/* The LEVEL CONTEXT of a hybrid key context (see "key level views" below):
+ * key_ctx has L + K limbs q_0..q_{L-1}, p_0..p_{K-1} with K = n_special and
+ * 1 <= level <= L; *out is the basis q_0..q_{level-1}, p_0..p_{K-1}, sharing
+ * key_ctx's tables as rnt_ctx_drop_last does (working limb t is key_ctx's limb
+ * t below level, t + (L - level) from there on).  rnt_ctx_degree,
+ * _channel_count (= level + K), _moduli, _total_bits, _psi, _stream and
+ * _destroy report the view.  It holds key level views alone: on it
+ * rnt_ctx_drop_last, rnt_buf_alloc, rnt_buf_alloc_uninit and rnt_buf_wrap ->
+ * RNT_ERR_UNSUPPORTED (fields 0, 0).  A null argument, n_special == 0 or >=
+ * the limb count, level == 0 or > L, or a key_ctx that is itself a level
+ * context -> RNT_ERR_BAD_ARGUMENT. */
+int rnt_ctx_hybrid_level(const rnt_ctx* key_ctx, size_t n_special, size_t level, rnt_ctx** out);
 int rnt_ctx_degree(const rnt_ctx* ctx, size_t* n);
 int rnt_ctx_channel_count(const rnt_ctx* ctx, size_t* count); /* basis.rs:116-118 */
 int rnt_ctx_moduli(const rnt_ctx* ctx, uint64_t* out);       /* basis.rs:108-110 */
@@ -435,7 +447,8 @@ int rnt_ct_linear_bsgs_hoisted(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, 
  * and 0 elsewhere (all special limbs 0); the caller chooses P >~ alpha max Q_d.
  * At a lower level Lv' the key is the first ceil(Lv'/alpha) polys of the full
  * one restricted to the limbs q_0 .. q_{Lv'-1}, p_0 .. p_{K-1}, on a root
- * context over exactly those moduli.
+ * context over exactly those moduli -- or, without a copy, a key level view of
+ * the full key (rnt_key_level_view, below).
  * Errors: alpha == 0, acc0 aliasing acc1 or d, batch sizes that differ ->
  * RNT_ERR_BAD_ARGUMENT; degree, device or moduli-prefix mismatch, or E without
  * a limb above C's -> RNT_ERR_BASIS_MISMATCH; E and C of different device word
@@ -460,6 +473,35 @@ int rnt_ct_rotate_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const 
 int rnt_ct_mul_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
                             const rnt_buf* c0p, const rnt_buf* c1p,
                             const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha);
+/* ---- key level views: one full-level hybrid key at every level -------------
+ * The level-Lv' key is a subset of the full key's planes, so it needs no copy:
+ * rnt_key_level_view makes a NON-owning, READ-ONLY buffer over `key`'s storage
+ * on level_ctx (rnt_ctx_hybrid_level of key's context).  key: m beta polys,
+ * beta = ceil(L / alpha), prepared (NTT domain, ordinary or hoisting form);
+ * m = 1 is a key, m > 1 a packed key set.  The view reports m beta' polys,
+ * beta' = ceil(level / alpha); its logical poly g beta' + d on working limb t
+ * is the stored plane (r(t) m beta + g beta + d) N with r(t) the limb map
+ * above: a set's steps keep the full key's poly stride beta.
+ * A view is accepted as the key argument(s) of the seven hybrid calls
+ * (rnt_keyswitch_hybrid, rnt_ct_rotate_hybrid, rnt_ct_mul_relin_hybrid,
+ * rnt_ct_rotate_hybrid_hoisted, rnt_ct_linear_bsgs_hybrid,
+ * rnt_ct_mul_relin_rescale_hybrid, rnt_ct_linear_bsgs_hybrid_rescale), and the
+ * call is then, word for word, the same call with the restricted key on a
+ * root context over the view's moduli.  Both halves (and both sets of a BSGS
+ * call) must be views on the SAME level-context handle; a view at level == L
+ * behaves as the key itself.  In any other position of any call a view ->
+ * RNT_ERR_UNSUPPORTED (fields 0, 0) and nothing is touched.  rnt_buf_n_polys
+ * and rnt_buf_is_ntt work on a view; rnt_buf_free releases the handle alone.
+ * LIFETIME: the parent buffer must outlive its views, and a view reads the
+ * parent's current words -- re-preparing or overwriting the parent changes
+ * what the view reads.
+ * Errors: key not on the context level_ctx was made from ->
+ * RNT_ERR_BASIS_MISMATCH; a coefficient-domain key -> RNT_ERR_DOMAIN_MISMATCH;
+ * alpha == 0, a level_ctx that is no level context, a view of a view, a null
+ * argument -> RNT_ERR_BAD_ARGUMENT; a poly count that is no multiple of beta
+ * -> RNT_ERR_CHANNEL_COUNT (fields: beta, got).  The first hybrid call of a
+ * (view, alpha) pair builds its constants and cannot be recorded. */
+int rnt_key_level_view(const rnt_buf* key, const rnt_ctx* level_ctx, size_t alpha, rnt_buf** out);
 /* ---- hoisted rotations and the baby-step giant-step transform on hybrid
  * keys (DESIGN.md "Hoisted hybrid rotations") ------------------------------
  * Notation as above: C, E, beta = ceil(Lv / alpha), ModUp_d, ModDown; sigma_k =

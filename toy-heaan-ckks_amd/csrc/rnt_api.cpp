@@ -244,7 +244,9 @@ inline rnt::Launch launch_for(const rnt_buf* b) {
 }
 
 inline size_t poly_words(const rnt_buf* b) { return b->ctx->L * b->n_polys * b->ctx->t->n; }
-inline uint64_t limb_stride(const rnt_buf* b) { return (uint64_t)b->n_polys * b->ctx->t->n; }
+inline uint64_t limb_stride(const rnt_buf* b) {
+  return (uint64_t)(b->view_of ? b->stored_polys : b->n_polys) * b->ctx->t->n;
+}
 
 int set_device(const rnt_ctx* ctx) {
   HIP_TRY(hipSetDevice(ctx->t->device), "hipSetDevice");
@@ -536,8 +538,17 @@ void trim_stage(rnt_buf* b) {
   }
 }
 
-int check_buf(const rnt_buf* b, const char* name) {
+// A key argument of a hybrid call: a buffer or a level view of one.
+int check_key_buf(const rnt_buf* b, const char* name) {
   if (b == nullptr || b->ctx == nullptr) return fail(RNT_ERR_BAD_ARGUMENT, "%s: null buffer", name);
+  return RNT_OK;
+}
+// Every other operand: a key level view is read-only, strided storage of
+// another buffer and serves as a hybrid key alone.
+int check_buf(const rnt_buf* b, const char* name) {
+  if (int rc = check_key_buf(b, name)) return rc;
+  if (b->view_of)
+    return fail_fields(RNT_ERR_UNSUPPORTED, 0, 0, "%s: a key level view serves only as the key of a hybrid call", name);
   return RNT_OK;
 }
 
@@ -859,7 +870,11 @@ extern "C" int rnt_ctx_create(uint32_t log_n, const uint64_t* moduli, size_t cou
 }
 
 static void ctx_release(const rnt_ctx* ctx) {
-  if (ctx && const_cast<rnt_ctx*>(ctx)->refs.fetch_sub(1) == 1) delete ctx;
+  while (ctx && const_cast<rnt_ctx*>(ctx)->refs.fetch_sub(1) == 1) {
+    const rnt_ctx* parent = ctx->parent;  // a level context holds its parent
+    delete ctx;
+    ctx = parent;
+  }
 }
 static void ctx_retain(const rnt_ctx* ctx) { const_cast<rnt_ctx*>(ctx)->refs.fetch_add(1); }
 
@@ -872,6 +887,8 @@ extern "C" int rnt_ctx_destroy(rnt_ctx* ctx) {
 extern "C" int rnt_ctx_drop_last(const rnt_ctx* ctx, size_t drop_count, rnt_ctx** out) {
   if (!ctx || !out) return fail(RNT_ERR_BAD_ARGUMENT, "null argument");
   *out = nullptr;
+  if (ctx->is_level())
+    return fail_fields(RNT_ERR_UNSUPPORTED, 0, 0, "rnt_ctx_drop_last: a level context has no prefixes");
   if (drop_count >= ctx->L)
     return fail_fields(RNT_ERR_INVALID_MOD_DROP, drop_count, ctx->L,
                        "invalid mod-drop count %zu for %zu channels", drop_count, ctx->L);
@@ -879,6 +896,31 @@ extern "C" int rnt_ctx_drop_last(const rnt_ctx* ctx, size_t drop_count, rnt_ctx*
     rnt_ctx* c = new rnt_ctx;
     c->t = ctx->t;
     c->L = ctx->L - drop_count;
+    *out = c;
+  } catch (...) {
+    return fail(RNT_ERR_OUT_OF_MEMORY, "host allocation failed");
+  }
+  return RNT_OK;
+}
+
+extern "C" int rnt_ctx_hybrid_level(const rnt_ctx* key_ctx, size_t n_special, size_t level, rnt_ctx** out) {
+  if (!key_ctx || !out) return fail(RNT_ERR_BAD_ARGUMENT, "null argument");
+  *out = nullptr;
+  if (key_ctx->is_level())
+    return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ctx_hybrid_level: the key context is itself a level context");
+  if (n_special == 0 || n_special >= key_ctx->L)
+    return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ctx_hybrid_level: %zu special limbs of %zu", n_special, key_ctx->L);
+  const size_t L = key_ctx->L - n_special;
+  if (level == 0 || level > L)
+    return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ctx_hybrid_level: level %zu of %zu", level, L);
+  try {
+    rnt_ctx* c = new rnt_ctx;
+    c->t = key_ctx->t;
+    c->L = level + n_special;
+    c->parent = key_ctx;
+    c->level = level;
+    c->gap = L - level;
+    ctx_retain(key_ctx);
     *out = c;
   } catch (...) {
     return fail(RNT_ERR_OUT_OF_MEMORY, "host allocation failed");
@@ -898,20 +940,20 @@ extern "C" int rnt_ctx_channel_count(const rnt_ctx* ctx, size_t* count) {
 }
 extern "C" int rnt_ctx_moduli(const rnt_ctx* ctx, uint64_t* out) {
   if (!ctx || !out) return fail(RNT_ERR_BAD_ARGUMENT, "null argument");
-  std::copy(ctx->t->moduli.begin(), ctx->t->moduli.begin() + ctx->L, out);
+  for (size_t i = 0; i < ctx->L; ++i) out[i] = ctx->modulus(i);
   return RNT_OK;
 }
 extern "C" int rnt_ctx_total_bits(const rnt_ctx* ctx, uint32_t* bits) {
   if (!ctx || !bits) return fail(RNT_ERR_BAD_ARGUMENT, "null argument");
   uint32_t s = 0;
-  for (size_t i = 0; i < ctx->L; ++i) s += 63u - (uint32_t)__builtin_clzll(ctx->t->moduli[i]);
+  for (size_t i = 0; i < ctx->L; ++i) s += 63u - (uint32_t)__builtin_clzll(ctx->modulus(i));
   *bits = s;
   return RNT_OK;
 }
 extern "C" int rnt_ctx_psi(const rnt_ctx* ctx, size_t limb, uint64_t* psi) {
   if (!ctx || !psi) return fail(RNT_ERR_BAD_ARGUMENT, "null argument");
   if (limb >= ctx->L) return fail(RNT_ERR_BAD_ARGUMENT, "limb %zu out of range", limb);
-  *psi = ctx->t->psi[limb];
+  *psi = ctx->t->psi[ctx->root_limb(limb)];
   return RNT_OK;
 }
 extern "C" int rnt_ctx_stream(const rnt_ctx* ctx, void** stream) {
@@ -1092,6 +1134,8 @@ extern "C" int rnt_buf_alloc_uninit(const rnt_ctx* ctx, size_t n_polys, rnt_buf*
 static int buf_alloc(const rnt_ctx* ctx, size_t n_polys, rnt_buf** out, bool zero) {
   if (!ctx || !out) return fail(RNT_ERR_BAD_ARGUMENT, "null argument");
   *out = nullptr;
+  if (ctx->is_level())
+    return fail_fields(RNT_ERR_UNSUPPORTED, 0, 0, "a level context holds key views alone (rnt_key_level_view)");
   if (n_polys == 0) return fail(RNT_ERR_BAD_ARGUMENT, "n_polys must be positive");
   if (int rc = set_device(ctx)) return rc;
   rnt_buf* b = nullptr;
@@ -1157,6 +1201,8 @@ extern "C" int rnt_pool_trim(int device, size_t* freed_bytes) {
 extern "C" int rnt_buf_wrap(const rnt_ctx* ctx, void* device_ptr, size_t n_polys, int in_ntt,
                             rnt_buf** out) {
   if (!ctx || !device_ptr || !out) return fail(RNT_ERR_BAD_ARGUMENT, "null argument");
+  if (ctx->is_level())
+    return fail_fields(RNT_ERR_UNSUPPORTED, 0, 0, "rnt_buf_wrap: a level context holds key views alone");
   if (n_polys == 0) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_buf_wrap: empty batch");
   rnt_buf* b = new (std::nothrow) rnt_buf;
   if (!b) return fail(RNT_ERR_OUT_OF_MEMORY, "rnt_buf_wrap");
@@ -1172,8 +1218,41 @@ extern "C" int rnt_buf_wrap(const rnt_ctx* ctx, void* device_ptr, size_t n_polys
 
 extern "C" int rnt_buf_device_ptr(const rnt_buf* b, void** device_ptr, size_t* word_bytes_out) {
   if (!b || !device_ptr) return fail(RNT_ERR_BAD_ARGUMENT, "null argument");
+  if (int rc = check_buf(b, "rnt_buf_device_ptr")) return rc;
   *device_ptr = b->data;
   if (word_bytes_out) *word_bytes_out = word_bytes(b->ctx->t.get());
+  return RNT_OK;
+}
+
+extern "C" int rnt_key_level_view(const rnt_buf* key, const rnt_ctx* level_ctx, size_t alpha, rnt_buf** out) {
+  const char* name = "rnt_key_level_view";
+  if (!out || !level_ctx) return fail(RNT_ERR_BAD_ARGUMENT, "%s: null argument", name);
+  *out = nullptr;
+  if (int rc = check_key_buf(key, name)) return rc;
+  if (key->view_of) return fail(RNT_ERR_BAD_ARGUMENT, "%s: the key is itself a level view", name);
+  if (!level_ctx->is_level()) return fail(RNT_ERR_BAD_ARGUMENT, "%s: not a level context", name);
+  if (key->ctx != level_ctx->parent)
+    return fail(RNT_ERR_BASIS_MISMATCH, "%s: the key is not on the context the level context was made from", name);
+  if (!key->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the key must be prepared (rnt_key_prepare)", name);
+  if (alpha == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: alpha must be at least 1", name);
+  const size_t L = level_ctx->level + level_ctx->gap;
+  const size_t beta = (L + alpha - 1) / alpha, beta_v = (level_ctx->level + alpha - 1) / alpha;
+  if (key->n_polys % beta != 0)
+    return fail_fields(RNT_ERR_CHANNEL_COUNT, beta, key->n_polys,
+                       "%s: a hybrid key for %zu limbs in digits of %zu holds a multiple of %zu polys", name, L, alpha,
+                       beta);
+  rnt_buf* b = new (std::nothrow) rnt_buf;
+  if (!b) return fail(RNT_ERR_OUT_OF_MEMORY, "%s", name);
+  b->ctx = level_ctx;
+  b->n_polys = key->n_polys / beta * beta_v;
+  b->data = key->data;
+  b->in_ntt = 1;
+  b->owns = false;
+  b->view_of = key;
+  b->stored_polys = key->n_polys;
+  b->step_polys = beta;
+  ctx_retain(level_ctx);
+  *out = b;
   return RNT_OK;
 }
 
@@ -2384,8 +2463,27 @@ int copy_rows(const rnt::Launch& k, void* dst, uint64_t dst_ls, const void* src,
 // tables whose profile counts them (nullptr: k.t, whose stream k.s then is) --
 // the hybrid key-switch transforms over the key basis' tables on the
 // ciphertext context's stream.
+// Over a level view with a gap (k.map_gap, the hybrid calls' launches alone)
+// the working limbs are two contiguous runs of root limbs -- [0, level) and
+// [level + gap, ..) -- and the same launches run once per run, the second with
+// its table-limb base (Launch::tab0) on the block's limb `level`.
+bool raw_split(const rnt::Launch& k, rnt::Launch* lo, rnt::Launch* hi) {
+  if (k.map_gap == 0 || k.L <= k.map_level) return false;
+  *lo = *hi = k;
+  lo->map_level = hi->map_level = UINT32_MAX;
+  lo->map_gap = hi->map_gap = 0;
+  lo->L = k.map_level;
+  hi->L = k.L - k.map_level;
+  hi->tab0 = k.map_level + k.map_gap;
+  return true;
+}
 int fwd_raw(const rnt::Launch& k, void* p, uint64_t ls, const rnt::Tables* pt = nullptr) {
   if (!pt) pt = k.t;
+  rnt::Launch lo, hi;
+  if (raw_split(k, &lo, &hi)) {
+    if (int rc = fwd_raw(lo, p, ls, pt)) return rc;
+    return fwd_raw(hi, (char*)p + (size_t)k.map_level * ls * word_bytes(k.t), ls, pt);
+  }
   if (use_mf(k)) {
     LAUNCH_ON(pt, k.s, rnt::K_MF_NTT_FWD, rnt::launch_mf_ntt(k, 0, p, ls), "MFMA forward transform");
   } else if (rnt::whole_ok(k.t, 0)) {
@@ -2398,6 +2496,11 @@ int fwd_raw(const rnt::Launch& k, void* p, uint64_t ls, const rnt::Tables* pt = 
 }
 int inv_raw(const rnt::Launch& k, void* p, uint64_t ls, const rnt::Tables* pt = nullptr) {
   if (!pt) pt = k.t;
+  rnt::Launch lo, hi;
+  if (raw_split(k, &lo, &hi)) {
+    if (int rc = inv_raw(lo, p, ls, pt)) return rc;
+    return inv_raw(hi, (char*)p + (size_t)k.map_level * ls * word_bytes(k.t), ls, pt);
+  }
   if (use_mf(k)) {
     LAUNCH_ON(pt, k.s, rnt::K_MF_NTT_INV, rnt::launch_mf_ntt(k, 1, p, ls), "MFMA inverse transform");
   } else if (rnt::whole_ok(k.t, 1)) {
@@ -2836,15 +2939,20 @@ struct HybridPlan {
   const rnt_ctx* C = nullptr;  // the ciphertext's context (Lv limbs)
   const rnt_ctx* E = nullptr;  // the key's context (Lv + K limbs)
   size_t Lv = 0, K = 0, LE = 0, alpha = 0, beta = 0;
+  // the key context's limb map (a level context with a gap; else the identity)
+  size_t level = UINT32_MAX, gap = 0;
   rnt::HybridConsts hc{};
 };
+
+// The polys between two steps of a key set: a view keeps the full key's beta.
+size_t key_step_polys(const rnt_buf* keys, const HybridPlan& pl) { return keys->view_of ? keys->step_polys : pl.beta; }
 
 // The argument rules the three hybrid calls share (no device work).
 int hybrid_check(const char* name, const rnt_ctx* C, const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha,
                  HybridPlan* pl) {
   if (alpha == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: alpha must be at least 1", name);
-  if (int rc = check_buf(key_a, name)) return rc;
-  if (int rc = check_buf(key_b, name)) return rc;
+  if (int rc = check_key_buf(key_a, name)) return rc;
+  if (int rc = check_key_buf(key_b, name)) return rc;
   if (key_a->ctx != key_b->ctx)
     return fail(RNT_ERR_BASIS_MISMATCH, "%s: the key halves belong to different bases", name);
   const rnt_ctx* E = key_a->ctx;
@@ -2857,9 +2965,9 @@ int hybrid_check(const char* name, const rnt_ctx* C, const rnt_buf* key_a, const
     return fail(RNT_ERR_BASIS_MISMATCH, "%s: the key basis (%zu limbs) has no special limb above the ciphertext's %zu",
                 name, E->L, Lv);
   for (size_t l = 0; l < Lv; ++l)
-    if (te->moduli[l] != tc->moduli[l])
+    if (E->modulus(l) != tc->moduli[l])
       return fail(RNT_ERR_BASIS_MISMATCH, "%s: limb %zu of the key basis is %" PRIu64 ", the ciphertext's %" PRIu64,
-                  name, l, te->moduli[l], tc->moduli[l]);
+                  name, l, E->modulus(l), tc->moduli[l]);
   if (te->wide != tc->wide)
     return fail_fields(RNT_ERR_UNSUPPORTED, 0, 0, "%s: key and ciphertext bases have different device word widths",
                        name);
@@ -2876,11 +2984,17 @@ int hybrid_check(const char* name, const rnt_ctx* C, const rnt_buf* key_a, const
   pl->K = E->L - Lv;
   pl->alpha = std::min(alpha, Lv);  // (one digit holds every limb from alpha = Lv on)
   pl->beta = beta;
+  if (E->is_level() && E->gap != 0) {
+    pl->level = E->level;
+    pl->gap = E->gap;
+  }
   return RNT_OK;
 }
 
-// The device constants of (key limbs, ciphertext limbs, alpha), cached on the
-// key basis' tables; the first use allocates and copies, so it cannot be
+// The device constants of (key limbs, ciphertext limbs, alpha, limb map),
+// cached on the key basis' tables -- the map is part of the key: a level view
+// and a drop_last prefix of one root can agree in the first three and differ
+// in their special primes; the first use allocates and copies, so it cannot be
 // recorded into a graph (one un-recorded run first).  Also orders the call
 // after the work queued on the key basis' stream where that is another stream
 // than the ciphertext's (its keys may still be in preparation there).
@@ -2897,13 +3011,15 @@ int hybrid_prepare(HybridPlan* pl) {
   }
   std::lock_guard<std::mutex> g(te->resc_mu);
   for (auto& e : te->hyb_cache)
-    if (e.LE == pl->LE && e.Lv == pl->Lv && e.alpha == pl->alpha) {
+    if (e.LE == pl->LE && e.Lv == pl->Lv && e.alpha == pl->alpha && e.level == pl->level && e.gap == pl->gap) {
       pl->hc = e.hc;
       return RNT_OK;
     }
   const rnt::host::HybridLayout lay(pl->Lv, pl->K, pl->alpha);
   std::vector<uint64_t> h(lay.total);
-  if (!rnt::host::hybrid_constants(te->moduli.data(), lay, te->wide ? 64 : 32, h.data()))
+  std::vector<uint64_t> mod(pl->LE);  // the key basis' moduli through the limb map
+  for (size_t t = 0; t < pl->LE; ++t) mod[t] = pl->E->modulus(t);
+  if (!rnt::host::hybrid_constants(mod.data(), lay, te->wide ? 64 : 32, h.data()))
     return fail(RNT_ERR_BAD_ARGUMENT, "hybrid key-switch: the moduli of the key basis are not pairwise coprime");
   const size_t wb = word_bytes(te);
   void* d = nullptr;
@@ -2923,6 +3039,8 @@ int hybrid_prepare(HybridPlan* pl) {
   hd.LE = pl->LE;
   hd.Lv = pl->Lv;
   hd.alpha = pl->alpha;
+  hd.level = pl->level;
+  hd.gap = pl->gap;
   hd.dev = d;
   auto at = [&](size_t o) { return (const void*)((const char*)d + o * wb); };
   hd.hc.yinv = at(lay.yinv), hd.hc.yinvp = at(lay.yinvp);
@@ -2936,6 +3054,19 @@ int hybrid_prepare(HybridPlan* pl) {
   te->hyb_cache.push_back(hd);
   pl->hc = hd.hc;
   return RNT_OK;
+}
+
+// A launch of c polys over the key basis: its tables and limb map, on the
+// ciphertext context's stream.
+rnt::Launch hybrid_launch(const HybridPlan& pl, size_t c) {
+  rnt::Launch k;
+  k.t = pl.E->t.get();
+  k.L = pl.LE;
+  k.B = c;
+  k.s = pl.C->t->stream;
+  k.map_level = (uint32_t)pl.level;
+  k.map_gap = (uint32_t)pl.gap;
+  return k;
 }
 
 // Planes of N words one poly of a chunk needs: the raised digits D
@@ -2962,11 +3093,7 @@ int hybrid_chunk_run(const HybridPlan& pl, size_t c, char* ws, const void* x, ui
   const rnt::Tables* tc = pl.C->t.get();
   const rnt::Tables* te = pl.E->t.get();
   const size_t n = te->n, wb = word_bytes(te);
-  rnt::Launch k;
-  k.t = te;
-  k.L = pl.LE;
-  k.B = c;
-  k.s = tc->stream;
+  const rnt::Launch k = hybrid_launch(pl, c);
   char* D = ws;
   char* A0 = D + pl.LE * pl.beta * c * n * wb;
   char* A1 = A0 + pl.LE * c * n * wb;
@@ -3231,11 +3358,7 @@ extern "C" int rnt_ct_mul_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, con
     const uint64_t cls = (uint64_t)c * n;
     const size_t po = p0 * n * wb;
     auto off = [&](const rnt_buf* b) { return (const char*)b->data + po; };
-    rnt::Launch ke;
-    ke.t = pl.E->t.get();
-    ke.L = pl.LE;
-    ke.B = c;
-    ke.s = tc->stream;
+    const rnt::Launch ke = hybrid_launch(pl, c);
     char* D = HW;
     char* A0 = D + pl.LE * pl.beta * c * n * wb;
     char* A1 = A0 + pl.LE * c * n * wb;
@@ -3734,8 +3857,8 @@ int hybrid_set_check(const char* name, const rnt_ctx* C, const int32_t* steps, s
   for (size_t t = 0; t < n_steps; ++t) nz += steps[t] != 0;
   *have = nz || keys_a || keys_b;
   if (!*have) return RNT_OK;
-  if (int rc = check_buf(keys_a, name)) return rc;
-  if (int rc = check_buf(keys_b, name)) return rc;
+  if (int rc = check_key_buf(keys_a, name)) return rc;
+  if (int rc = check_key_buf(keys_b, name)) return rc;
   const size_t beta = alpha >= C->L ? 1 : (C->L + alpha - 1) / alpha;
   rnt_buf va, vb;  // step 0's slot: a key of beta polys for hybrid_check
   auto view = [&](rnt_buf& v, const rnt_buf* kbuf) {
@@ -3744,6 +3867,9 @@ int hybrid_set_check(const char* name, const rnt_ctx* C, const int32_t* steps, s
     v.data = kbuf->data;
     v.in_ntt = kbuf->in_ntt;
     v.owns = false;
+    v.view_of = kbuf->view_of;
+    v.stored_polys = kbuf->stored_polys;
+    v.step_polys = kbuf->step_polys;
   };
   view(va, keys_a);
   view(vb, keys_b);
@@ -3753,15 +3879,6 @@ int hybrid_set_check(const char* name, const rnt_ctx* C, const int32_t* steps, s
     return fail_fields(RNT_ERR_CHANNEL_COUNT, want, keys_a->n_polys != want ? keys_a->n_polys : keys_b->n_polys,
                        "%s: the key set must hold one poly per step and digit (%zu)", name, want);
   return RNT_OK;
-}
-
-rnt::Launch hybrid_launch(const HybridPlan& pl, size_t c) {
-  rnt::Launch k;
-  k.t = pl.E->t.get();
-  k.L = pl.LE;
-  k.B = c;
-  k.s = pl.C->t->stream;
-  return k;
 }
 
 // Whether the tail of a chunk of bc ciphertexts is k_moddown_auto.  Its result
@@ -3843,8 +3960,8 @@ int hybrid_hoist_chunk(const HybridPlan& pl, size_t c, char* D, char* ACC, const
       idx[nt] = t;
       a0[nt] = ACC + 2 * nt * pe;
       a1[nt] = ACC + (2 * nt + 1) * pe;
-      ka[nt] = (const char*)keys_a->data + t * pl.beta * n * wb;
-      kb[nt] = (const char*)keys_b->data + t * pl.beta * n * wb;
+      ka[nt] = (const char*)keys_a->data + t * key_step_polys(keys_a, pl) * n * wb;
+      kb[nt] = (const char*)keys_b->data + t * key_step_polys(keys_b, pl) * n * wb;
       ++nt;
     }
     if (nt == 0) break;
@@ -4099,8 +4216,8 @@ static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* o
       km.Ls = pl.beta;
       void* a0[1] = {A0};
       void* a1[1] = {A1};
-      const void* ka[1] = {(const char*)giant_keys_a->data + j * pl.beta * n * wb};
-      const void* kb[1] = {(const char*)giant_keys_b->data + j * pl.beta * n * wb};
+      const void* ka[1] = {(const char*)giant_keys_a->data + j * key_step_polys(giant_keys_a, pl) * n * wb};
+      const void* kb[1] = {(const char*)giant_keys_b->data + j * key_step_polys(giant_keys_b, pl) * n * wb};
       if (first) {
         LAUNCH_ON(kc.t, ke.s, rnt::K_HOIST_MAC,
                   rnt::launch_hoist_mac(km, a0, a1, 1, D, ka, kb, limb_stride(giant_keys_a)), "giant key products");

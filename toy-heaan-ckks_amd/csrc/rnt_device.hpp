@@ -31,6 +31,17 @@ static TabPtrs<W> tab_ptrs(const Tables* t) {
   p.Lroot = (uint32_t)t->L;
   return p;
 }
+// The same from root limb limb0 on: the twiddles and limb constants of a
+// transform launch whose limb l is root limb limb0 + l (Launch::tab0).  The
+// rescale table keeps its root indexing (no transform reads it).
+template <class W>
+static TabPtrs<W> tab_ptrs(const Tables* t, uint32_t limb0) {
+  TabPtrs<W> p = tab_ptrs<W>(t);
+  p.tw += (uint64_t)limb0 * t->n;
+  p.itw += (uint64_t)limb0 * t->n;
+  p.lc += limb0;
+  return p;
+}
 
 template <class W>
 __device__ __forceinline__ Mod<W> mod_of(const LimbConst<W>& lc) {

@@ -97,6 +97,7 @@ struct HybridConsts {
 };
 struct HybridDev {
   size_t LE = 0, Lv = 0, alpha = 0;
+  size_t level = 0, gap = 0;  // the key context's limb map (a level view; else UINT32_MAX, 0)
   void* dev = nullptr;
   HybridConsts hc{};
 };
@@ -135,7 +136,7 @@ struct Tables {
   // centred-CRT constants per limb count (rnt_to_coeffs / rnt_crt_centered)
   std::vector<std::pair<size_t, struct CrtDev>> crt_cache;
   // hybrid key-switch constants (rnt_*_hybrid) of a key basis, per (key limbs,
-  // ciphertext limbs, alpha); under resc_mu, built on first use
+  // ciphertext limbs, alpha, limb map); under resc_mu, built on first use
   std::vector<struct HybridDev> hyb_cache;
   // CKKS special-FFT twiddles (rnt_encode.hip), [N/2] double2, built on
   // first encode/decode
@@ -184,6 +185,15 @@ struct rnt_ctx {
   std::shared_ptr<rnt::Tables> t;
   size_t L = 0;  // channel count of this (possibly dropped) basis
   std::atomic<long> refs{1};  // 1 for the creator + 1 per live buffer
+  // A level context (rnt_ctx_hybrid_level): the basis q_0..q_{level-1},
+  // p_0..p_{K-1} of `parent` (retained), L = level + K.  Working limb t is the
+  // tables' limb t below `level` and t + gap from there on.  It holds key
+  // views alone (rnt_key_level_view): nothing is allocated on it.
+  const rnt_ctx* parent = nullptr;
+  size_t level = 0, gap = 0;
+  bool is_level() const { return parent != nullptr; }
+  size_t root_limb(size_t t) const { return parent && t >= level ? t + gap : t; }
+  uint64_t modulus(size_t t) const { return this->t->moduli[root_limb(t)]; }
 };
 
 struct rnt_buf {
@@ -199,6 +209,12 @@ struct rnt_buf {
   void* stage = nullptr;      // u64 host-format staging for upload/download
   size_t stage_bytes = 0;
   bool owns = true;           // false: rnt_buf_wrap view of caller memory
+  // A key level view (rnt_key_level_view; ctx is a level context, owns false,
+  // data the parent's): logical poly g beta' + d on working limb t is the
+  // parent's plane (ctx->root_limb(t) stored_polys + g step_polys + d) N.
+  const rnt_buf* view_of = nullptr;
+  size_t stored_polys = 0;    // the parent's polys: its limb stride in planes
+  size_t step_polys = 0;      // the full key's digits beta: the poly stride of a set's steps
 };
 
 namespace rnt {
@@ -227,6 +243,15 @@ struct Launch {
   // inverse's addend (g^-1 mod 2N, odd; 0: the addend as it is): no
   // separate automorphism launch for c0 (tiled column grids only)
   uint32_t add_ginv = 0;
+  // The transforms' table-limb base: limb l of the launch reads the tables of
+  // root limb tab0 + l (the forward / inverse transforms alone: col_fwd, row,
+  // whole modes 0 / 1, col_inv without ColRescArgs, mf_ntt).  The data pointer
+  // is the launch's first limb.
+  uint32_t tab0 = 0;
+  // The limb map of a hybrid key's level view (the hybrid kernels alone):
+  // working limb t is root limb t below map_level, t + map_gap from there on.
+  uint32_t map_level = UINT32_MAX;
+  uint32_t map_gap = 0;
   size_t src_limbs() const { return Ls ? Ls : L; }
 };
 
@@ -387,7 +412,10 @@ hipError_t launch_hoist_mac(const Launch& k, void* const* acc0, void* const* acc
 hipError_t launch_hoist_mac_acc(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt, const void* d,
                                 const void* const* key_a, const void* const* key_b, uint64_t key_ls);
 // Hybrid key-switching (rnt_keyswitch_hybrid).  k.t is the KEY basis' tables,
-// k.L = Lv + K its limbs, k.B the chunk's polys.  launch_modup (k_modup): the
+// k.L = Lv + K its limbs, k.B the chunk's polys.  These launchers and the three
+// launch_hoist_mac* read the limb constants and the key planes through the limb
+// map (k.map_level, k.map_gap: a key level view); D, A and the constants of hc
+// stay dense in working limbs.  launch_modup (k_modup): the
 // Montgomery-form raised digits D[t][d][p] = ModUp_d(x) 2^w mod m_t for t < k.L,
 // d < hc.beta, x coefficient-domain over the first Lv limbs at limb stride
 // src_ls; D is [k.L][beta][k.B][N], the block launch_hoist_mac reads with

@@ -1917,6 +1917,15 @@ k_hoist_digits(W* __restrict__ D, const W* __restrict__ c1, TabPtrs<W> tp, uint6
 // mont_mul(d 2^w, key) is the canonical product and the sums stay canonical
 // through add_mod.  No gather: the pre-rotated keys make it a stream.
 constexpr int HOIST_T = (int)kHoistT;
+// The limb map of a hybrid key's level view (rnt_key_level_view): working limb
+// t of the basis q_0..q_{level-1}, p_0..p_{K-1} is root limb t below `level`
+// and t + gap from there on -- the row of tp.lc and the key plane to read.
+// Every caller derives t from blockIdx or a loop counter, so the mapped index
+// is wave-uniform; gap 0 (every other caller) is the identity.
+struct LimbMap {
+  uint32_t level, gap;
+};
+__device__ __forceinline__ uint32_t root_limb(uint32_t t, LimbMap m) { return t < m.level ? t : t + m.gap; }
 template <class W>
 struct HoistArgs {
   const W* key_b[HOIST_T];
@@ -1927,15 +1936,16 @@ struct HoistArgs {
 template <class W, bool VEC>
 __global__ void __launch_bounds__(256)
 k_hoist_mac(HoistArgs<W> a, const W* __restrict__ d, TabPtrs<W> tp, uint32_t log_n, uint64_t limb_words,
-            uint64_t key_ls, uint32_t Ls, uint32_t nt) {
+            uint64_t key_ls, uint32_t Ls, uint32_t nt, LimbMap lm) {
   constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
   const uint32_t j = blockIdx.y;
   const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
   if (i >= limb_words) return;
-  const LimbConst<W> lc = tp.lc[j];
+  const uint32_t rj = root_limb(j, lm);
+  const LimbConst<W> lc = tp.lc[rj];
   const uint64_t N = 1ull << log_n;
   const W* dp = d + (uint64_t)j * Ls * limb_words + i;
-  const uint64_t ko = (uint64_t)j * key_ls + (i & (N - 1));  // V divides N: one plane
+  const uint64_t ko = (uint64_t)rj * key_ls + (i & (N - 1));  // V divides N: one plane
   W acc0[HOIST_T][V], acc1[HOIST_T][V];
 #pragma unroll
   for (int t = 0; t < HOIST_T; ++t)
@@ -1996,15 +2006,16 @@ k_hoist_mac(HoistArgs<W> a, const W* __restrict__ d, TabPtrs<W> tp, uint32_t log
 template <class W, bool VEC>
 __global__ void __launch_bounds__(256)
 k_hoist_mac_acc(HoistArgs<W> a, const W* __restrict__ d, TabPtrs<W> tp, uint32_t log_n, uint64_t limb_words,
-                uint64_t key_ls, uint32_t Ls, uint32_t nt) {
+                uint64_t key_ls, uint32_t Ls, uint32_t nt, LimbMap lm) {
   constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
   const uint32_t j = blockIdx.y;
   const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
   if (i >= limb_words) return;
-  const LimbConst<W> lc = tp.lc[j];
+  const uint32_t rj = root_limb(j, lm);
+  const LimbConst<W> lc = tp.lc[rj];
   const uint64_t N = 1ull << log_n;
   const W* dp = d + (uint64_t)j * Ls * limb_words + i;
-  const uint64_t ko = (uint64_t)j * key_ls + (i & (N - 1));  // V divides N: one plane
+  const uint64_t ko = (uint64_t)rj * key_ls + (i & (N - 1));  // V divides N: one plane
   const uint64_t g = (uint64_t)j * limb_words + i;
   W acc0[HOIST_T][V], acc1[HOIST_T][V];
 #pragma unroll
@@ -2109,7 +2120,8 @@ template <class W, bool VEC, int AMAX>
 __global__ void __launch_bounds__(256)
 k_modup(W* __restrict__ D, const W* __restrict__ x, TabPtrs<W> tp, const W* __restrict__ yinv,
         const W* __restrict__ yinvp, const W* __restrict__ conv, const W* __restrict__ convp,
-        uint64_t limb_words, uint64_t src_ls, uint32_t alpha, uint32_t Lv, uint32_t LE, uint32_t tper) {
+        uint64_t limb_words, uint64_t src_ls, uint32_t alpha, uint32_t Lv, uint32_t LE, uint32_t tper,
+        LimbMap lm) {
   constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
   const uint32_t d = blockIdx.y;
   const uint32_t t0 = blockIdx.z * tper;
@@ -2128,14 +2140,14 @@ k_modup(W* __restrict__ D, const W* __restrict__ x, TabPtrs<W> tp, const W* __re
       if ((uint32_t)a < cnt) {  // (uniform)
         W xv[V];
         ld_vec<W, VEC, V>(xv, xp + (uint64_t)a * src_ls);
-        const W q = tp.lc[first + a].q, c = yinv[first + a], cp = yinvp[first + a];
+        const W q = tp.lc[root_limb(first + a, lm)].q, c = yinv[first + a], cp = yinvp[first + a];
 #pragma unroll
         for (int v = 0; v < V; ++v) y[a][v] = shoup_mul<W>(xv[v], c, cp, q);
       }
     }
   }
   for (uint32_t t = t0; t < t1; ++t) {
-    const W q = tp.lc[t].q;
+    const W q = tp.lc[root_limb(t, lm)].q;
     W acc[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) acc[v] = (W)0;
@@ -2152,7 +2164,7 @@ k_modup(W* __restrict__ D, const W* __restrict__ x, TabPtrs<W> tp, const W* __re
       for (uint32_t a = 0; a < cnt; ++a) {
         W xv[V];
         ld_vec<W, VEC, V>(xv, xp + (uint64_t)a * src_ls);
-        const W qs = tp.lc[first + a].q, ci = yinv[first + a], cip = yinvp[first + a];
+        const W qs = tp.lc[root_limb(first + a, lm)].q, ci = yinv[first + a], cip = yinvp[first + a];
         const W c = crow[(uint64_t)a * LE + t], cp = prow[(uint64_t)a * LE + t];
 #pragma unroll
         for (int v = 0; v < V; ++v)
@@ -2176,7 +2188,7 @@ __global__ void __launch_bounds__(256)
 k_moddown(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A, uint64_t a_ls, const W* add,
           uint64_t add_ls, TabPtrs<W> tp, const W* __restrict__ pinv, const W* __restrict__ pinvp,
           const W* __restrict__ pq, const W* __restrict__ pqp, const W* __restrict__ Pinv,
-          const W* __restrict__ Pinvp, uint64_t limb_words, uint32_t Lv, uint32_t K, uint32_t jper) {
+          const W* __restrict__ Pinvp, uint64_t limb_words, uint32_t Lv, uint32_t K, uint32_t jper, LimbMap lm) {
   constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
   const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
   if (i >= limb_words) return;
@@ -2190,14 +2202,14 @@ k_moddown(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A, uint64_
       if ((uint32_t)k < K) {  // (uniform)
         W av[V];
         ld_vec<W, VEC, V>(av, sp + (uint64_t)k * a_ls);
-        const W p = tp.lc[Lv + k].q, c = pinv[k], cp = pinvp[k];
+        const W p = tp.lc[root_limb(Lv + k, lm)].q, c = pinv[k], cp = pinvp[k];
 #pragma unroll
         for (int v = 0; v < V; ++v) z[k][v] = shoup_mul<W>(av[v], c, cp, p);
       }
     }
   }
   for (uint32_t j = j0; j < j1; ++j) {
-    const W q = tp.lc[j].q;
+    const W q = tp.lc[root_limb(j, lm)].q;
     W cv[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) cv[v] = (W)0;
@@ -2214,7 +2226,7 @@ k_moddown(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A, uint64_
       for (uint32_t k = 0; k < K; ++k) {
         W av[V];
         ld_vec<W, VEC, V>(av, sp + (uint64_t)k * a_ls);
-        const W p = tp.lc[Lv + k].q, ci = pinv[k], cip = pinvp[k];
+        const W p = tp.lc[root_limb(Lv + k, lm)].q, ci = pinv[k], cip = pinvp[k];
         const W c = pq[(uint64_t)k * Lv + j], cp = pqp[(uint64_t)k * Lv + j];
 #pragma unroll
         for (int v = 0; v < V; ++v)
@@ -2245,8 +2257,8 @@ __device__ __forceinline__ void moddown_limb(W (&r)[V], uint32_t j, const W (&z)
                                              const TabPtrs<W>& tp, const W* __restrict__ pinv,
                                              const W* __restrict__ pinvp, const W* __restrict__ pq,
                                              const W* __restrict__ pqp, const W* __restrict__ Pinv,
-                                             const W* __restrict__ Pinvp, uint64_t i, uint32_t Lv, uint32_t K) {
-  const W q = tp.lc[j].q;
+                                             const W* __restrict__ Pinvp, uint64_t i, uint32_t Lv, uint32_t K, LimbMap lm) {
+  const W q = tp.lc[root_limb(j, lm)].q;
   W cv[V];
 #pragma unroll
   for (int v = 0; v < V; ++v) cv[v] = (W)0;
@@ -2264,7 +2276,7 @@ __device__ __forceinline__ void moddown_limb(W (&r)[V], uint32_t j, const W (&z)
     for (uint32_t k = 0; k < K; ++k) {
       W av[V];
       ld_vec<W, VEC, V>(av, sp + (uint64_t)k * a_ls);
-      const W p = tp.lc[Lv + k].q, ci = pinv[k], cip = pinvp[k];
+      const W p = tp.lc[root_limb(Lv + k, lm)].q, ci = pinv[k], cip = pinvp[k];
       const W c = pq[(uint64_t)k * Lv + j], cp = pqp[(uint64_t)k * Lv + j];
 #pragma unroll
       for (int v = 0; v < V; ++v)
@@ -2299,7 +2311,7 @@ k_moddown_rescale(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A,
                   uint64_t add_ls, TabPtrs<W> tp, const W* __restrict__ pinv, const W* __restrict__ pinvp,
                   const W* __restrict__ pq, const W* __restrict__ pqp, const W* __restrict__ Pinv,
                   const W* __restrict__ Pinvp, const W* __restrict__ rinv, const W* __restrict__ rinvp,
-                  uint64_t limb_words, uint32_t Lv, uint32_t K, uint32_t jper) {
+                  uint64_t limb_words, uint32_t Lv, uint32_t K, uint32_t jper, LimbMap lm) {
   constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
   const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
   if (i >= limb_words) return;
@@ -2314,18 +2326,18 @@ k_moddown_rescale(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A,
       if ((uint32_t)k < K) {  // (uniform)
         W av[V];
         ld_vec<W, VEC, V>(av, sp + (uint64_t)k * a_ls);
-        const W p = tp.lc[Lv + k].q, c = pinv[k], cp = pinvp[k];
+        const W p = tp.lc[root_limb(Lv + k, lm)].q, c = pinv[k], cp = pinvp[k];
 #pragma unroll
         for (int v = 0; v < V; ++v) z[k][v] = shoup_mul<W>(av[v], c, cp, p);
       }
     }
   }
   W rl[V];
-  moddown_limb<W, VEC, KMAX, V>(rl, last, z, A, a_ls, add, add_ls, tp, pinv, pinvp, pq, pqp, Pinv, Pinvp, i, Lv, K);
+  moddown_limb<W, VEC, KMAX, V>(rl, last, z, A, a_ls, add, add_ls, tp, pinv, pinvp, pq, pqp, Pinv, Pinvp, i, Lv, K, lm);
   for (uint32_t j = j0; j < j1; ++j) {
     W r[V], o[V];
-    moddown_limb<W, VEC, KMAX, V>(r, j, z, A, a_ls, add, add_ls, tp, pinv, pinvp, pq, pqp, Pinv, Pinvp, i, Lv, K);
-    const LimbConst<W> lc = tp.lc[j];
+    moddown_limb<W, VEC, KMAX, V>(r, j, z, A, a_ls, add, add_ls, tp, pinv, pinvp, pq, pqp, Pinv, Pinvp, i, Lv, K, lm);
+    const LimbConst<W> lc = tp.lc[root_limb(j, lm)];
     const W inv = rinv[j], invp = rinvp[j];
 #pragma unroll
     for (int v = 0; v < V; ++v) {
@@ -2354,15 +2366,16 @@ k_hoist_mac_seed(W* out0, W* out1, const W* __restrict__ key_b,
                  const W* __restrict__ key_a, const W* __restrict__ d, const W* seed_b,
                  const W* seed_a, uint64_t seed_ls, const W* __restrict__ Pw,
                  const W* __restrict__ Pwp, TabPtrs<W> tp, uint32_t log_n, uint64_t limb_words, uint64_t key_ls,
-                 uint32_t Ls, uint32_t Lv) {
+                 uint32_t Ls, uint32_t Lv, LimbMap lm) {
   constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
   const uint32_t j = blockIdx.y;
   const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
   if (i >= limb_words) return;
-  const LimbConst<W> lc = tp.lc[j];
+  const uint32_t rj = root_limb(j, lm);
+  const LimbConst<W> lc = tp.lc[rj];
   const uint64_t N = 1ull << log_n;
   const W* dp = d + (uint64_t)j * Ls * limb_words + i;
-  const uint64_t ko = (uint64_t)j * key_ls + (i & (N - 1));  // V divides N: one plane
+  const uint64_t ko = (uint64_t)rj * key_ls + (i & (N - 1));  // V divides N: one plane
   W acc0[V], acc1[V];
   if (j < Lv) {  // (uniform)
     W s0[V], s1[V];
@@ -2416,7 +2429,7 @@ k_moddown_auto(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A, ui
                const W* __restrict__ add, uint64_t add_ls, TabPtrs<W> tp, const W* __restrict__ pinv,
                const W* __restrict__ pinvp, const W* __restrict__ pq, const W* __restrict__ pqp,
                const W* __restrict__ Pinv, const W* __restrict__ Pinvp, uint64_t limb_words, uint32_t log_n,
-               uint32_t g, uint32_t Lv, uint32_t K, uint32_t jper) {
+               uint32_t g, uint32_t Lv, uint32_t K, uint32_t jper, LimbMap lm) {
   constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
   const uint64_t i = xcd_gid() * V;
   if (i >= limb_words) return;
@@ -2440,14 +2453,14 @@ k_moddown_auto(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A, ui
       if ((uint32_t)k < K) {  // (uniform)
         W av[V];
         ld_vec<W, VEC, V>(av, sp + (uint64_t)k * a_ls);
-        const W p = tp.lc[Lv + k].q, c = pinv[k], cp = pinvp[k];
+        const W p = tp.lc[root_limb(Lv + k, lm)].q, c = pinv[k], cp = pinvp[k];
 #pragma unroll
         for (int v = 0; v < V; ++v) z[k][v] = shoup_mul<W>(av[v], c, cp, p);
       }
     }
   }
   for (uint32_t j = j0; j < j1; ++j) {
-    const W q = tp.lc[j].q;
+    const W q = tp.lc[root_limb(j, lm)].q;
     W cv[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) cv[v] = (W)0;
@@ -2464,7 +2477,7 @@ k_moddown_auto(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A, ui
       for (uint32_t k = 0; k < K; ++k) {
         W av[V];
         ld_vec<W, VEC, V>(av, sp + (uint64_t)k * a_ls);
-        const W p = tp.lc[Lv + k].q, ci = pinv[k], cip = pinvp[k];
+        const W p = tp.lc[root_limb(Lv + k, lm)].q, ci = pinv[k], cip = pinvp[k];
         const W c = pq[(uint64_t)k * Lv + j], cp = pqp[(uint64_t)k * Lv + j];
 #pragma unroll
         for (int v = 0; v < V; ++v)
@@ -2711,7 +2724,7 @@ template <class W, bool LZ>
 static hipError_t col_fwd_t(const Launch& k, void* out0, const void* in0, void* out1,
                             const void* in1, uint64_t in_ls, uint64_t out_ls) {
   const Geom g = geom_for(k.t->log_n);
-  const TabPtrs<W> tp = tab_ptrs<W>(k.t);
+  const TabPtrs<W> tp = tab_ptrs<W>(k.t, k.tab0);
   if ((uint64_t)k.L * k.B == 0) return hipSuccess;
   if (g.log_r >= 5) {
     const dim3 grid = col_grid(k, g, (uint32_t)k.L, 1);
@@ -2753,7 +2766,7 @@ static hipError_t col_inv_t(const Launch& k, void* out, uint64_t out_ls, const v
   rs.invp = (const W*)ra.invp;
   rs.limb0 = ra.limb0;
   const Geom g = geom_for(k.t->log_n);
-  const TabPtrs<W> tp = tab_ptrs<W>(k.t);
+  const TabPtrs<W> tp = tab_ptrs<W>(k.t, k.tab0);
   if ((uint64_t)k.L * k.B == 0) return hipSuccess;
   if (g.log_r >= 5) {
     const dim3 grid = col_grid(k, g, (uint32_t)k.L, 1);
@@ -2800,7 +2813,7 @@ static hipError_t row_launch(const Launch& k, void* x, const void* y, uint64_t l
   hipError_t e = allow_lds(k_row<W, MODE, LOG_C, LZ, WHOLE>, lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_row<W, MODE, LOG_C, LZ, WHOLE>), dim3((unsigned)blocks), dim3(G::THREADS), lds, k.s,
-                     (W*)x, (const W*)y, (W*)(out ? out : x), tab_ptrs<W>(k.t), WHOLE ? (uint32_t)LOG_C : g.log_n,
+                     (W*)x, (const W*)y, (W*)(out ? out : x), tab_ptrs<W>(k.t, k.tab0), WHOLE ? (uint32_t)LOG_C : g.log_n,
                      (uint32_t)k.B, ls, rows);
   return hipGetLastError();
 }
@@ -2982,6 +2995,13 @@ static hipError_t hoist_digits_t(const Launch& k, void* D, const void* c1, uint6
   return hipGetLastError();
 }
 
+// The limb map of a launch over a level view (Launch::map_level / map_gap) and
+// its bound: the last working limb's root limb is one of the tables'.
+static LimbMap limb_map(const Launch& k) { return LimbMap{k.map_level, k.map_gap}; }
+static bool limb_map_ok(const Launch& k) {
+  return k.L <= k.t->L && (k.L <= k.map_level || k.L + k.map_gap <= k.t->L);
+}
+
 template <class W>
 static hipError_t hoist_mac_t(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt,
                               const void* d, const void* const* key_a, const void* const* key_b,
@@ -2989,7 +3009,8 @@ static hipError_t hoist_mac_t(const Launch& k, void* const* acc0, void* const* a
   const uint64_t N = 1ull << k.t->log_n;
   const uint64_t limb_words = (uint64_t)k.B * N;
   const size_t Ls = k.src_limbs();
-  if (nt == 0 || nt > (uint32_t)HOIST_T || Ls == 0 || key_ls < Ls * N) return hipErrorInvalidValue;
+  if (nt == 0 || nt > (uint32_t)HOIST_T || Ls == 0 || key_ls < Ls * N || !limb_map_ok(k))
+    return hipErrorInvalidValue;
   if (limb_words == 0 || k.L == 0) return hipSuccess;
   constexpr int V = 16 / (int)sizeof(W);
   HoistArgs<W> a{};
@@ -3009,7 +3030,7 @@ static hipError_t hoist_mac_t(const Launch& k, void* const* acc0, void* const* a
   const dim3 grid((unsigned)bx, (unsigned)k.L);
 #define RNT_HM(KERNEL, VEC)                                                                      \
   hipLaunchKernelGGL((KERNEL<W, VEC>), grid, dim3(256), 0, k.s, a, (const W*)d,                  \
-                     tab_ptrs<W>(k.t), k.t->log_n, limb_words, key_ls, (uint32_t)Ls, nt)
+                     tab_ptrs<W>(k.t), k.t->log_n, limb_words, key_ls, (uint32_t)Ls, nt, limb_map(k))
   if (accum) {
     if (vec) RNT_HM(k_hoist_mac_acc, true); else RNT_HM(k_hoist_mac_acc, false);
   } else {
@@ -3026,7 +3047,7 @@ template <class W>
 static hipError_t modup_t(const Launch& k, void* D, const void* x, uint64_t src_ls, const HybridConsts& hc) {
   const uint64_t N = 1ull << k.t->log_n;
   const uint64_t limb_words = (uint64_t)k.B * N;
-  if (hc.alpha == 0 || hc.beta == 0 || hc.Lv == 0 || k.L != (size_t)hc.Lv + hc.K || k.L > k.t->L ||
+  if (hc.alpha == 0 || hc.beta == 0 || hc.Lv == 0 || k.L != (size_t)hc.Lv + hc.K || !limb_map_ok(k) ||
       (uint64_t)hc.beta * hc.alpha < hc.Lv || (uint64_t)(hc.beta - 1) * hc.alpha >= hc.Lv || src_ls < limb_words)
     return hipErrorInvalidValue;
   if (limb_words == 0) return hipSuccess;
@@ -3044,7 +3065,8 @@ static hipError_t modup_t(const Launch& k, void* D, const void* x, uint64_t src_
 #define RNT_MU(VEC, AMAX)                                                                              \
   hipLaunchKernelGGL((k_modup<W, VEC, AMAX>), grid, dim3(256), 0, k.s, (W*)D, (const W*)x,             \
                      tab_ptrs<W>(k.t), (const W*)hc.yinv, (const W*)hc.yinvp, (const W*)hc.conv,       \
-                     (const W*)hc.convp, limb_words, src_ls, hc.alpha, hc.Lv, (uint32_t)k.L, tper)
+                     (const W*)hc.convp, limb_words, src_ls, hc.alpha, hc.Lv, (uint32_t)k.L, tper,    \
+                     limb_map(k))
 #define RNT_MU_A(AMAX) do { if (vec) RNT_MU(true, AMAX); else RNT_MU(false, AMAX); } while (0)
   if (hc.alpha <= 4) RNT_MU_A(4);
   else if (hc.alpha <= 8) RNT_MU_A(8);
@@ -3060,7 +3082,7 @@ static hipError_t moddown_t(const Launch& k, void* out, uint64_t out_ls, const v
                             const void* add, uint64_t add_ls, const HybridConsts& hc) {
   const uint64_t N = 1ull << k.t->log_n;
   const uint64_t limb_words = (uint64_t)k.B * N;
-  if (hc.Lv == 0 || hc.K == 0 || k.L != (size_t)hc.Lv + hc.K || k.L > k.t->L || out_ls < limb_words ||
+  if (hc.Lv == 0 || hc.K == 0 || k.L != (size_t)hc.Lv + hc.K || !limb_map_ok(k) || out_ls < limb_words ||
       a_ls < limb_words || (add && add_ls < limb_words))
     return hipErrorInvalidValue;
   if (limb_words == 0) return hipSuccess;
@@ -3077,7 +3099,7 @@ static hipError_t moddown_t(const Launch& k, void* out, uint64_t out_ls, const v
   hipLaunchKernelGGL((k_moddown<W, VEC, KMAX>), grid, dim3(256), 0, k.s, (W*)out, out_ls,               \
                      (const W*)A, a_ls, (const W*)add, add_ls, tab_ptrs<W>(k.t), (const W*)hc.pinv,     \
                      (const W*)hc.pinvp, (const W*)hc.pq, (const W*)hc.pqp, (const W*)hc.Pinv,          \
-                     (const W*)hc.Pinvp, limb_words, hc.Lv, hc.K, jper)
+                     (const W*)hc.Pinvp, limb_words, hc.Lv, hc.K, jper, limb_map(k))
 #define RNT_MD_K(KMAX) do { if (vec) RNT_MD(true, KMAX); else RNT_MD(false, KMAX); } while (0)
   if (hc.K <= 4) RNT_MD_K(4);
   else if (hc.K <= 8) RNT_MD_K(8);
@@ -3095,7 +3117,7 @@ static hipError_t moddown_rescale_t(const Launch& k, void* out, uint64_t out_ls,
                                     const HybridConsts& hc) {
   const uint64_t N = 1ull << k.t->log_n;
   const uint64_t limb_words = (uint64_t)k.B * N;
-  if (hc.Lv < 2 || hc.K == 0 || k.L != (size_t)hc.Lv + hc.K || k.L > k.t->L || out_ls < limb_words ||
+  if (hc.Lv < 2 || hc.K == 0 || k.L != (size_t)hc.Lv + hc.K || !limb_map_ok(k) || out_ls < limb_words ||
       a_ls < limb_words || (add && add_ls < limb_words) || !rinv || !rinvp)
     return hipErrorInvalidValue;
   if (limb_words == 0) return hipSuccess;
@@ -3113,7 +3135,8 @@ static hipError_t moddown_rescale_t(const Launch& k, void* out, uint64_t out_ls,
   hipLaunchKernelGGL((k_moddown_rescale<W, VEC, KMAX>), grid, dim3(256), 0, k.s, (W*)out, out_ls,       \
                      (const W*)A, a_ls, (const W*)add, add_ls, tab_ptrs<W>(k.t), (const W*)hc.pinv,     \
                      (const W*)hc.pinvp, (const W*)hc.pq, (const W*)hc.pqp, (const W*)hc.Pinv,          \
-                     (const W*)hc.Pinvp, (const W*)rinv, (const W*)rinvp, limb_words, hc.Lv, hc.K, jper)
+                     (const W*)hc.Pinvp, (const W*)rinv, (const W*)rinvp, limb_words, hc.Lv, hc.K, jper,    \
+                     limb_map(k))
 #define RNT_MR_K(KMAX) do { if (vec) RNT_MR(true, KMAX); else RNT_MR(false, KMAX); } while (0)
   if (hc.K <= 4) RNT_MR_K(4);
   else if (hc.K <= 8) RNT_MR_K(8);
@@ -3131,7 +3154,7 @@ static hipError_t hoist_mac_seed_t(const Launch& k, void* acc0, void* acc1, cons
   const uint64_t N = 1ull << k.t->log_n;
   const uint64_t limb_words = (uint64_t)k.B * N;
   const size_t Ls = k.src_limbs();
-  if (Ls == 0 || key_ls < Ls * N || hc.Lv == 0 || k.L != (size_t)hc.Lv + hc.K || k.L > k.t->L ||
+  if (Ls == 0 || key_ls < Ls * N || hc.Lv == 0 || k.L != (size_t)hc.Lv + hc.K || !limb_map_ok(k) ||
       seed_ls < limb_words || !seed_a || !seed_b || !hc.Pw || !hc.Pwp)
     return hipErrorInvalidValue;
   if (limb_words == 0) return hipSuccess;
@@ -3148,7 +3171,7 @@ static hipError_t hoist_mac_seed_t(const Launch& k, void* acc0, void* acc1, cons
   hipLaunchKernelGGL((k_hoist_mac_seed<W, VEC>), grid, dim3(256), 0, k.s, (W*)acc0, (W*)acc1,            \
                      (const W*)key_b, (const W*)key_a, (const W*)d, (const W*)seed_b, (const W*)seed_a,  \
                      seed_ls, (const W*)hc.Pw, (const W*)hc.Pwp, tab_ptrs<W>(k.t), k.t->log_n,           \
-                     limb_words, key_ls, (uint32_t)Ls, hc.Lv)
+                     limb_words, key_ls, (uint32_t)Ls, hc.Lv, limb_map(k))
   if (vec) RNT_HS(true); else RNT_HS(false);
 #undef RNT_HS
   return hipGetLastError();
@@ -3161,7 +3184,7 @@ static hipError_t moddown_auto_t(const Launch& k, void* out, uint64_t out_ls, co
                                  const void* add, uint64_t add_ls, uint64_t g, const HybridConsts& hc) {
   const uint64_t N = 1ull << k.t->log_n;
   const uint64_t limb_words = (uint64_t)k.B * N;
-  if (hc.Lv == 0 || hc.K == 0 || k.L != (size_t)hc.Lv + hc.K || k.L > k.t->L || out_ls < limb_words ||
+  if (hc.Lv == 0 || hc.K == 0 || k.L != (size_t)hc.Lv + hc.K || !limb_map_ok(k) || out_ls < limb_words ||
       a_ls < limb_words || (add && add_ls < limb_words) || (g & 1) == 0 || g >= 2 * N)
     return hipErrorInvalidValue;
   if (limb_words == 0) return hipSuccess;
@@ -3178,7 +3201,8 @@ static hipError_t moddown_auto_t(const Launch& k, void* out, uint64_t out_ls, co
   hipLaunchKernelGGL((k_moddown_auto<W, VEC, KMAX>), grid, dim3(256), 0, k.s, (W*)out, out_ls,           \
                      (const W*)A, a_ls, (const W*)add, add_ls, tab_ptrs<W>(k.t), (const W*)hc.pinv,      \
                      (const W*)hc.pinvp, (const W*)hc.pq, (const W*)hc.pqp, (const W*)hc.Pinv,           \
-                     (const W*)hc.Pinvp, limb_words, k.t->log_n, (uint32_t)g, hc.Lv, hc.K, jper)
+                     (const W*)hc.Pinvp, limb_words, k.t->log_n, (uint32_t)g, hc.Lv, hc.K, jper,    \
+                     limb_map(k))
 #define RNT_MA_K(KMAX) do { if (vec) RNT_MA(true, KMAX); else RNT_MA(false, KMAX); } while (0)
   // (no 16-limb tier: with the destination offsets beside 16 z_k it spills
   // scalar registers; more than 8 special primes take the recomputing form)

@@ -1600,8 +1600,9 @@ static hipError_t launch_ntt_t(const Launch& k, const void* fn, void* data, uint
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf::kLdsBytes);
   if (e != hipSuccess) return e;
   uint32_t* d = (uint32_t*)data;
-  const void* mft = k.t->mf;
-  const LimbConst<uint32_t>* lcs = (const LimbConst<uint32_t>*)k.t->lconst;
+  // limb l of the launch reads the tables of root limb k.tab0 + l
+  const void* mft = (const mf::v4i*)k.t->mf + (size_t)k.tab0 * mf::kLimb;
+  const LimbConst<uint32_t>* lcs = (const LimbConst<uint32_t>*)k.t->lconst + k.tab0;
   void* args[] = {&d, &mft, &lcs, &ls};
   return hipLaunchKernel(fn, dim3((unsigned)k.B, (unsigned)k.L), dim3(mf::kT), args, mf::kLdsBytes, k.s);
 }

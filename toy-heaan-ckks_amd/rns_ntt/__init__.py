@@ -195,6 +195,21 @@ class RnsBasis:
         check(load().rnt_ctx_drop_last(self._h, drop_count, ctypes.byref(h)))
         return RnsBasis._from_handle(h, self)
 
+    def hybrid_level(self, n_special: int, level: int) -> "RnsBasis":
+        """The level basis ``q_0..q_{level-1}, p_0..p_{K-1}`` of this hybrid
+        key basis (its last ``K = n_special`` limbs the special primes), on
+        this basis' own tables (rnt_ctx_hybrid_level).  It holds key level
+        views alone (:meth:`RnsHybridKey.at_level`).  One object per
+        ``(n_special, level)``: the hybrid calls compare the handles of the
+        key halves and sets, so every key at a level must share it."""
+        cache = self.__dict__.setdefault("_levels", {})
+        at = (int(n_special), int(level))
+        if at not in cache:
+            h = ctypes.c_void_p()
+            check(load().rnt_ctx_hybrid_level(self._h, at[0], at[1], ctypes.byref(h)))
+            cache[at] = RnsBasis._from_handle(h, self)
+        return cache[at]
+
     def total_bits(self) -> int:
         r = ctypes.c_uint32(0)
         check(load().rnt_ctx_total_bits(self._h, ctypes.byref(r)))
@@ -340,6 +355,23 @@ class RnsPoly:
         contents are unspecified until the op (which writes every word)
         fills it, so no zero fill is queued (rnt_buf_alloc_uninit)."""
         return RnsPoly(basis or self.basis, self.n_polys if self.batched else None, _uninit=True)
+
+    @classmethod
+    def _key_level_view(cls, key_polys: "RnsPoly", level_basis: RnsBasis, alpha: int) -> "RnsPoly":
+        """A read-only view of a prepared hybrid key's (or key set's) polys at
+        the level of ``level_basis`` (rnt_key_level_view): no copy; it keeps
+        ``key_polys`` alive and serves as a hybrid key argument alone."""
+        h = ctypes.c_void_p()
+        check(load().rnt_key_level_view(key_polys.handle, level_basis.handle, int(alpha), ctypes.byref(h)))
+        self = cls.__new__(cls)
+        self._h = h
+        self.basis = level_basis
+        self._view_of = key_polys
+        n = ctypes.c_size_t(0)
+        check(load().rnt_buf_n_polys(h, ctypes.byref(n)))
+        self.n_polys = int(n.value)
+        self.batched = True
+        return self
 
     # -- constructors (poly.rs:34-114) --------------------------------------
     @classmethod
@@ -681,17 +713,54 @@ class RnsHybridKey:
     :meth:`prepare_hoisted`) the hoisting form of the hoisted hybrid
     rotations."""
 
-    def __init__(self, a: RnsPoly, b: RnsPoly, alpha: int, rotation: Optional[int] = None):
+    def __init__(self, a: RnsPoly, b: RnsPoly, alpha: int, rotation: Optional[int] = None,
+                 n_special: Optional[int] = None):
         if int(alpha) < 1:
             raise ValueError("RnsHybridKey: alpha must be at least 1")
         if a.basis is not b.basis and a.basis.moduli() != b.basis.moduli():
             raise ValueError("RnsHybridKey: the key halves are on different bases")
+        if n_special is not None and not 1 <= int(n_special) < a.basis.channel_count():
+            raise ValueError("RnsHybridKey: n_special must be at least 1 and below the basis' limb count")
         self.a = a
         self.b = b
         self.alpha = int(alpha)
         self.rotation = rotation
         self.hoisted = False
+        # the count K of special primes (the basis' last limbs): with it the
+        # hybrid wrappers pick the key's view at a lower-level ciphertext's
+        # level by themselves (at_level); None: the caller restricts, as before
+        self.n_special = None if n_special is None else int(n_special)
+        self.level = None  # a view's level (at_level)
+        self._views = {}
         check(load().rnt_key_prepare(a.handle, b.handle))
+
+    def at_level(self, level: int, n_special: Optional[int] = None) -> "RnsHybridKey":
+        """This key at a lower level, as a VIEW of its device planes
+        (rnt_key_level_view): the key of ``q_0..q_{level-1}`` and the special
+        primes, with no copy and no host trip; it keeps ``alpha``, ``rotation``
+        and ``hoisted`` and holds this key alive.  Cached per level; every key
+        of one extended basis shares the level's basis object
+        (:meth:`RnsBasis.hybrid_level`).  ``n_special`` defaults to the
+        key's."""
+        if self.level is not None:
+            raise ValueError("at_level: the key is a level view already")
+        ns = self.n_special if n_special is None else int(n_special)
+        if ns is None:
+            raise ValueError("at_level: the key carries no n_special; pass it")
+        at = (ns, int(level))
+        if at not in self._views:
+            lb = self.a.basis.hybrid_level(ns, int(level))
+            if self.b.basis is not self.a.basis:
+                raise ValueError("at_level: the key halves must share one basis object")
+            v = RnsHybridKey.__new__(RnsHybridKey)
+            v.a = RnsPoly._key_level_view(self.a, lb, self.alpha)
+            v.b = RnsPoly._key_level_view(self.b, lb, self.alpha)
+            v.alpha, v.rotation, v.hoisted, v.n_special = self.alpha, self.rotation, self.hoisted, ns
+            v.level = int(level)
+            v._views = {}
+            v._parent = self
+            self._views[at] = v
+        return self._views[at]
 
     def prepare_hoisted(self) -> "RnsHybridKey":
         """Turn this rotation key into its hoisting form
@@ -704,14 +773,16 @@ class RnsHybridKey:
             raise ValueError("prepare_hoisted: the key is in hoisting form already")
         check(load().rnt_key_prepare_hoisted(self.a.handle, self.b.handle, int(self.rotation)))
         self.hoisted = True
+        self._views = {}  # (views made before read the new words but carry the old form)
         return self
 
     @classmethod
     def from_channels(cls, a_channels, b_channels, ext_basis: RnsBasis, alpha: int,
-                      rotation: Optional[int] = None) -> "RnsHybridKey":
+                      rotation: Optional[int] = None, n_special: Optional[int] = None) -> "RnsHybridKey":
         """a_channels / b_channels: [beta][L + K][N] coefficient-domain residues."""
         return cls(RnsPoly.from_channels(np.asarray(a_channels, dtype=np.uint64), ext_basis),
-                   RnsPoly.from_channels(np.asarray(b_channels, dtype=np.uint64), ext_basis), alpha, rotation)
+                   RnsPoly.from_channels(np.asarray(b_channels, dtype=np.uint64), ext_basis), alpha, rotation,
+                   n_special)
 
     def restrict(self, ext_basis_lv: RnsBasis) -> "RnsHybridKey":
         """The key of a lower level: ``ext_basis_lv`` is a root basis over
@@ -745,11 +816,26 @@ class RnsHybridKey:
         return out
 
 
+def _at_ct_level(key, ct_basis: RnsBasis):
+    """The key (an RnsHybridKey or RnsHybridKeySet) the call reads for a
+    ciphertext on ``ct_basis``: where it carries ``n_special`` and the
+    ciphertext has fewer limbs than the key's level, its view at that level
+    (at_level); else the key as it is."""
+    ns = getattr(key, "n_special", None)
+    if ns is None or getattr(key, "level", None) is not None or key.a is None:
+        return key
+    lv = ct_basis.channel_count()
+    if lv < key.a.basis.channel_count() - ns:
+        return key.at_level(lv)
+    return key
+
+
 def keyswitch_hybrid(d: RnsPoly, key: RnsHybridKey) -> tuple[RnsPoly, RnsPoly]:
     """The hybrid key-switch sums of a coefficient-domain batch
     (rnt_keyswitch_hybrid): ``acc0 + acc1 s = d s' + small``."""
     _require_class(key, RnsHybridKey, "keyswitch_hybrid")
     _require_form(key, False, "keyswitch_hybrid")
+    key = _at_ct_level(key, d.basis)
     acc0, acc1 = d._like(), d._like()
     check(load().rnt_keyswitch_hybrid(acc0.handle, acc1.handle, d.handle, key.a.handle, key.b.handle, key.alpha))
     return acc0, acc1
@@ -760,6 +846,7 @@ def rotate_ciphertext_hybrid(ct: Ciphertext, rotk: RnsHybridKey) -> Ciphertext:
     the same rotation with less noise, not the gadget call's words."""
     _require_class(rotk, RnsHybridKey, "rotate_ciphertext_hybrid")
     _require_form(rotk, False, "rotate_ciphertext_hybrid")
+    rotk = _at_ct_level(rotk, ct.c0.basis)
     out0, out1 = ct.c0._like(), ct.c0._like()
     check(load().rnt_ct_rotate_hybrid(out0.handle, out1.handle, ct.c0.handle, ct.c1.handle,
                                       int(rotk.rotation or 0), rotk.a.handle, rotk.b.handle, rotk.alpha))
@@ -770,6 +857,7 @@ def mul_ciphertexts_hybrid(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsHybridKey) 
     """mul_ciphertexts_gadget with the hybrid key-switch (rnt_ct_mul_relin_hybrid)."""
     _require_class(rlk, RnsHybridKey, "mul_ciphertexts_hybrid")
     assert ct1.logq == ct2.logq, "logq mismatch in hybrid multiplication"
+    rlk = _at_ct_level(rlk, ct1.c0.basis)
     out0, out1 = ct1.c0._like(), ct1.c0._like()
     check(load().rnt_ct_mul_relin_hybrid(out0.handle, out1.handle, ct1.c0.handle, ct1.c1.handle,
                                          ct2.c0.handle, ct2.c1.handle, rlk.a.handle, rlk.b.handle, rlk.alpha))
@@ -805,6 +893,13 @@ class RnsHybridKeySet:
         self.steps = [0 if k is None else int(k.rotation or 0) for k in keys]
         self.basis = real[0].a.basis if real else None
         self.a = self.b = None
+        if any(k.level is not None for k in real):
+            raise ValueError("RnsHybridKeySet: pack full keys and take the set's view (at_level)")
+        if len({k.n_special for k in real}) > 1:
+            raise ValueError("RnsHybridKeySet: the keys carry different n_special")
+        self.n_special = real[0].n_special if real else None
+        self.level = None  # a view's level (at_level)
+        self._views = {}
         if real:
             beta = real[0].a.n_polys
             for k in real:
@@ -821,6 +916,29 @@ class RnsHybridKeySet:
                 if k is not None:
                     self.a.copy_polys(k.a, t * beta, 0, beta)
                     self.b.copy_polys(k.b, t * beta, 0, beta)
+
+    def at_level(self, level: int) -> "RnsHybridKeySet":
+        """This set at a lower level, as a view of its packed planes
+        (rnt_key_level_view; step t's key at ``[t beta', (t + 1) beta')`` of
+        the view): no copy; it keeps ``alpha``, the steps and ``hoisted`` and
+        holds this set alive.  Cached per level.  The keys must carry
+        ``n_special``; a set without any key is its own view."""
+        if self.level is not None:
+            raise ValueError("at_level: the set is a level view already")
+        if self.a is None:
+            return self
+        if self.n_special is None:
+            raise ValueError("at_level: the set's keys carry no n_special")
+        level = int(level)
+        if level not in self._views:
+            lb = self.basis.hybrid_level(self.n_special, level)
+            v = RnsHybridKeySet.__new__(RnsHybridKeySet)
+            v.hoisted, v.alpha, v.steps, v.basis = self.hoisted, self.alpha, list(self.steps), lb
+            v.a = RnsPoly._key_level_view(self.a, lb, self.alpha)
+            v.b = RnsPoly._key_level_view(self.b, lb, self.alpha)
+            v.n_special, v.level, v._views, v._parent = self.n_special, level, {}, self
+            self._views[level] = v
+        return self._views[level]
 
     def __len__(self) -> int:
         return len(self.steps)
@@ -842,6 +960,7 @@ def rotate_ciphertext_hybrid_hoisted(ct: Ciphertext, keyset: RnsHybridKeySet,
     Valid rotations with ``rotate_ciphertext_hybrid``'s noise, not its
     words."""
     _require_hybrid_set(keyset, True, "rotate_ciphertext_hybrid_hoisted")
+    keyset = _at_ct_level(keyset, ct.c0.basis)
     basis = ct.c0.basis
     n_out = len(keyset.steps) * ct.c0.n_polys
     if out is None:
@@ -864,6 +983,8 @@ def linear_transform_bsgs_hybrid(ct: Ciphertext, diag: RnsPoly, baby_keyset: Rns
     _require_hybrid_set(giant_keyset, False, "linear_transform_bsgs_hybrid (giant keys)")
     if baby_keyset.alpha != giant_keyset.alpha:
         raise ValueError("linear_transform_bsgs_hybrid: the two key sets were generated for different alpha")
+    baby_keyset = _at_ct_level(baby_keyset, ct.c0.basis)
+    giant_keyset = _at_ct_level(giant_keyset, ct.c0.basis)
     basis = ct.c0.basis
     if out is None:
         out = Ciphertext(ct.c0._like(basis), ct.c0._like(basis), ct.logp, ct.logq)
@@ -1068,6 +1189,7 @@ def mul_ciphertexts_hybrid_rescale(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsHyb
     the un-rescaled product never reaches memory."""
     _require_class(rlk, RnsHybridKey, "mul_ciphertexts_hybrid_rescale")
     assert ct1.logq == ct2.logq, "logq mismatch in hybrid multiplication"
+    rlk = _at_ct_level(rlk, ct1.c0.basis)
     q_last = ct1.c0.basis.moduli()[-1]
     bits_dropped = q_last.bit_length()
     new_basis = ct1.c0.basis.drop_last(1)
@@ -1087,6 +1209,8 @@ def linear_transform_bsgs_hybrid_rescale(ct: Ciphertext, diag: RnsPoly, baby_key
     _require_hybrid_set(giant_keyset, False, "linear_transform_bsgs_hybrid_rescale (giant keys)")
     if baby_keyset.alpha != giant_keyset.alpha:
         raise ValueError("linear_transform_bsgs_hybrid_rescale: the two key sets were generated for different alpha")
+    baby_keyset = _at_ct_level(baby_keyset, ct.c0.basis)
+    giant_keyset = _at_ct_level(giant_keyset, ct.c0.basis)
     q_last = ct.c0.basis.moduli()[-1]
     bits_dropped = q_last.bit_length()
     new_basis = ct.c0.basis.drop_last(1)

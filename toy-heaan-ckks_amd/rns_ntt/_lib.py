@@ -151,6 +151,8 @@ SIGNATURES = {
     "rnt_ct_rotate_hoisted": (c_int, [_P, _P, _P, _P, POINTER(c_int32), c_size_t, _P, _P]),
     "rnt_ct_linear_bsgs_hoisted": (c_int, [_P, _P, _P, _P, POINTER(c_int32), c_size_t, POINTER(c_int32), c_size_t,
                                            _P, _P, _P, _P, _P]),
+    "rnt_ctx_hybrid_level": (c_int, [_P, c_size_t, c_size_t, POINTER(_P)]),
+    "rnt_key_level_view": (c_int, [_P, _P, c_size_t, POINTER(_P)]),
     "rnt_keyswitch_hybrid": (c_int, [_P, _P, _P, _P, _P, c_size_t]),
     "rnt_ct_rotate_hybrid": (c_int, [_P, _P, _P, _P, c_int32, _P, _P, c_size_t]),
     "rnt_ct_mul_relin_hybrid": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_size_t]),

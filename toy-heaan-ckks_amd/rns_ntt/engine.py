@@ -182,7 +182,7 @@ class CkksEngine:
         else:
             e = RnsPoly.from_coeffs(self._gaussian(rng, beta), self.ext_basis)
         b = -(a * s_rep) + e + RnsPoly.from_channels(plain, self.ext_basis)
-        return RnsHybridKey(a, b, alpha, rotation)
+        return RnsHybridKey(a, b, alpha, rotation, n_special=K)
 
     def generate_hybrid_relin_key(self, sk: RnsPoly, rng, alpha: int) -> RnsHybridKey:
         return self._hybrid_key(sk, sk * sk, rng, alpha)
