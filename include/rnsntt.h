@@ -92,7 +92,7 @@ int rnt_device_count(int* n);
  * "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd",
  * "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
  * "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown",
- * "moddown_auto", "moddown_rescale"), the launch count and summed device milliseconds since enabling. */
+ * "moddown_auto", "moddown_rescale", "lincomb"), the launch count and summed device milliseconds since enabling. */
 int rnt_profile_enable(const rnt_ctx* ctx, int enable);
 int rnt_profile_read(const rnt_ctx* ctx, const char* kernel, uint64_t* launches,
                      double* total_ms);
@@ -619,6 +619,45 @@ int rnt_ct_linear_bsgs_hybrid_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_bu
                                       const int32_t* giant_steps, size_t n_giant, const rnt_buf* diag,
                                       const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
                                       const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b, size_t alpha);
+/* ---- scalar linear combinations of ciphertexts (DESIGN.md "Scalar linear
+ * combinations and polynomial evaluation") --------------------------------
+ * The scalar path of a circuit: ciphertext x constant, ciphertext + constant
+ * and every weighted sum of a set of ciphertexts, n_out of them from n_in
+ * inputs in one launch.  x0, x1: n_in B polys over a context C with Lv limbs,
+ * coefficient domain, term i of ciphertext b at poly i B + b (the layout
+ * rnt_ct_rotate_hybrid_hoisted writes).  weights: host uint64_t[n_out][n_in][Lv],
+ * residues mod q_t; bias: host uint64_t[n_out][Lv] or NULL for none.  For
+ * output j, ciphertext b, limb t, exact mod q_t and canonical:
+ *   r0 = sum_i w[j][i][t] x0_i + bias[j][t] X^0
+ *   r1 = sum_i w[j][i][t] x1_i
+ * (the bias on coefficient 0 of component 0 alone: a constant polynomial is
+ * that constant in every slot).  rnt_ct_lincomb writes (r0, r1): out0 / out1
+ * hold n_out B polys over C, output j of ciphertext b at poly j B + b,
+ * coefficient domain.  No output aliases an input or the other output.
+ * Errors: n_in or n_out of 0, inputs whose poly counts differ or are no
+ * multiple of n_in, outputs of other than n_out B polys, aliasing, null
+ * weights -> RNT_ERR_BAD_ARGUMENT; n_in or n_out above 16 -> RNT_ERR_UNSUPPORTED
+ * (fields 0, 0); a weight or bias >= its modulus -> RNT_ERR_NON_REDUCED
+ * (fields: value, modulus); an NTT-domain input -> RNT_ERR_DOMAIN_MISMATCH;
+ * inputs on different contexts, or an output on another context than the
+ * inputs' -> RNT_ERR_BASIS_MISMATCH; a key level view in any position ->
+ * RNT_ERR_UNSUPPORTED.  A refused call leaves its outputs untouched.
+ * Both host arrays are read during the call (packed into staging memory the
+ * library owns and copied up on the context's stream); the caller may free
+ * them on return.  That host copy is one a graph cannot own, so the call CANNOT
+ * be recorded: between rnt_capture_begin and rnt_capture_end it returns
+ * RNT_ERR_UNSUPPORTED (fields 0, 0) and records nothing. */
+int rnt_ct_lincomb(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1,
+                   size_t n_in, size_t n_out, const uint64_t* weights, const uint64_t* bias);
+/* rnt_ct_lincomb followed by rnt_ct_rescale, word for word: the outputs are
+ * n_out B polys on ONE shared context that is drop_last(1) of C,
+ *   out_t = (r_t - [r_last]_{q_t}) (q_last mod q_t)^-1 mod q_t,  t < Lv - 1,
+ * and r is never written to memory.  Errors as above, then
+ * rnt_ct_mul_relin_rescale's output rules: Lv == 1 -> RNT_ERR_INVALID_MOD_DROP
+ * (fields: 1, Lv); an output whose context is not drop_last(1) of C, or outputs
+ * on two contexts -> RNT_ERR_BASIS_MISMATCH.  Not recordable, as above. */
+int rnt_ct_lincomb_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1,
+                           size_t n_in, size_t n_out, const uint64_t* weights, const uint64_t* bias);
 
 /* ---- limb-sharded building blocks ------------------------ */
 /* A rank owning a contiguous run of the global basis' limbs holds every

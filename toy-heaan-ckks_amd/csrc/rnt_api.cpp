@@ -98,7 +98,7 @@ const char* const kKernelNames[rnt::K_COUNT] = {
     "automorphism", "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt",
     "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
     "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto",
-    "moddown_rescale"};
+    "moddown_rescale", "lincomb"};
 
 // A profiling call failed: clear the runtime's slot, keep the first failure
 // in the profiler, and stop profiling (rnt_profile_read reports it).
@@ -4315,6 +4315,155 @@ extern "C" int rnt_ct_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, c
     return fail(RNT_ERR_BASIS_MISMATCH, "rescale_ciphertext: outputs must share one basis");
   if (int rc = rnt_rescale(out0, c0)) return rc;
   return rnt_rescale(out1, c1);
+}
+
+// ---------------------------------------------------------------------------
+// scalar linear combinations of ciphertexts (k_lincomb)
+// ---------------------------------------------------------------------------
+namespace {
+
+// Pinned host staging for the weights of rnt_ct_lincomb: the caller's arrays
+// are packed here during the call and copied up on the op's stream, so the
+// call neither waits for the device nor leaves a pointer to caller memory
+// behind.  A ring of slots per thread, each behind an event on the stream of
+// its last copy: the host waits only when kLcSlots later calls find the copy of
+// this one still queued.  The slots live as long as the thread.
+constexpr unsigned kLcSlots = 4;
+struct LcSlot {
+  void* p = nullptr;
+  size_t bytes = 0;
+  hipEvent_t ev = nullptr;
+  int device = -1;
+  bool busy = false;
+};
+thread_local LcSlot g_lc_slots[kLcSlots];
+thread_local unsigned g_lc_next = 0;
+
+int lincomb_stage(int device, size_t bytes, LcSlot** out) {
+  LcSlot& s = g_lc_slots[g_lc_next++ % kLcSlots];
+  if (s.busy) {
+    HIP_TRY(hipEventSynchronize(s.ev), "hipEventSynchronize(lincomb weights)");
+    s.busy = false;
+  }
+  if (s.ev && s.device != device) {  // an event records on its own device's streams
+    HIP_TRY(hipEventDestroy(s.ev), "hipEventDestroy(lincomb weights)");
+    s.ev = nullptr;
+  }
+  if (!s.ev) {
+    HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming), "hipEventCreate(lincomb weights)");
+    s.device = device;
+  }
+  if (s.bytes < bytes) {
+    if (s.p) {
+      HIP_TRY(hipHostFree(s.p), "hipHostFree(lincomb weights)");
+      s.p = nullptr;
+      s.bytes = 0;
+    }
+    const size_t cap = std::max<size_t>(bytes, 4096);
+    HIP_TRY(hipHostMalloc(&s.p, cap, hipHostMallocPortable), "hipHostMalloc(lincomb weights)");
+    s.bytes = cap;
+  }
+  *out = &s;
+  return RNT_OK;
+}
+
+template <class W>
+void lincomb_pack(W* dst, const rnt_ctx* ctx, size_t n_in, size_t n_out, const uint64_t* weights,
+                  const uint64_t* bias) {
+  const size_t Lv = ctx->L, nw = Lv * n_out * n_in;
+  const unsigned wbits = sizeof(W) * 8;
+  for (size_t t = 0; t < Lv; ++t) {
+    const uint64_t q = ctx->modulus(t);
+    for (size_t j = 0; j < n_out; ++j) {
+      for (size_t i = 0; i < n_in; ++i) {
+        const uint64_t v = weights[(j * n_in + i) * Lv + t];
+        dst[(t * n_out + j) * n_in + i] = (W)v;
+        dst[nw + (t * n_out + j) * n_in + i] = (W)rnt::host::shoup_companion(v, q, wbits);
+      }
+      if (bias) dst[2 * nw + t * n_out + j] = (W)bias[j * Lv + t];
+    }
+  }
+}
+
+int lincomb_impl(const char* name, bool rescale, rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1,
+                 size_t n_in, size_t n_out, const uint64_t* weights, const uint64_t* bias) {
+  const rnt_buf* all[4] = {out0, out1, x0, x1};
+  for (const rnt_buf* b : all)
+    if (int rc = check_buf(b, name)) return rc;
+  if (n_in == 0 || n_out == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: n_in and n_out must be at least 1", name);
+  if (n_in > rnt::kLincombMax || n_out > rnt::kLincombMax)
+    return fail_fields(RNT_ERR_UNSUPPORTED, 0, 0, "%s: %zu inputs and %zu outputs (at most %zu of either)", name, n_in,
+                       n_out, rnt::kLincombMax);
+  if (!weights) return fail(RNT_ERR_BAD_ARGUMENT, "%s: null weights", name);
+  if (g_capture != nullptr)
+    return fail_fields(RNT_ERR_UNSUPPORTED, 0, 0,
+                       "%s cannot be recorded: its weights go up by a host copy that a graph does not own", name);
+  if (int rc = check_same(x0, x1, name)) return rc;
+  if (x0->n_polys % n_in != 0)
+    return fail(RNT_ERR_BAD_ARGUMENT, "%s: inputs of %zu polys are no %zu terms of a batch", name, x0->n_polys, n_in);
+  const size_t B = x0->n_polys / n_in, Lv = x0->ctx->L;
+  if (x0->in_ntt || x1->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: inputs must be in coefficient domain", name);
+  for (size_t t = 0; t < Lv; ++t) {
+    const uint64_t q = x0->ctx->modulus(t);
+    for (size_t e = 0; e < n_out * n_in; ++e)
+      if (weights[e * Lv + t] >= q)
+        return fail_fields(RNT_ERR_NON_REDUCED, weights[e * Lv + t], q,
+                           "%s: weight %" PRIu64 " is not reduced mod %" PRIu64, name, weights[e * Lv + t], q);
+    for (size_t j = 0; bias && j < n_out; ++j)
+      if (bias[j * Lv + t] >= q)
+        return fail_fields(RNT_ERR_NON_REDUCED, bias[j * Lv + t], q,
+                           "%s: bias %" PRIu64 " is not reduced mod %" PRIu64, name, bias[j * Lv + t], q);
+  }
+  if (rescale && Lv < 2)  // poly.rs:191-197
+    return fail_fields(RNT_ERR_INVALID_MOD_DROP, 1, Lv, "invalid mod-drop count 1 for %zu channels", Lv);
+  for (const rnt_buf* o : {out0, out1}) {
+    if (rescale ? (o->ctx->t != x0->ctx->t || o->ctx->L != Lv - 1) : o->ctx != x0->ctx)
+      return fail(RNT_ERR_BASIS_MISMATCH, "%s: an output's basis is not %s the inputs'", name,
+                  rescale ? "drop_last(1) of" : "");
+    if (o->n_polys != n_out * B)
+      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output of %zu polys for %zu outputs of %zu", name, o->n_polys, n_out, B);
+  }
+  if (out0->ctx != out1->ctx)  // engine.rs:272-274: one shared new basis
+    return fail(RNT_ERR_BASIS_MISMATCH, "%s: outputs must share one basis", name);
+  if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
+  for (const rnt_buf* in : {x0, x1})
+    if (out0 == in || out1 == in || out0->data == in->data || out1->data == in->data)
+      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output aliases an input", name);
+  if (int rc = set_device(x0->ctx)) return rc;
+  rnt::Launch k = launch_for(x0);
+  k.B = B;
+  const size_t wb = word_bytes(k.t);
+  const size_t words = Lv * n_out * (2 * n_in + (bias ? 1 : 0));
+  LcSlot* slot = nullptr;
+  if (int rc = lincomb_stage(k.t->device, words * wb, &slot)) return rc;
+  if (wb == 4) lincomb_pack<uint32_t>((uint32_t*)slot->p, x0->ctx, n_in, n_out, weights, bias);
+  else lincomb_pack<uint64_t>((uint64_t*)slot->p, x0->ctx, n_in, n_out, weights, bias);
+  CallWs cws(out0);
+  if (int rc = cws.get(std::max<size_t>(words * wb, 16))) return rc;
+  HIP_TRY(hipMemcpyAsync(cws.p, slot->p, words * wb, hipMemcpyHostToDevice, k.s), "hipMemcpyAsync(lincomb weights)");
+  HIP_TRY(hipEventRecord(slot->ev, k.s), "hipEventRecord(lincomb weights)");
+  slot->busy = true;
+  const char* w = (const char*)cws.p;
+  const size_t nw = Lv * n_out * n_in * wb;
+  LAUNCH(k.t, rnt::K_LINCOMB,
+         rnt::launch_lincomb(k, out0->data, out1->data, limb_stride(out0), x0->data, x1->data, limb_stride(x0), n_in,
+                             n_out, w, w + nw, bias ? w + 2 * nw : nullptr, rescale),
+         "lincomb");
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
+}  // namespace
+
+extern "C" int rnt_ct_lincomb(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1, size_t n_in,
+                              size_t n_out, const uint64_t* weights, const uint64_t* bias) {
+  return lincomb_impl("rnt_ct_lincomb", false, out0, out1, x0, x1, n_in, n_out, weights, bias);
+}
+
+extern "C" int rnt_ct_lincomb_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1, size_t n_in,
+                                      size_t n_out, const uint64_t* weights, const uint64_t* bias) {
+  return lincomb_impl("rnt_ct_lincomb_rescale", true, out0, out1, x0, x1, n_in, n_out, weights, bias);
 }
 
 // ---------------------------------------------------------------------------

@@ -155,7 +155,7 @@ enum KernelId {
   K_AUTOMORPHISM, K_KS_DECOMPOSE, K_KS_ROWS, K_TENSOR_ROWS, K_IMPORT, K_EXPORT, K_CRT,
   K_SFFT, K_SAMPLE, K_COPY, K_PLANE_FUSED, K_MF_NTT_FWD, K_MF_NTT_INV, K_WHOLE_FWD, K_WHOLE_INV, K_WHOLE_MUL,
   K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_MODUP, K_MODDOWN,
-  K_MODDOWN_AUTO, K_MODDOWN_RESCALE, K_COUNT
+  K_MODDOWN_AUTO, K_MODDOWN_RESCALE, K_LINCOMB, K_COUNT
 };
 
 struct Prof {
@@ -438,6 +438,18 @@ hipError_t launch_moddown_auto(const Launch& k, void* out, uint64_t out_ls, cons
 hipError_t launch_moddown_rescale(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
                                   const void* add, uint64_t add_ls, const void* rinv, const void* rinvp,
                                   const HybridConsts& hc);
+// launch_lincomb (k_lincomb): n_out scalar linear combinations of n_in
+// ciphertexts, both components in one launch.  k.L = Lv limbs of the inputs,
+// k.B ciphertexts; x0 / x1 hold n_in k.B polys a limb at limb stride in_ls
+// (term i at poly i k.B), out0 / out1 n_out k.B at out_ls over Lv limbs, or
+// Lv - 1 with `rescale` (the words of launch_rescale on the sums, which are not
+// written; Lv >= 2).  w / wp: device [Lv][n_out][n_in] weights mod q_t and
+// their Shoup companions; bias: device [Lv][n_out] (coefficient 0 of component
+// 0) or nullptr.  1 <= n_in, n_out <= kLincombMax.
+constexpr size_t kLincombMax = 16;
+hipError_t launch_lincomb(const Launch& k, void* out0, void* out1, uint64_t out_ls, const void* x0, const void* x1,
+                          uint64_t in_ls, size_t n_in, size_t n_out, const void* w, const void* wp, const void* bias,
+                          bool rescale);
 // launch_hoist_mac_seed (k_hoist_mac_seed): launch_hoist_mac for one step whose
 // sums start, on the limbs j < hc.Lv, from seed_b[j] (P 2^w mod q_j) and
 // seed_a[j] (P 2^w mod q_j) and from 0 on the special limbs; the seeds are

@@ -2524,6 +2524,131 @@ k_rescale(W* __restrict__ out, const W* __restrict__ in, const W* __restrict__ l
   }
 }
 
+// Scalar linear combinations of ciphertexts (rnt_ct_lincomb[_rescale]): with
+// x_i the n_in terms of a ciphertext component ([Lv][n_in B][N], term i of
+// ciphertext b at poly i B + b, so at + i ct_words of a limb plane),
+//   r_j = sum_i w[t][j][i] x_i (+ bias[t][j] X^0 on component 0)  mod q_t,
+// canonical, for the n_out outputs j ([.][n_out B][N], output j at + j
+// ct_words).  A lane owns one vector of the B N positions of a ciphertext
+// batch; blockIdx.z is the component (a uniform choice of pointers).  For each
+// limb t of its run it loads its n_in vectors once, forms the n_out sums one
+// after the other (Shoup products by the wave-uniform weights w / wp, read
+// through scalar registers) and stores them: every input plane is read once a
+// run, every output plane written once.  RESCALE: the lane first forms
+// r_last[j] on limb Lv - 1 for every j and then stores
+//   out_j = (r_j - [r_last_j]_{q_t}) (q_last mod q_t)^-1 mod q_t,  t < Lv - 1,
+// reduced as k_rescale reduces it (Shoup product by 1; rinv / rinvp the row of
+// the rescale table k_rescale reads): the words of the un-rescaled kernel
+// followed by k_rescale, the sums never written.  blockIdx.y takes a run of
+// tper limbs; with RESCALE every run recomputes r_last (n_in planes read again,
+// hits of the cache).  The NI >= n_in input vectors of a limb live in registers
+// (the unrolled loop's guard is uniform); the loop over the outputs is a
+// runtime one, so the code does not grow with n_out and the weights of one
+// output are the only scalars held.  The n_out last-limb sums of a lane wait in
+// LDS, 16 bytes per lane and output (lc_rl[j][lane]: lanes side by side, no
+// bank conflict; each lane reads back only what it wrote, so no barrier).  The
+// bias belongs to coefficient 0 of every poly: element 0 of the lane whose
+// position is a multiple of N (V divides N where VEC).
+struct LincombGeom {
+  uint64_t ct_words, in_ls, out_ls;
+  uint32_t n_in, n_out, Lv, tper, nmask;
+};
+
+template <class W, bool VEC, int NI, int V>
+__device__ __forceinline__ void lincomb_load(W (&xv)[NI][V], const W* __restrict__ xp, uint64_t ct_words,
+                                             uint32_t n_in) {
+#pragma unroll
+  for (int ii = 0; ii < NI; ++ii)
+    if ((uint32_t)ii < n_in) ld_vec<W, VEC, V>(xv[ii], xp + (uint64_t)ii * ct_words);  // (uniform)
+}
+
+// Output j's sum on limb t for a lane: wrow = the weights of (t, j).
+template <class W, int NI, int V>
+__device__ __forceinline__ void lincomb_sum(W (&r)[V], const W (&xv)[NI][V], const W* __restrict__ wrow,
+                                            const W* __restrict__ wprow, uint32_t n_in, W bias, W q) {
+#pragma unroll
+  for (int v = 0; v < V; ++v) r[v] = (W)0;
+#pragma unroll
+  for (int ii = 0; ii < NI; ++ii) {
+    if ((uint32_t)ii < n_in) {  // (uniform)
+      const W c = wrow[ii], cp = wprow[ii];
+#pragma unroll
+      for (int v = 0; v < V; ++v) r[v] = add_mod<W>(r[v], shoup_mul<W>(xv[ii][v], c, cp, q), q);
+    }
+  }
+  r[0] = add_mod<W>(r[0], bias, q);
+}
+
+extern __shared__ uint4 lc_rl[];  // RESCALE: [n_out][256] last-limb sums, one 16-byte slot per lane
+
+template <class W, bool VEC, bool RESCALE, int NI>
+__global__ void __launch_bounds__(256)
+k_lincomb(W* __restrict__ out0, W* __restrict__ out1, const W* __restrict__ x0, const W* __restrict__ x1,
+          const W* __restrict__ w, const W* __restrict__ wp, const W* __restrict__ bias,
+          const W* __restrict__ rinv, const W* __restrict__ rinvp, LincombGeom a, TabPtrs<W> tp) {
+  // w, wp: [Lv][n_out][n_in] weights and Shoup companions; bias: [Lv][n_out] or nullptr; rinv, rinvp
+  // (RESCALE): (q_last mod q_t)^-1 mod q_t and companions.  All __restrict__ parameters: the outputs
+  // alias none of them, so the uniform reads stay scalar loads after the first store.
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= a.ct_words) return;
+  const uint32_t comp = blockIdx.z;
+  const W* x = (comp ? x1 : x0) + i;
+  W* out = (comp ? out1 : out0) + i;
+  const bool biased = comp == 0 && bias != nullptr;           // (uniform)
+  const bool bias_lane = biased && ((uint32_t)i & a.nmask) == 0;  // coefficient 0 of a poly
+  const uint32_t lo = RESCALE ? a.Lv - 1 : a.Lv;
+  const uint32_t t0 = blockIdx.y * a.tper;
+  const uint32_t t1 = t0 + a.tper < lo ? t0 + a.tper : lo;
+  const uint32_t wstride = a.n_out * a.n_in;
+  W xv[NI][V];
+  if constexpr (RESCALE) {
+    const uint32_t last = a.Lv - 1;
+    const W q = tp.lc[last].q;
+    lincomb_load<W, VEC, NI, V>(xv, x + (uint64_t)last * a.in_ls, a.ct_words, a.n_in);
+#pragma unroll 1
+    for (uint32_t j = 0; j < a.n_out; ++j) {
+      const uint32_t wj = last * a.n_out + j;
+      const W b = biased ? bias[wj] : (W)0;
+      W r[V];
+      lincomb_sum<W, NI, V>(r, xv, w + (uint64_t)wj * a.n_in, wp + (uint64_t)wj * a.n_in, a.n_in,
+                            bias_lane ? b : (W)0, q);
+      uint4 slot = make_uint4(0, 0, 0, 0);
+      __builtin_memcpy(&slot, r, sizeof(r));
+      lc_rl[j * 256 + threadIdx.x] = slot;
+    }
+  }
+  for (uint32_t t = t0; t < t1; ++t) {
+    const LimbConst<W> lc = tp.lc[t];
+    lincomb_load<W, VEC, NI, V>(xv, x + (uint64_t)t * a.in_ls, a.ct_words, a.n_in);
+    const W* wrow = w + (uint64_t)t * wstride;
+    const W* wprow = wp + (uint64_t)t * wstride;
+    W* op = out + (uint64_t)t * a.out_ls;
+    W inv = (W)0, invp = (W)0;
+    if constexpr (RESCALE) {
+      inv = rinv[t];
+      invp = rinvp[t];
+    }
+#pragma unroll 1
+    for (uint32_t j = 0; j < a.n_out; ++j) {
+      const W b = biased ? bias[t * a.n_out + j] : (W)0;
+      W r[V];
+      lincomb_sum<W, NI, V>(r, xv, wrow + j * a.n_in, wprow + j * a.n_in, a.n_in, bias_lane ? b : (W)0, lc.q);
+      if constexpr (RESCALE) {
+        const uint4 slot = lc_rl[j * 256 + threadIdx.x];
+        W rl[V];
+        __builtin_memcpy(rl, &slot, sizeof(rl));
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const W cl = shoup_mul<W>(rl[v], (W)1, lc.one_p, lc.q);  // canonical r_last mod q_t, as k_rescale's
+          r[v] = shoup_mul<W>(sub_mod<W>(r[v], cl, lc.q), inv, invp, lc.q);
+        }
+      }
+      st_vec<W, VEC, V>(op + (uint64_t)j * a.ct_words, r);
+    }
+  }
+}
+
 // Gather kernels: grid y = limb, x = the limb's B*N words (no per-thread
 // division).  XCD-aware deal along x: hardware block b of a row runs on XCD
 // b % 8 (gridDim.x is a multiple of 8), so logical block (b % 8) *
@@ -3311,6 +3436,62 @@ static hipError_t rescale_ext_t(const Launch& k, void* out, const void* in, cons
   return hipGetLastError();
 }
 
+// k.L = Lv limbs of the inputs, k.B = ciphertexts per term (rnt_internal.hpp).
+// Register tiers: 4, 8 or 16 input vectors a lane; rescaling, 16 bytes of LDS a
+// lane and output.
+// The runs split the output limbs until the grid (two components) has
+// kSplitBlocks workgroups.
+template <class W>
+static hipError_t lincomb_t(const Launch& k, void* out0, void* out1, uint64_t out_ls, const void* x0, const void* x1,
+                            uint64_t in_ls, size_t n_in, size_t n_out, const void* w, const void* wp,
+                            const void* bias, bool rescale) {
+  const uint64_t N = 1ull << k.t->log_n;
+  const uint64_t ct_words = (uint64_t)k.B * N;
+  if (n_in == 0 || n_in > kLincombMax || n_out == 0 || n_out > kLincombMax || k.L == 0 || k.L > k.t->L ||
+      (rescale && k.L < 2) || in_ls < n_in * ct_words || out_ls < n_out * ct_words || !w || !wp || !out0 || !out1 ||
+      !x0 || !x1)
+    return hipErrorInvalidValue;
+  if (ct_words == 0) return hipSuccess;
+  constexpr int V = 16 / (int)sizeof(W);
+  // 16-byte accesses: whole vectors within a plane, every plane and term 16-byte aligned
+  const bool vec = N % V == 0 && in_ls % V == 0 && out_ls % V == 0 &&
+                   ((uintptr_t)out0 | (uintptr_t)out1 | (uintptr_t)x0 | (uintptr_t)x1) % 16 == 0;
+  const uint64_t per = vec ? ct_words / V : ct_words;
+  const uint64_t bx = (per + 255) / 256;
+  if (bx > 0x7fffffffull) return hipErrorInvalidConfiguration;
+  const uint64_t lo = rescale ? k.L - 1 : k.L;
+  const uint64_t runs = std::min<uint64_t>(lo, std::max<uint64_t>(kSplitBlocks / (2 * bx), 1));
+  const uint32_t tper = (uint32_t)((lo + runs - 1) / runs);
+  const dim3 grid((unsigned)bx, (unsigned)((lo + tper - 1) / tper), 2);
+  const TabPtrs<W> tp = tab_ptrs<W>(k.t);
+  LincombGeom a;
+  const W* rinv = tp.resc + (k.L - 1) * tp.Lroot;
+  const W* rinvp = tp.rescp + (k.L - 1) * tp.Lroot;
+  a.ct_words = ct_words;
+  a.in_ls = in_ls;
+  a.out_ls = out_ls;
+  a.n_in = (uint32_t)n_in;
+  a.n_out = (uint32_t)n_out;
+  a.Lv = (uint32_t)k.L;
+  a.tper = tper;
+  a.nmask = (uint32_t)(N - 1);
+  const size_t lds = rescale ? n_out * 256 * sizeof(uint4) : 0;  // (at most 64 KiB)
+#define RNT_LC(VEC, RESC, NI) \
+  hipLaunchKernelGGL((k_lincomb<W, VEC, RESC, NI>), grid, dim3(256), lds, k.s, (W*)out0, (W*)out1, (const W*)x0, \
+                     (const W*)x1, (const W*)w, (const W*)wp, (const W*)bias, rinv, rinvp, a, tp)
+#define RNT_LC_V(NI)                                                            \
+  do {                                                                          \
+    if (vec) { if (rescale) RNT_LC(true, true, NI); else RNT_LC(true, false, NI); }    \
+    else { if (rescale) RNT_LC(false, true, NI); else RNT_LC(false, false, NI); }      \
+  } while (0)
+  if (n_in <= 4) RNT_LC_V(4);
+  else if (n_in <= 8) RNT_LC_V(8);
+  else RNT_LC_V(16);
+#undef RNT_LC_V
+#undef RNT_LC
+  return hipGetLastError();
+}
+
 static uint64_t inv_mod_pow2(uint64_t h, uint64_t M) {
   // h odd, M power of two: Newton iteration for h^-1 mod 2^64, then mask.
   uint64_t x = h;  // correct to 3 bits
@@ -3857,6 +4038,12 @@ hipError_t launch_moddown_rescale(const Launch& k, void* out, uint64_t out_ls, c
                                   const HybridConsts& hc) {
   RNT_WIDE(moddown_rescale_t<uint32_t>(k, out, out_ls, A, a_ls, add, add_ls, rinv, rinvp, hc),
            moddown_rescale_t<uint64_t>(k, out, out_ls, A, a_ls, add, add_ls, rinv, rinvp, hc));
+}
+hipError_t launch_lincomb(const Launch& k, void* out0, void* out1, uint64_t out_ls, const void* x0, const void* x1,
+                          uint64_t in_ls, size_t n_in, size_t n_out, const void* w, const void* wp, const void* bias,
+                          bool rescale) {
+  RNT_WIDE(lincomb_t<uint32_t>(k, out0, out1, out_ls, x0, x1, in_ls, n_in, n_out, w, wp, bias, rescale),
+           lincomb_t<uint64_t>(k, out0, out1, out_ls, x0, x1, in_ls, n_in, n_out, w, wp, bias, rescale));
 }
 hipError_t launch_hoist_mac_seed(const Launch& k, void* acc0, void* acc1, const void* d, const void* key_a,
                                  const void* key_b, uint64_t key_ls, const void* seed_a, const void* seed_b,

@@ -26,6 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RnsNttError, check, load
+from .poly_eval import PolyEvalPlan, poly_eval_plan
 
 __all__ = [
     "device_count",
@@ -58,6 +59,9 @@ __all__ = [
     "rotate_ciphertext_hoisted",
     "bsgs_diagonal_rows",
     "rescale_ciphertext",
+    "ct_lincomb",
+    "poly_eval_plan",
+    "PolyEvalPlan",
     "Plaintext",
     "CkksEncoder",
     "DeviceRng",
@@ -1183,16 +1187,19 @@ def mul_ciphertexts_gadget_rescale(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsGad
     return Ciphertext(out0, out1, ct1.logp + ct2.logp - bits_dropped, ct1.logq - bits_dropped)
 
 
-def mul_ciphertexts_hybrid_rescale(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsHybridKey) -> Ciphertext:
+def mul_ciphertexts_hybrid_rescale(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsHybridKey,
+                                   out_basis: Optional[RnsBasis] = None) -> Ciphertext:
     """mul_ciphertexts_hybrid then rescale_ciphertext as one op
     (rnt_ct_mul_relin_rescale_hybrid): equal word for word to the two calls;
-    the un-rescaled product never reaches memory."""
+    the un-rescaled product never reaches memory.  ``out_basis`` (a
+    ``drop_last(1)`` of the inputs' basis) receives the result where a circuit
+    keeps one basis object per level; by default a fresh one is made."""
     _require_class(rlk, RnsHybridKey, "mul_ciphertexts_hybrid_rescale")
     assert ct1.logq == ct2.logq, "logq mismatch in hybrid multiplication"
     rlk = _at_ct_level(rlk, ct1.c0.basis)
     q_last = ct1.c0.basis.moduli()[-1]
     bits_dropped = q_last.bit_length()
-    new_basis = ct1.c0.basis.drop_last(1)
+    new_basis = out_basis if out_basis is not None else ct1.c0.basis.drop_last(1)
     out0, out1 = ct1.c0._like(new_basis), ct1.c0._like(new_basis)
     check(load().rnt_ct_mul_relin_rescale_hybrid(out0.handle, out1.handle, ct1.c0.handle, ct1.c1.handle,
                                                  ct2.c0.handle, ct2.c1.handle, rlk.a.handle, rlk.b.handle,
@@ -1225,6 +1232,51 @@ def linear_transform_bsgs_hybrid_rescale(ct: Ciphertext, diag: RnsPoly, baby_key
                                                    len(baby_keyset.steps), giant, len(giant_keyset.steps),
                                                    diag.handle, h(baby_keyset.a), h(baby_keyset.b),
                                                    h(giant_keyset.a), h(giant_keyset.b), baby_keyset.alpha))
+    return Ciphertext(out0, out1, ct.logp - bits_dropped, ct.logq - bits_dropped)
+
+
+def ct_lincomb(ct: Ciphertext, n_in: int, weights, bias=None, rescale: bool = True,
+               out_basis: Optional[RnsBasis] = None) -> Ciphertext:
+    """``n_out`` scalar linear combinations of the ``n_in`` ciphertexts packed
+    in ``ct`` (a batch of ``n_in * B``, term i of ciphertext b at ``i * B + b``,
+    the layout ``rotate_ciphertext_hybrid_hoisted`` writes) in one launch
+    (rnt_ct_lincomb / rnt_ct_lincomb_rescale): output j is ``sum_i
+    weights[j][i] * ct_i + bias[j]``, a batch of ``n_out * B`` with output j of
+    ciphertext b at ``j * B + b``.  ``weights`` ([n_out][n_in]) and ``bias``
+    ([n_out] or None) are signed Python ints, reduced mod every q_t here; a
+    bias is the constant in every slot, at the scale the caller means (the
+    products' scale).  With ``rescale`` the result is rescaled in the same
+    kernel, word for word ``rescale_ciphertext`` of the un-rescaled call, and
+    logp / logq drop by the bit length of the limb rescaled away.  logp does
+    not grow by the weights' scale: the caller adds it.  ``out_basis`` as in
+    :func:`mul_ciphertexts_hybrid_rescale`."""
+    n_in = int(n_in)
+    rows = [[int(v) for v in row] for row in weights]
+    if n_in < 1 or not rows or any(len(r) != n_in for r in rows):
+        raise ValueError("ct_lincomb: weights must be [n_out][n_in] with n_out, n_in >= 1")
+    if ct.c0.n_polys % n_in != 0:
+        raise ValueError(f"ct_lincomb: a batch of {ct.c0.n_polys} polys is no {n_in} terms of ciphertexts")
+    if bias is not None and len(bias) != len(rows):
+        raise ValueError("ct_lincomb: bias must have one entry per output")
+    basis = ct.c0.basis
+    mods = basis.moduli()
+    n_out, B = len(rows), ct.c0.n_polys // n_in
+    w = np.array([[[v % q for q in mods] for v in row] for row in rows], dtype=np.uint64)
+    b = None if bias is None else np.array([[int(v) % q for q in mods] for v in bias], dtype=np.uint64)
+    bits_dropped = 0
+    if rescale:
+        if len(mods) < 2:
+            raise RnsNttError(_lib.INVALID_MOD_DROP, f"invalid mod-drop count 1 for {len(mods)} channels",
+                              {"drop_count": 1, "channel_count": len(mods)})
+        bits_dropped = mods[-1].bit_length()
+        new_basis = out_basis if out_basis is not None else basis.drop_last(1)
+    else:
+        new_basis = out_basis if out_basis is not None else basis
+    out0 = RnsPoly(new_basis, n_out * B, _uninit=True)
+    out1 = RnsPoly(new_basis, n_out * B, _uninit=True)
+    call = load().rnt_ct_lincomb_rescale if rescale else load().rnt_ct_lincomb
+    check(call(out0.handle, out1.handle, ct.c0.handle, ct.c1.handle, n_in, n_out, _u64p(w),
+               None if b is None else _u64p(b)))
     return Ciphertext(out0, out1, ct.logp - bits_dropped, ct.logq - bits_dropped)
 
 

@@ -24,10 +24,10 @@ from typing import Optional
 import numpy as np
 
 from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsGadgetKeySet, RnsHybridKey,
-               RnsHybridKeySet, RnsPoly, bsgs_diagonal_rows, linear_transform, linear_transform_bsgs,
+               RnsHybridKeySet, RnsPoly, bsgs_diagonal_rows, check, ct_lincomb, linear_transform, linear_transform_bsgs,
                linear_transform_bsgs_hoisted, linear_transform_bsgs_hybrid, linear_transform_bsgs_hybrid_rescale,
-               linear_transform_hybrid, mul_ciphertexts_gadget, mul_ciphertexts_hybrid,
-               mul_ciphertexts_hybrid_rescale, rescale_ciphertext, rotate_ciphertext,
+               linear_transform_hybrid, load, mul_ciphertexts_gadget, mul_ciphertexts_hybrid,
+               mul_ciphertexts_hybrid_rescale, poly_eval_plan, rescale_ciphertext, rotate_ciphertext,
                rotate_ciphertext_hoisted, rotate_ciphertext_hybrid, rotate_ciphertext_hybrid_hoisted)
 
 
@@ -243,6 +243,83 @@ class CkksEngine:
         out = linear_transform_bsgs_hybrid_rescale(ct, diag_plaintexts.poly, baby_keyset, giant_keyset)
         out.logp += diag_plaintexts.scale_bits
         return out
+
+    # -- polynomial evaluation -------------------------------------------------
+    ct_lincomb = staticmethod(ct_lincomb)
+
+    @staticmethod
+    def evaluate_polynomial_hybrid(ct: Ciphertext, coeffs, rlk: RnsHybridKey, basis: str = "monomial") -> Ciphertext:
+        """``p(ct)`` for every ciphertext of the batch, ``p = sum_k coeffs[k]
+        Phi_k`` with ``Phi_k = x^k`` (``basis="monomial"``) or the Chebyshev
+        ``T_k`` (``"chebyshev"``), degree >= 1: the Paterson-Stockmeyer
+        schedule of ``poly_eval_plan`` on ``mul_ciphertexts_hybrid_rescale``,
+        ``ct_lincomb`` and additions.  ``rlk`` is one full-level hybrid
+        relinearisation key with ``n_special``: it picks each multiply's level
+        by itself.  Every ciphertext prime the circuit consumes (the last
+        ``plan.depth`` of ``ct``'s basis) must have bit length ``ct.logp``, so
+        the scale stays 2^logp (up to the drift of q != 2^logp, which the
+        integer logp does not track); the result is ``plan.depth`` levels
+        down."""
+        p = int(ct.logp)
+        plan = poly_eval_plan(coeffs, basis, p)
+        top = ct.c0.basis
+        mods = top.moduli()
+        if len(mods) - plan.depth < 1:
+            raise ValueError(f"evaluate_polynomial_hybrid: degree {plan.degree} consumes {plan.depth} levels, the "
+                             f"ciphertext has {len(mods)} limbs")
+        for q in mods[len(mods) - plan.depth:]:
+            if q.bit_length() != p:
+                raise ValueError(f"evaluate_polynomial_hybrid: the consumed prime {q} has {q.bit_length()} bits, "
+                                 f"the ciphertext's logp is {p}")
+        B = ct.c0.n_polys
+        level_basis = {0: top}  # one basis object per level: operands of a call share it
+
+        def lb(level):
+            if level not in level_basis:
+                level_basis[level] = top.drop_last(level)
+            return level_basis[level]
+
+        def drop(poly, basis_to):
+            out = poly._like(basis_to)
+            check(load().rnt_mod_drop_last(out.handle, poly.handle))
+            return out
+
+        v = {"x": ct}
+        for op in plan.ops:
+            if op[0] == "drop":
+                _, dst, src, level = op
+                s = v[src]
+                bits = sum(q.bit_length() for q in mods[len(mods) - level:len(mods) - plan.levels[src]])
+                v[dst] = Ciphertext(drop(s.c0, lb(level)), drop(s.c1, lb(level)), s.logp, s.logq - bits)
+            elif op[0] == "mul":
+                _, dst, a, b = op
+                v[dst] = mul_ciphertexts_hybrid_rescale(v[a], v[b], rlk, out_basis=lb(plan.levels[dst]))
+            elif op[0] == "add":
+                _, dst, a, b = op
+                v[dst] = CkksEngine.add_ciphertexts(v[a], v[b])
+            else:
+                _, dsts, srcs, weights, bias, rescale, _, _ = op
+                if len(srcs) == 1:
+                    packed = v[srcs[0]]
+                else:
+                    here = lb(plan.levels[srcs[0]])
+                    c0, c1 = RnsPoly(here, len(srcs) * B, _uninit=True), RnsPoly(here, len(srcs) * B, _uninit=True)
+                    for i, s in enumerate(srcs):
+                        c0.copy_polys(v[s].c0, i * B, 0, B)
+                        c1.copy_polys(v[s].c1, i * B, 0, B)
+                    packed = Ciphertext(c0, c1, v[srcs[0]].logp, v[srcs[0]].logq)
+                out = ct_lincomb(packed, len(srcs), weights, bias, rescale=rescale, out_basis=lb(plan.levels[dsts[0]]))
+                if rescale:
+                    out.logp += p  # the weights' scale
+                for j, d in enumerate(dsts):
+                    if len(dsts) == 1:
+                        v[d] = out
+                        break
+                    c0, c1 = RnsPoly(out.c0.basis, B, _uninit=True), RnsPoly(out.c0.basis, B, _uninit=True)
+                    c0.copy_polys(out.c0, 0, j * B, B)
+                    c1.copy_polys(out.c1, 0, j * B, B)
+                    v[d] = Ciphertext(c0, c1, out.logp, out.logq)
+        return v[plan.result]
 
     # -- encryption (engine.rs:84-127) -----------------------------------------
     def encrypt(self, plaintext, pk: PublicKey, rng, logp: int = 0,
