@@ -11,7 +11,11 @@ Checks, for a 31-bit prime at N = 2^16:
   4. the digit arithmetic of one pass (balanced byte digits of the centred
      matrix and data, int32 digit sums as the i8 MFMA forms them, the
      shift-add recombination and the signed Montgomery reduction) is exact
-     and stays within the stated ranges.
+     and stays within the stated ranges;
+  5. the same pass on the plain matrix with the quotient-estimate reduction
+     (recomb_q, RNT_MF_QR): the rounding offset as the accumulator start of
+     digit plane 3, the 32-bit wrapping arithmetic, the congruence and
+     mf_build's bound on |r|.
 
 Run: python tools/mfma_model.py
 """
@@ -151,6 +155,43 @@ def main():
             assert (r - sum(F[j][k] * xs[k] for k in range(16))) % q == 0
     print(f"4: digit arithmetic exact; max |C_a| = {worst_C} (< 2^20 = {1 << 20}), max |T| = 2^{np.log2(worst_T):.2f},"
           f" max |r| = {worst_r} (q/2 + 2^14 = {q // 2 + (1 << 14)})")
+    # 5: the plain matrix and the quotient estimate (recomb_q)
+    c = 48
+    mu, rho = (1 << 48) // q, (1 << 48) % q
+    Bq = (1 << 28) + (1 << 20) + (1 << 15)
+    rq = max(Bq + (c << 24) + (((Bq - (c << 8)) * rho) >> 32) + 1,
+             Bq + q + (((Bq + (c << 8)) * rho) >> 32) + 1 - (c << 24))
+    assert rq <= 0x7F7F7F7F and rq * rq // R + q // 2 + 1 < 0x7F7F7F7F
+
+    def s32(v):
+        v &= R - 1
+        return v - R if v >> 31 else v
+
+    Wp = [[centred(F[j][k] * (1 << (8 * b)), q) for b in range(4) for k in range(16)] for j in range(16)]
+    worst_q = 0
+    for trial in range(200):
+        # operands up to the new bound: a previous recomb_q pass's outputs
+        xs = [int(v) - rq for v in rng.integers(0, 2 * rq + 1, size=16)]
+        if trial == 0:
+            xs = [-rq] * 16
+        if trial == 1:
+            xs = [rq] * 16
+        xd = [digits(v) for v in xs]
+        for j in range(16):
+            C = [0, 0, 0, c]  # the MFMA's inline-constant accumulator on plane 3
+            for kb, w in enumerate(Wp[j]):
+                b, k = divmod(kb, 16)
+                wd = digits(w)
+                for aa in range(4):
+                    C[aa] += wd[aa] * xd[k][b]
+            lo = (C[0] + (C[1] << 8)) & (R - 1)
+            hi = (C[2] + (C[3] << 8)) & (R - 1)
+            qt = (s32(hi) * mu) >> 32
+            r = s32(((hi << 16) + lo) - qt * q - (c << 24))
+            worst_q = max(worst_q, abs(r))
+            assert abs(r) <= rq
+            assert (r - sum(F[j][k] * xs[k] for k in range(16))) % q == 0
+    print(f"5: quotient-estimate reduction exact; max |r| = {worst_q} = {worst_q / q:.3f} q (bound {rq} = {rq / q:.3f} q)")
 
 
 if __name__ == "__main__":

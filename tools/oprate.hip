@@ -89,6 +89,7 @@ __global__ void __launch_bounds__(256) k(unsigned* out, unsigned seed) {
   if (OP == 13) BODY("v_ashrrev_i32")
   if (OP == 14) BODY("v_min_i32")
   if (OP == 15) BODY("v_lshlrev_b32")
+  if (OP == 19) BODY("v_mul_hi_i32")
   out[blockIdx.x * blockDim.x + threadIdx.x] = a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7;
 }
 
@@ -115,9 +116,9 @@ int main(int argc, char** argv) {
   const char* names[] = {"v_add_u32", "v_min_u32", "v_mul_lo_u32", "v_mul_hi_u32", "v_mul_u32_u24",
                          "v_lshl_add_u32", "v_add3_u32", "v_sub_u32", "v_mul_hi_u32_u24", "v_xor_b32",
                          "v_cndmask_b32_e32", "v_max_u32", "v_and_b32", "v_ashrrev_i32", "v_min_i32",
-                         "v_lshlrev_b32", "v_sub_co_u32", "v_add_co_u32", "v_mad_u64_u32(x4/iter)"};
-  const int NOPS = 19;
-  float ms[19];
+                         "v_lshlrev_b32", "v_sub_co_u32", "v_add_co_u32", "v_mad_u64_u32(x4/iter)", "v_mul_hi_i32"};
+  const int NOPS = 20;
+  float ms[20];
   ms[0] = run<0>(d, blocks);
   ms[1] = run<1>(d, blocks);
   ms[2] = run<2>(d, blocks);
@@ -137,6 +138,7 @@ int main(int argc, char** argv) {
   ms[16] = run<16>(d, blocks);
   ms[17] = run<17>(d, blocks);
   ms[18] = run<18>(d, blocks);
+  ms[19] = run<19>(d, blocks);
   const double waves = (double)blocks * 256 / 64;
   const double wave_instr = waves * ITERS * 8;
   const double simds = 256 * 4;

@@ -26,8 +26,9 @@
 // pointwise product are folded into its last matrix.
 //
 // ---- exact integer matrix products on the i8 matrix cores -----------------
-// Words travel between passes as signed representatives r, |r| < q/2 + 2^14,
-// packed as four balanced byte digits: (r + 0x80808080) ^ 0x80808080 (byte b
+// Words travel between passes as signed representatives r, |r| < q/2 + 2^14
+// (up to about q after a quotient-estimate pass, below), packed as four
+// balanced byte digits: (r + 0x80808080) ^ 0x80808080 (byte b
 // of that is digit b, in [-128, 128)).  A pass computes, for each output j,
 //   T_j = sum_{k,b} E[j][k][b] * x_k^(b),   E[j][k][b] = centred(W[j][k] 2^(8b) 2^32 mod q)
 // with E split into four digit planes too: v_mfma_i32_16x16x64_i8 forms the
@@ -43,12 +44,28 @@
 //   x = (lo tA + hi tB + m q) / 2^32,  tA = centred(t),  tB = centred(t 2^16)
 // is congruent to r' t' 2^-32, |lo tA + hi tB| < 2^59.1 and |x| < 0.563 q
 // (recomb_tw), which packs as well.
+// Quotient-estimate form (RNT_MF_QR, recomb_q): the passes whose
+// output goes on as packed digits or into a Montgomery product -- pass 0, the
+// first step of the two-step passes, k_mf_mul's last forward pass and the
+// inverse's pass 1 -- run plain matrices, E = centred(W 2^(8b) mod q), so that
+// T is congruent to sum_k W[j][k] x_k itself, and reduce it by an estimate of
+// its quotient from hi alone:
+//   qt = floor(hi' mu / 2^32),  mu = floor(2^48 / q),  hi' = hi + 48 2^8
+//   r' = (hi' 2^16 + lo) - qt q - 48 2^24      (32-bit arithmetic)
+// (the offset 48 rounds the estimate to nearest and enters free, as the inline
+// constant accumulator of digit plane 3's MFMA).  Two multiply-class
+// instructions a word instead of recomb()'s three or four, no 64-bit pair;
+// |r'| reaches about q instead of q/2, which the packed digits and mont() take
+// (bounds per prime in mf_build) and canon() does not: every pass in front of
+// a canon() and the folded passes keep the Montgomery form.
 // Counted in the gfx950 code (profiles/mf_twist_fold_isa.txt): 7 VALU
 // instructions per word for a pass's recombination (6 where the word is not
 // packed again), 10 with a two-step twist, 7 with a folded one; k_mf_mul, 12
 // passes a product, runs 9.9 per word per pass all told (10.65 with every
 // twist in two steps), instead of 22 for four radix-2 CT stages; the MFMAs
-// (4 per 256 words) run beside them.
+// (4 per 256 words) run beside them.  recomb_q keeps those counts (7 and 6)
+// and moves 11 of a word's 54 multiply-class instructions a product to the
+// shift-add class (profiles/mf_quot_reduce_isa.txt).
 //
 // ---- layouts -----------------------------------------------------------------
 // One 1024-thread workgroup per (poly, limb) plane, 64 words a thread as 16
@@ -148,7 +165,55 @@ constexpr int kTwB3 = 1024, kTwB4 = 16384;  // A -> B distance of a family (its 
 constexpr int kTw3fA = kFoldBase, kTw3iA = kTw3fA + 2 * kTwB3;
 constexpr int kFold4Base = kFoldBase + (kFold3 ? 4 * kTwB3 : 0);
 constexpr int kTw4fA = kFold4Base, kTw4iA = kTw4fA + 2 * kTwB4;
-constexpr int kLimb = kFold4Base + (kFold4 ? 4 * kTwB4 : 0);
+// RNT_MF_QR: the quotient-estimate reduction (recomb_q) on plain
+// (non-Montgomery) matrices instead of recomb()'s Montgomery step, as a mask:
+// bit 0 the untwisted passes (pass_p1, ipass_p2 and, in k_mf_mul, pass_p4),
+// bit 1 the first step of the two-step twisted passes (pass_p3, ipass_p4).
+// The folded passes (recomb_tw), the standalone forward's two-step pass_p2
+// (it shares its matrices with the folded one), every pass_p4 whose words are
+// made canonical and the inverse's last pass keep the Montgomery form: their
+// consumers need r in (-q, q), which recomb_q gives only with a thin margin
+// at q just above 2^30 ("Quotient-estimate reduction").  The
+// plain matrices and the split input-bias compensations live in slots of
+// their own past the fold tables (no offset before them moves).
+// RNT_MF_QR_MUL / _NTT / _NTTF / _TENSOR: the mask of one kernel, _NTT the
+// standalone inverse's and _NTTF the standalone forward's (a kernel that
+// starts to spill keeps the old form).
+#ifndef RNT_MF_QR
+#define RNT_MF_QR 3
+#endif
+#ifndef RNT_MF_QR_MUL
+#define RNT_MF_QR_MUL RNT_MF_QR
+#endif
+#ifndef RNT_MF_QR_NTT
+#define RNT_MF_QR_NTT RNT_MF_QR
+#endif
+#ifndef RNT_MF_QR_NTTF
+// (bit 1 in the standalone forward spilled 20 bytes a lane: profiles/mf_quot_reduce_isa.txt)
+#define RNT_MF_QR_NTTF (RNT_MF_QR & 1)
+#endif
+#ifndef RNT_MF_QR_TENSOR
+#define RNT_MF_QR_TENSOR RNT_MF_QR
+#endif
+constexpr int kQrMul = RNT_MF_QR_MUL & 3, kQrNtt = RNT_MF_QR_NTT & 3, kQrNttFwd = RNT_MF_QR_NTTF & 3;
+constexpr int kQrTensor = RNT_MF_QR_TENSOR & 3;
+constexpr bool kQrAny = (kQrMul | kQrNtt | kQrNttFwd | kQrTensor) != 0;
+constexpr int kQrP4 = 4;  // fwd<>'s QR mask, bit 2: pass_p4 too (k_mf_mul only)
+constexpr int kQrBase = kFold4Base + (kFold4 ? 4 * kTwB4 : 0);
+static_assert(kQrBase % 256 == 0, "matrix slots are 256 v4i");
+constexpr int S_QF1 = kQrBase / 256, S_QF3 = S_QF1 + 1, S_QF4 = S_QF1 + 2, S_QI4 = S_QF1 + 3, S_QI2 = S_QF1 + 4;
+// [2][lam]: the plain input-bias compensation of pass 0 (of the standalone
+// inverse's first pass), split into the digit-0 and the digit-2 accumulator
+// starts (v = v0 + 2^16 v2, |v0| <= 2^15, |v2| <= 2^14 + 1)
+constexpr int kQCompF1 = (S_QI2 + 16) * 256, kQCompI4 = kQCompF1 + 128;
+constexpr int kQConst = kQCompI4 + 128;  // word 0: mu = floor(2^48 / q)
+constexpr int kQrEnd = kQConst + 64;
+constexpr int kLimb = kQrAny ? kQrEnd : kQrBase;
+static_assert(!kQrAny || (kQConst < kLimb && (S_QI2 + 16) * 256 <= kQCompF1), "the plain slots lie inside the limb's table");
+// the rounding offset of recomb_q's quotient estimate: the inline constant
+// accumulator of digit plane 3 (tile<.., QC>), kQrC 2^8 in hi, kQrC 2^24 in T
+#define RNT_MF_QRC "48"
+constexpr uint32_t kQrC = 48;
 // where the passes read their twists (the A table when folded)
 constexpr int kTw3iR = kFold3 ? kTw3iA : kTw3i;
 constexpr int kTw4fR = kFold4 ? kTw4fA : kTw4f, kTw4iR = kFold4 ? kTw4iA : kTw4i;
@@ -183,6 +248,10 @@ struct Mc {
   int64_t K0;      // 0 (opaque)
   int32_t one;     // opaque 1 and 2^16 (SGPR operands of v_mad_i64_i32)
   int32_t s16;
+  // recomb_q: mu = floor(2^48 / q), nq = -q, kq = 0x80808080 - kQrC 2^24 (the
+  // digit bias less the rounding offset's share of T), kq0 = -kQrC 2^24
+  int32_t mu;
+  uint32_t nq, kq, kq0;
 };
 
 // Every global access goes through a buffer descriptor (base and range in
@@ -251,6 +320,37 @@ __device__ __forceinline__ int32_t recomb(int32_t c0, int32_t c1, int32_t c2, in
   const int64_t v = (int64_t)(int32_t)mm * m.q + t;
   return (int32_t)(v >> 32);
 }
+// The same word from a plain (non-Montgomery) matrix, by a quotient estimate:
+// r = T - qt q with qt = floor(hi' mu / 2^32), hi' = hi + kQrC 2^8 (the offset
+// came in through digit plane 3's accumulator, so c3 holds it already), in
+// 32-bit arithmetic; + 0x80808080 when WK.  Two multiply-class instructions
+// (v_mul_hi_i32, v_mul_lo_u32) and no 64-bit pair.  With rho = 2^48 mod q,
+//   r = lo - kQrC 2^24 + eps q,  eps = frac(hi' mu / 2^32) + hi' rho / (2^32 q),
+// so -Bl - kQrC 2^24 - (Bh - kQrC 2^8) rho / 2^32 < r
+//      < Bl - kQrC 2^24 + q + (Bh + kQrC 2^8) rho / 2^32
+// for |lo| <= Bl, |hi| <= Bh: r is T mod q exactly (the low 32 bits of a value
+// inside the int32 range), but not in (-q/2, q/2): about (-q, q/2) at q = 2^30
+// and (-q/2, 3q/4) at q = 2^31 (mf_build computes and checks the bound per
+// prime; tests/test_mf_quot_reduce.py is the integer model).
+template <bool WK>
+__device__ __forceinline__ int32_t recomb_q(int32_t c0, int32_t c1, int32_t c2, int32_t c3, const Mc& m) {
+  uint32_t lo = (uint32_t)c0 + ((uint32_t)c1 << 8);
+  uint32_t hi = (uint32_t)c2 + ((uint32_t)c3 << 8);
+  // (opaque values: hipcc otherwise spreads the sum below over the four digit
+  // sums, two shifts instead of one v_lshl_add_u32 and an add more a word)
+  asm("" : "+v"(lo), "+v"(hi));
+  uint32_t t = (hi << 16) + lo;
+  asm("" : "+v"(t));
+  const int32_t qt = __mulhi((int32_t)hi, m.mu);
+  return (int32_t)(t + (uint32_t)qt * m.nq + (WK ? m.kq : m.kq0));
+}
+template <bool QR, bool WK>
+__device__ __forceinline__ int32_t recomb_x(int32_t c0, int32_t c1, int32_t c2, int32_t c3, const Mc& m) {
+  if constexpr (QR)
+    return recomb_q<WK>(c0, c1, c2, c3, m);
+  else
+    return recomb<WK>(c0, c1, c2, c3, m);
+}
 // Signed Montgomery product a b 2^-32 mod q, + 0x80808080 when WK.  Any
 // |a|, |b| < q < 2^31: |a b + m q| < q^2 + 2^31 q < 2^63 and the result lies
 // in (-q, q); the bias K only adds to the high word (its low word is 0), so
@@ -258,7 +358,10 @@ __device__ __forceinline__ int32_t recomb(int32_t c0, int32_t c1, int32_t c2, in
 // Where the result is handed on in the packed byte form (k_mf_mul's
 // product), the operands are pass outputs, |a|, |b| < q/2 + 2^14, so
 // |v| < (q/2 + 2^14)^2 / 2^32 + q/2 + 1 < 5q/8 + 1 < 0x7F7F7F7F, inside the
-// packed range [-0x80808080, 0x7F7F7F7F] (mf_build checks it per prime).
+// packed range [-0x80808080, 0x7F7F7F7F] (mf_build checks it per prime); with
+// recomb_q outputs, |a|, |b| <= rq (mf_build's bound, about 0.75 q .. 1.07 q),
+// |v| < rq^2 / 2^32 + q/2 + 1, checked per prime as well (below 0.84 q for
+// every 31-bit prime: rq is large only where q is small).
 template <bool WK>
 __device__ __forceinline__ int32_t mont(int32_t a, int32_t b, const Mc& m) {
   // one v_mad_i64_i32 (left to itself hipcc widens a -- the high word of
@@ -354,29 +457,47 @@ __device__ __forceinline__ uint32_t canon(int32_t r, int32_t q) { return (uint32
 //    window hipcc itself pads for its own reads of a builtin MFMA's D).
 // DA: the data is the A operand (the matrix the B operand).  HC: the first
 // digit plane accumulates onto c0 (otherwise the inline constant 0).
-template <bool DA, bool HC>
-__device__ __forceinline__ void tile(v4i (&D)[4], const v4i (&M)[4], v4i dat, v4i c0) {
-#define RNT_MF4(A0, B0, A1, B1, A2, B2, A3, B3, C0)                                  \
+template <bool DA, bool HC, bool QC = false>
+__device__ __forceinline__ void tile(v4i (&D)[4], const v4i (&M)[4], v4i dat, v4i c0, v4i c2 = v4i{0, 0, 0, 0}) {
+#define RNT_MF4(A0, B0, A1, B1, A2, B2, A3, B3, C0, C2, C3)                          \
   "s_nop 1\n\t"                                                                      \
   "v_mfma_i32_16x16x64_i8 %0, " A0 ", " B0 ", " C0 "\n\t"                            \
   "v_mfma_i32_16x16x64_i8 %1, " A1 ", " B1 ", 0\n\t"                                 \
-  "v_mfma_i32_16x16x64_i8 %2, " A2 ", " B2 ", 0\n\t"                                 \
-  "v_mfma_i32_16x16x64_i8 %3, " A3 ", " B3 ", 0\n\t"                                 \
+  "v_mfma_i32_16x16x64_i8 %2, " A2 ", " B2 ", " C2 "\n\t"                            \
+  "v_mfma_i32_16x16x64_i8 %3, " A3 ", " B3 ", " C3 "\n\t"                            \
   "s_nop 7"
-  if constexpr (DA && HC)
-    asm volatile(RNT_MF4("%4", "%5", "%4", "%6", "%4", "%7", "%4", "%8", "%9")
+  // QC: digit plane 3 accumulates onto the inline constant kQrC (recomb_q's
+  // rounding offset, every element), and with HC digit plane 2 onto c2
+  if constexpr (QC && DA && HC)
+    asm volatile(RNT_MF4("%4", "%5", "%4", "%6", "%4", "%7", "%4", "%8", "%9", "%10", RNT_MF_QRC)
+                 : "=&v"(D[0]), "=&v"(D[1]), "=&v"(D[2]), "=&v"(D[3])
+                 : "v"(dat), "v"(M[0]), "v"(M[1]), "v"(M[2]), "v"(M[3]), "v"(c0), "v"(c2));
+  else if constexpr (QC && DA)
+    asm volatile(RNT_MF4("%4", "%5", "%4", "%6", "%4", "%7", "%4", "%8", "0", "0", RNT_MF_QRC)
+                 : "=&v"(D[0]), "=&v"(D[1]), "=&v"(D[2]), "=&v"(D[3])
+                 : "v"(dat), "v"(M[0]), "v"(M[1]), "v"(M[2]), "v"(M[3]));
+  else if constexpr (QC && HC)
+    asm volatile(RNT_MF4("%5", "%4", "%6", "%4", "%7", "%4", "%8", "%4", "%9", "%10", RNT_MF_QRC)
+                 : "=&v"(D[0]), "=&v"(D[1]), "=&v"(D[2]), "=&v"(D[3])
+                 : "v"(dat), "v"(M[0]), "v"(M[1]), "v"(M[2]), "v"(M[3]), "v"(c0), "v"(c2));
+  else if constexpr (QC)
+    asm volatile(RNT_MF4("%5", "%4", "%6", "%4", "%7", "%4", "%8", "%4", "0", "0", RNT_MF_QRC)
+                 : "=&v"(D[0]), "=&v"(D[1]), "=&v"(D[2]), "=&v"(D[3])
+                 : "v"(dat), "v"(M[0]), "v"(M[1]), "v"(M[2]), "v"(M[3]));
+  else if constexpr (DA && HC)
+    asm volatile(RNT_MF4("%4", "%5", "%4", "%6", "%4", "%7", "%4", "%8", "%9", "0", "0")
                  : "=&v"(D[0]), "=&v"(D[1]), "=&v"(D[2]), "=&v"(D[3])
                  : "v"(dat), "v"(M[0]), "v"(M[1]), "v"(M[2]), "v"(M[3]), "v"(c0));
   else if constexpr (DA)
-    asm volatile(RNT_MF4("%4", "%5", "%4", "%6", "%4", "%7", "%4", "%8", "0")
+    asm volatile(RNT_MF4("%4", "%5", "%4", "%6", "%4", "%7", "%4", "%8", "0", "0", "0")
                  : "=&v"(D[0]), "=&v"(D[1]), "=&v"(D[2]), "=&v"(D[3])
                  : "v"(dat), "v"(M[0]), "v"(M[1]), "v"(M[2]), "v"(M[3]));
   else if constexpr (HC)
-    asm volatile(RNT_MF4("%5", "%4", "%6", "%4", "%7", "%4", "%8", "%4", "%9")
+    asm volatile(RNT_MF4("%5", "%4", "%6", "%4", "%7", "%4", "%8", "%4", "%9", "0", "0")
                  : "=&v"(D[0]), "=&v"(D[1]), "=&v"(D[2]), "=&v"(D[3])
                  : "v"(dat), "v"(M[0]), "v"(M[1]), "v"(M[2]), "v"(M[3]), "v"(c0));
   else
-    asm volatile(RNT_MF4("%5", "%4", "%6", "%4", "%7", "%4", "%8", "%4", "0")
+    asm volatile(RNT_MF4("%5", "%4", "%6", "%4", "%7", "%4", "%8", "%4", "0", "0", "0")
                  : "=&v"(D[0]), "=&v"(D[1]), "=&v"(D[2]), "=&v"(D[3])
                  : "v"(dat), "v"(M[0]), "v"(M[1]), "v"(M[2]), "v"(M[3]));
 #undef RNT_MF4
@@ -654,17 +775,18 @@ __device__ __forceinline__ void mf_prio(int p) {
 }
 // pass 0 on P1 chunks [C0, C0 + 8): input canonical (BIAS: packed with the
 // -2^30 shift its compensation undoes) or packed; output packed.
-template <int C0, bool BIAS>
-__device__ __forceinline__ void pass_p1(uint32_t (&x1)[64], const v4i (&M)[4], v4i comp, const Mc& m) {
+// QR: the plain matrix and recomb_q (comp, comp2: the split compensation).
+template <int C0, bool BIAS, bool QR = false>
+__device__ __forceinline__ void pass_p1(uint32_t (&x1)[64], const v4i (&M)[4], v4i comp, v4i comp2, const Mc& m) {
 #pragma unroll
   for (int c = C0; c < C0 + 8; ++c) {
     v4i b;
 #pragma unroll
     for (int i = 0; i < 4; ++i) b[i] = (int)(BIAS ? pk_canon(x1[4 * c + i]) : x1[4 * c + i]);
     v4i D[4];
-    tile<false, BIAS>(D, M, b, comp);
+    tile<false, BIAS, QR>(D, M, b, comp, comp2);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) x1[4 * c + i] = (uint32_t)recomb<true>(D[0][i], D[1][i], D[2][i], D[3][i], m) ^ K32;
+    for (int i = 0; i < 4; ++i) x1[4 * c + i] = (uint32_t)recomb_x<QR, true>(D[0][i], D[1][i], D[2][i], D[3][i], m) ^ K32;
     pin4(x1[4 * c + 0], x1[4 * c + 1], x1[4 * c + 2], x1[4 * c + 3]);
     tile_fence();
   }
@@ -705,8 +827,11 @@ __device__ __forceinline__ void pass_p2(uint32_t (&x2)[64], const v4i (&M)[4], R
   }
 }
 // pass 2 (F, data as A: P3 -> P4 positions), then the pass-3 twist.
+// QR: the first step of the two-step twist as recomb_q (plain matrix).
+template <bool QR = false>
 __device__ __forceinline__ void pass_p3(uint32_t (&x)[64], const v4i (&M)[4], Rsrc tab, uint32_t tvo, uint32_t tso,
                                         const Mc& m) {
+  static_assert(!(QR && kFold4), "a folded pass keeps the Montgomery matrix");
   const uint32_t tsb = kFold4 ? tw_b<kTwB4>(tso) : tso;
   const v4i z = {0, 0, 0, 0};
 #pragma unroll
@@ -717,7 +842,7 @@ __device__ __forceinline__ void pass_p3(uint32_t (&x)[64], const v4i (&M)[4], Rs
     for (int i = 0; i < 4; ++i) a[i] = (int)x[p3(c, i)];
     const v4i tv = bld(tab, tvo, tso + (uint32_t)c * 1024u);
     v4i D[4];
-    tile<true, false>(D, M, a, z);
+    tile<true, false, QR>(D, M, a, z);
     if constexpr (kFold4) {
       uint32_t o[4];
       twist4<false>(o, D, tv, tab, tvo, 0, tsb + (uint32_t)c * 1024u, m);
@@ -726,7 +851,7 @@ __device__ __forceinline__ void pass_p3(uint32_t (&x)[64], const v4i (&M)[4], Rs
     } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int32_t r = recomb<false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
+        const int32_t r = recomb_x<QR, false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
         x[p3(c, i)] = (uint32_t)mont<true>(r, tv[i], m) ^ K32;
       }
     }
@@ -737,7 +862,9 @@ __device__ __forceinline__ void pass_p3(uint32_t (&x)[64], const v4i (&M)[4], Rs
 // pass 3 (F, P4 in place): each tile's centred outputs go to EPI(c, r, x)
 // at once (stored, or multiplied into the product), so no 64-bit reduction
 // result stays live beyond its tile.
-template <class EPI>
+// QR: recomb_q (plain matrix); the epilogue then gets |r| up to mf_build's
+// bound, not centred words.
+template <bool QR = false, class EPI>
 __device__ __forceinline__ void pass_p4(uint32_t (&x)[64], const v4i (&M)[4], const Mc& m, const EPI& epi) {
   const v4i z = {0, 0, 0, 0};
 #pragma unroll
@@ -747,10 +874,10 @@ __device__ __forceinline__ void pass_p4(uint32_t (&x)[64], const v4i (&M)[4], co
 #pragma unroll
     for (int i = 0; i < 4; ++i) b[i] = (int)x[p3(c, i)];
     v4i D[4];
-    tile<false, false>(D, M, b, z);
+    tile<false, false, QR>(D, M, b, z);
     int32_t r[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = recomb<false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
+    for (int i = 0; i < 4; ++i) r[i] = recomb_x<QR, false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
     epi(c, r, x);
     tile_fence();
   }
@@ -778,9 +905,12 @@ __device__ __forceinline__ v4i stash_get(uint32_t addr, int c) {
 // tv: tile 0's twists (each tile loads the next one's).
 // PK: the words are already in the passes' packed signed form (a product
 // epilogue's Montgomery output), so no bias and no compensation.
-template <bool PK = false>
-__device__ __forceinline__ void ipass_p4(uint32_t (&x)[64], const v4i (&M)[4], v4i comp, v4i tv, Rsrc tab,
+// QR: the first step as recomb_q (plain matrix; comp, comp2: the split
+// compensation).
+template <bool PK = false, bool QR = false>
+__device__ __forceinline__ void ipass_p4(uint32_t (&x)[64], const v4i (&M)[4], v4i comp, v4i comp2, v4i tv, Rsrc tab,
                                          uint32_t tvo, uint32_t tso, const Mc& m, uint32_t* lds, const Th& h) {
+  static_assert(!(QR && kFold4), "a folded pass keeps the Montgomery matrix");
   const uint32_t tsb = kFold4 ? tw_b<kTwB4>(tso) : tso;
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
@@ -791,9 +921,9 @@ __device__ __forceinline__ void ipass_p4(uint32_t (&x)[64], const v4i (&M)[4], v
     const v4i tn = c + 1 < 16 ? bld(tab, tvo, tso + (uint32_t)(c + 1) * 1024u) : tv;
     v4i D[4];
     if constexpr (PK)
-      tile<true, false>(D, M, a, v4i{0, 0, 0, 0});
+      tile<true, false, QR>(D, M, a, v4i{0, 0, 0, 0});
     else
-      tile<true, true>(D, M, a, comp);
+      tile<true, true, QR>(D, M, a, comp, comp2);
     if constexpr (kFold4) {
       uint32_t o[4];
       twist4<false>(o, D, tv, tab, tvo, 0, tsb + (uint32_t)c * 1024u, m);
@@ -802,7 +932,7 @@ __device__ __forceinline__ void ipass_p4(uint32_t (&x)[64], const v4i (&M)[4], v
     } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int32_t r = recomb<false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
+        const int32_t r = recomb_x<QR, false>(D[0][i], D[1][i], D[2][i], D[3][i], m);
         x[p3(c, i)] = (uint32_t)mont<true>(r, tv[i], m) ^ K32;
       }
     }
@@ -850,7 +980,7 @@ __device__ __forceinline__ void ipass_p3(uint32_t (&x)[64], const v4i (&M)[4], R
 }
 // inverse pass 1 (per-wave matrix) on P2 chunks [C0, C0 + 8) at q2 slots
 // (the registers after the Q3 -> P2 swap); packed output.
-template <int C0>
+template <int C0, bool QR = false>
 __device__ __forceinline__ void ipass_p2(uint32_t (&x)[64], const v4i (&M)[4], const Mc& m) {
   const v4i z = {0, 0, 0, 0};
 #pragma unroll
@@ -860,10 +990,10 @@ __device__ __forceinline__ void ipass_p2(uint32_t (&x)[64], const v4i (&M)[4], c
 #pragma unroll
     for (int i = 0; i < 4; ++i) b[i] = (int)x[q2(c, i)];
     v4i D[4];
-    tile<false, false>(D, M, b, z);
+    tile<false, false, QR>(D, M, b, z);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      x[q2(c, i)] = (uint32_t)recomb<true>(D[0][i], D[1][i], D[2][i], D[3][i], m) ^ K32;
+      x[q2(c, i)] = (uint32_t)recomb_x<QR, true>(D[0][i], D[1][i], D[2][i], D[3][i], m) ^ K32;
     pin4(x[q2(c, 0)], x[q2(c, 1)], x[q2(c, 2)], x[q2(c, 3)]);
     tile_fence();
   }
@@ -942,6 +1072,16 @@ __device__ __forceinline__ Tabs tabs_of(const void* mf, const LimbConst<uint32_t
   int64_t K = (int64_t)((uint64_t)K32 << 32), K0 = 0;
   int32_t one = 1, s16 = 65536;
   asm volatile("" : "+s"(one), "+s"(s16), "+s"(K), "+s"(K0));
+  if constexpr (kQrAny) {
+    // (opaque: as literals hipcc moves them to VGPRs, VOP3 takes no literal)
+    int32_t mu = ((const int32_t*)((const v4i*)mf + (size_t)l * kLimb + kQConst))[0];  // a scalar load
+    uint32_t nq = 0u - lc.q, kq = K32 - (kQrC << 24), kq0 = 0u - (kQrC << 24);
+    asm volatile("" : "+s"(mu), "+s"(nq), "+s"(kq), "+s"(kq0));
+    r.m.mu = mu;
+    r.m.nq = nq;
+    r.m.kq = kq;
+    r.m.kq0 = kq0;
+  }
   r.m.K = K;
   r.m.K0 = K0;
   r.m.one = one;
@@ -964,13 +1104,15 @@ struct NoEpi {
 // instead of being spilled to scratch memory (whose write-back is HBM
 // traffic); the caller guarantees no other wave touches that LDS then.
 // F3: pass 1's twist folded (not in the standalone forward, kFold3Fwd).
+// QR: the RNT_MF_QR mask of the caller's kernel (| kQrP4: the last pass too,
+// F4 then names a plain matrix).
 template <int NPARK, uint32_t PBASE, uint32_t PSTRIDE>
 __device__ __forceinline__ uint32_t park_addr(const uint32_t* lds, const Th& h) {
   static_assert(NPARK * 1024 <= (int)PSTRIDE && PBASE + 16 * PSTRIDE <= kLdsBytes, "park area");
   return (uint32_t)(uintptr_t)lds + PBASE + h.w * PSTRIDE + h.lam() * 16u;
 }
 template <bool SYNC1, int F4 = S_F4, bool Q4 = false, bool SYNCX = false, int NPARK = 0, uint32_t PBASE = 0,
-          uint32_t PSTRIDE = 0, bool F3 = kFold3, class EPI = NoEpi>
+          uint32_t PSTRIDE = 0, bool F3 = kFold3, int QR = 0, class EPI = NoEpi>
 __device__ __forceinline__ void fwd(uint32_t (&x2)[64], Rsrc src, uint32_t* lds, const Th& h, const Tabs& T,
                                     const EPI& epi = EPI{}) {
   // the first pass's operands load ahead of the plane (cache hits, needed
@@ -978,12 +1120,14 @@ __device__ __forceinline__ void fwd(uint32_t (&x2)[64], Rsrc src, uint32_t* lds,
   const Mc& m = T.m;
   const uint32_t lo = h.lam() * 16u;
   v4i M[4];
-  load_mat(M, T.tab, S_F1, lo);
-  const v4i comp = bld(T.tab, lo, (uint32_t)kCompF1 * 16u);
+  constexpr bool Q1 = (QR & 1) != 0, Q3 = (QR & 2) != 0, Q4P = (QR & kQrP4) != 0;
+  load_mat(M, T.tab, Q1 ? S_QF1 : S_F1, lo);
+  const v4i comp = bld(T.tab, lo, (uint32_t)(Q1 ? kQCompF1 : kCompF1) * 16u);
+  const v4i comp2 = Q1 ? bld(T.tab, lo, (uint32_t)(kQCompF1 + 64) * 16u) : comp;
   uint32_t x1[64];
   load_p1(x1, src, h);
   MF_STAMP(1);
-  pass_p1<0, true>(x1, M, comp, m);
+  pass_p1<0, true, Q1>(x1, M, comp, comp2, m);
   MF_STAMP(2);
   if constexpr (SYNC1) __syncthreads();
   uint32_t wb[4], rb[4];
@@ -991,7 +1135,7 @@ __device__ __forceinline__ void fwd(uint32_t (&x2)[64], Rsrc src, uint32_t* lds,
   if constexpr (Q4) {
     p1_bases4(wb, h);
     x_write_p1q<0>(x1, lds, wb);
-    pass_p1<8, true>(x1, M, comp, m);
+    pass_p1<8, true, Q1>(x1, M, comp, comp2, m);
     __syncthreads();
     p2_bases4(rb, h);
     x_read_p2q<0>(x2, lds, rb);
@@ -1018,7 +1162,7 @@ __device__ __forceinline__ void fwd(uint32_t (&x2)[64], Rsrc src, uint32_t* lds,
   } else {
   p1_bases(wb, h);
   x_write_p1<0>(x1, lds, wb);
-  pass_p1<8, true>(x1, M, comp, m);
+  pass_p1<8, true, Q1>(x1, M, comp, comp2, m);
   MF_STAMP(3);
   __syncthreads();
   MF_STAMP(4);
@@ -1050,11 +1194,11 @@ __device__ __forceinline__ void fwd(uint32_t (&x2)[64], Rsrc src, uint32_t* lds,
     for (int i = 0; i < 4; ++i) x2[4 * c + i] = (uint32_t)v[i];
   }
   swap_p2p3(x2);
-  load_mat(M, T.tab, S_F3, lo);
-  pass_p3(x2, M, T.tab, lo, (uint32_t)(kTw4fR + h.w * 1024) * 16u, m);
+  load_mat(M, T.tab, Q3 ? S_QF3 : S_F3, lo);
+  pass_p3<Q3>(x2, M, T.tab, lo, (uint32_t)(kTw4fR + h.w * 1024) * 16u, m);
   MF_STAMP(9);
   load_mat(M, T.tab, F4, lo);
-  pass_p4(x2, M, m, epi);
+  pass_p4<Q4P>(x2, M, m, epi);
   MF_STAMP(10);
 }
 
@@ -1067,13 +1211,15 @@ __device__ __forceinline__ void fwd(uint32_t (&x2)[64], Rsrc src, uint32_t* lds,
 // barriers, which it passes once it has used (so read) every word it loaded.
 // LOAD = false: the plane is already in x2 (P4 positions, canonical), as a
 // forward pass's epilogue left it; the LDS may still be read by other waves.
-template <bool LOAD, bool PK = false>
+template <bool LOAD, bool PK = false, int QR = 0>
 __device__ __forceinline__ void inv_x(uint32_t (&x2)[64], Rsrc pr, uint32_t* lds, const Th& h, const Tabs& T) {
   const Mc& m = T.m;
   const uint32_t lo = h.lam() * 16u;
   v4i M[4];
-  load_mat(M, T.tab, S_I4, lo);
-  const v4i comp = bld(T.tab, lo, (uint32_t)kCompI4 * 16u);
+  constexpr bool Q2 = (QR & 1) != 0, Q4 = (QR & 2) != 0;
+  load_mat(M, T.tab, Q4 ? S_QI4 : S_I4, lo);
+  const v4i comp = bld(T.tab, lo, (uint32_t)(Q4 ? kQCompI4 : kCompI4) * 16u);
+  const v4i comp2 = Q4 && !PK ? bld(T.tab, lo, (uint32_t)(kQCompI4 + 64) * 16u) : comp;
   const uint32_t t4s = (uint32_t)(kTw4iR + h.w * 1024) * 16u;
   const v4i tv0 = bld(T.tab, lo, t4s);
   if constexpr (LOAD) {
@@ -1086,18 +1232,18 @@ __device__ __forceinline__ void inv_x(uint32_t (&x2)[64], Rsrc pr, uint32_t* lds
   } else {
     __syncthreads();  // ipass_p4's stash reuses the LDS of the last exchange
   }
-  ipass_p4<PK>(x2, M, comp, tv0, T.tab, lo, t4s, m, lds, h);
+  ipass_p4<PK, Q4>(x2, M, comp, comp2, tv0, T.tab, lo, t4s, m, lds, h);
   load_mat(M, T.tab, S_I3, lo);
   ipass_p3(x2, M, T.tab, h.g() * 16u, (uint32_t)(kTw3iR + h.w * 64) * 16u, m, lds, h);
   swap_q3p2(x2);
-  load_mat(M, T.tab, S_I2 + h.w, lo);
+  load_mat(M, T.tab, (Q2 ? S_QI2 : S_I2) + h.w, lo);
   uint32_t wb[4], rb[4];
   uint32_t x1[64];
-  ipass_p2<0>(x2, M, m);
+  ipass_p2<0, Q2>(x2, M, m);
   __syncthreads();  // other waves may still read the LDS (the last forward exchange)
   p2_bases(rb, h);
   x_write_p2<0>(x2, lds, rb);
-  ipass_p2<8>(x2, M, m);
+  ipass_p2<8, Q2>(x2, M, m);
   __syncthreads();
   p1_bases(wb, h);
   x_read_p1<0>(x1, lds, wb);
@@ -1113,7 +1259,7 @@ __device__ __forceinline__ void inv_x(uint32_t (&x2)[64], Rsrc pr, uint32_t* lds
 }
 __device__ __forceinline__ void inv(Rsrc pr, uint32_t* lds, const Th& h, const Tabs& T) {
   uint32_t x2[64];
-  inv_x<true>(x2, pr, lds, h, T);
+  inv_x<true, false, kQrNtt>(x2, pr, lds, h, T);
 }
 
 }  // namespace mf
@@ -1138,7 +1284,7 @@ k_mf_ntt(uint32_t* __restrict__ data, const void* __restrict__ mft, const LimbCo
     // the last pass stores each tile, canonical, in the device order (in
     // place: every wave read its words of the plane before the first
     // exchange's barrier)
-    fwd<false, S_F4, false, false, 0, 0, 0, kFold3 && kFold3Fwd>(x, pr, lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) {
+    fwd<false, S_F4, false, false, 0, 0, 0, kFold3 && kFold3Fwd, kQrNttFwd>(x, pr, lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) {
       bst<kStreamAux>(v4i{(int)canon(r[0], T.m.q), (int)canon(r[1], T.m.q), (int)canon(r[2], T.m.q), (int)canon(r[3], T.m.q)}, pr,
           p4_lane(h), p4_soff(h, cc));
     });
@@ -1229,13 +1375,13 @@ k_mf_tensor(uint32_t* __restrict__ d0, uint32_t* __restrict__ d1, uint32_t* __re
   // both reads); the PMC bytes each build saves say whether that temporary
   // leaves the L2
   constexpr int MEAS = RNT_MF_TENSOR_MEAS;
-  fwd<false, S_F4, false, SX, NP, PB, PS>(x, rsrc(c0 + io, kN * 4u), lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) {
+  fwd<false, S_F4, false, SX, NP, PB, PS, kFold3, kQrTensor>(x, rsrc(c0 + io, kN * 4u), lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) {
     if constexpr (MEAS != 3) bst(canon4(r), R1, pl, p4_soff(h, cc));
   });
-  fwd<!SX, S_F4, false, SX, NP, PB, PS>(x, rsrc(c1 + io, kN * 4u), lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) {
+  fwd<!SX, S_F4, false, SX, NP, PB, PS, kFold3, kQrTensor>(x, rsrc(c1 + io, kN * 4u), lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) {
     if constexpr (MEAS != 1) bst(canon4(r), RS, pl, p4_soff(h, cc));
   });
-  fwd<!SX, S_F4, false, SX, NP, PB, PS>(x, rsrc(c0p + io, kN * 4u), lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) {
+  fwd<!SX, S_F4, false, SX, NP, PB, PS, kFold3, kQrTensor>(x, rsrc(c0p + io, kN * 4u), lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) {
     const v4i a0 = MEAS == 3 ? canon4(r) : bld(R1, pl, p4_soff(h, cc));
     const v4i a1 = MEAS == 1 ? canon4(r) : bld(RS, pl, p4_soff(h, cc));
     const v4i b = canon4(r);
@@ -1248,7 +1394,7 @@ k_mf_tensor(uint32_t* __restrict__ d0, uint32_t* __restrict__ d1, uint32_t* __re
     bst<kLastAux>(o0, R0, pl, p4_soff(h, cc));
     if constexpr (MEAS != 2) bst(t, R2, pl, p4_soff(h, cc));
   });
-  fwd<!SX, S_F4, false, RNT_MF_TENSOR_PARK4 && SX, RNT_MF_TENSOR_PARK4 ? NP : 0, PB, PS>(x, rsrc(c1p + io, kN * 4u), lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&xx)[64]) {
+  fwd<!SX, S_F4, false, RNT_MF_TENSOR_PARK4 && SX, RNT_MF_TENSOR_PARK4 ? NP : 0, PB, PS, kFold3, kQrTensor>(x, rsrc(c1p + io, kN * 4u), lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&xx)[64]) {
     const v4i b = canon4(r);
     const v4i a0 = MEAS == 3 ? b : bld<kLastAux>(R1, pl, p4_soff(h, cc));
     const v4i a1 = MEAS == 1 ? b : bld<kLastAux>(RS, pl, p4_soff(h, cc));
@@ -1270,7 +1416,7 @@ k_mf_tensor(uint32_t* __restrict__ d0, uint32_t* __restrict__ d1, uint32_t* __re
       bst<kLastAux>(v4i{(int)xx[p3(cc, 0)], (int)xx[p3(cc, 1)], (int)xx[p3(cc, 2)], (int)xx[p3(cc, 3)]}, RH, pl,
                     p4_soff(h, cc));
   });
-  inv_x<false>(x, R2, lds, h, T);
+  inv_x<false, false, kQrTensor>(x, R2, lds, h, T);
 }
 
 // RNT_MF_MUL_Q4: fwd(b) exchanges in quarter-plane rounds, and six a^
@@ -1346,7 +1492,12 @@ k_mf_mul(uint32_t* c, const uint32_t* a, const uint32_t* b, uint64_t ls, uint32_
   // (with Q4 the tiles overlap fwd(a)'s exchange region: SYNCX holds every
   // wave's last pass until all have read their last exchange words)
   constexpr int NP = RNT_MF_MUL_Q4 ? RNT_MF_MUL_PARK : 0;
-  fwd<false, S_F4S, false, RNT_MF_MUL_Q4 != 0, NP, kMulLdsBase * 4, kMulLdsTiles * 1024>(x, rsrc(a + o, kN * 4u), lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) {
+  // with the last pass in the plain form (recomb_q) a^ 2^32 comes from the
+  // plain reading of F 2^32, which is slot S_F4 as it stands, and b^ from the
+  // plain F (S_QF4)
+  constexpr int QM = kQrMul | ((kQrMul & 1) ? kQrP4 : 0);
+  constexpr int FA = (kQrMul & 1) ? S_F4 : S_F4S, FB = (kQrMul & 1) ? S_QF4 : S_F4;
+  fwd<false, FA, false, RNT_MF_MUL_Q4 != 0, NP, kMulLdsBase * 4, kMulLdsTiles * 1024, kFold3, QM>(x, rsrc(a + o, kN * 4u), lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&)[64]) {
     if (cc >= 16 - kMulLdsTiles)
       hat(cc - (16 - kMulLdsTiles)) = v4i{r[0], r[1], r[2], r[3]};
     else if (cc >= RNT_MF_MUL_MEAS_SKIP)
@@ -1355,14 +1506,15 @@ k_mf_mul(uint32_t* c, const uint32_t* a, const uint32_t* b, uint64_t ls, uint32_
   // fwd(b) needs no barrier before its first exchange write with Q4: every
   // wave passed fwd(a)'s SYNCX after its last read of fwd(a)'s exchange,
   // and fwd(b)'s quarter rounds stay below the a^ tiles
-  fwd<!(RNT_MF_MUL_Q4 && RNT_MF_MUL_NOSYNC1), S_F4, RNT_MF_MUL_Q4 != 0, (NP > 0), NP, 0, 4096>(x, rsrc(b + o, kN * 4u), lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&xx)[64]) {
+  fwd<!(RNT_MF_MUL_Q4 && RNT_MF_MUL_NOSYNC1), FB, RNT_MF_MUL_Q4 != 0, (NP > 0), NP, 0, 4096, kFold3, QM>(x, rsrc(b + o, kN * 4u), lds, h, T, [&](int cc, const int32_t (&r)[4], uint32_t (&xx)[64]) {
     const v4i ah = cc >= 16 - kMulLdsTiles ? hat(cc - (16 - kMulLdsTiles))
                    : cc < RNT_MF_MUL_MEAS_SKIP ? v4i{r[0], r[1], r[2], r[3]} : bld(RS, p4_lane(h), p4_soff(h, cc));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       // (a^ 2^32) b^ 2^-32, a signed Montgomery product of two pass
-      // outputs (|a^|, |b^| < q/2 + 2^14, so |v| < 5q/8 + 1, inside the
-      // packed range; mont() and mf_build): the exact product, in the
+      // outputs (|a^|, |b^| < q/2 + 2^14, so |v| < 5q/8 + 1, or up to
+      // recomb_q's bound, inside the packed range either way; mont() and
+      // mf_build): the exact product, in the
       // packed signed form the inverse's first pass takes as it is
       // (inv_x<false, true>)
       xx[p3(cc, i)] = (uint32_t)mont<true>(ah[i], r[i], T.m) ^ K32;
@@ -1372,7 +1524,7 @@ k_mf_mul(uint32_t* c, const uint32_t* a, const uint32_t* b, uint64_t ls, uint32_
     // lane of spills)
     pin4(xx[p3(cc, 0)], xx[p3(cc, 1)], xx[p3(cc, 2)], xx[p3(cc, 3)]);
   });
-  inv_x<false, true>(x, rsrc(c + o, kN * 4u), lds, h, T);
+  inv_x<false, true, kQrMul>(x, rsrc(c + o, kN * 4u), lds, h, T);
 }
 
 // ---------------------------------------------------------------------------
@@ -1456,6 +1608,33 @@ int mf_build(Tables* t, std::string* err) {
         return -1;
       }
     }
+    // recomb_q's outputs (see its comment), exactly, per prime: digit-sum
+    // halves |lo|, |hi| <= 2^28 + 2^20 + 2^15 (the last term: the split
+    // compensation an input-biased pass starts from), rho = 2^48 mod q.
+    //  - every output is handed on packed (or to mont(), int32): rq inside
+    //    the packed range;
+    //  - a two-step pass then multiplies by a twist |t| <= q/2 (mont<true>):
+    //    rq q / 2^33 + q/2 + 1 inside the packed range;
+    //  - k_mf_mul's product takes two last-pass outputs: rq^2 / 2^32 + q/2 + 1
+    //    inside the packed range (and rq^2 + 2^31 q < 2^63 follows from rq <
+    //    2^31).
+    // No consumer of a recomb_q word needs more: the next pass reads its byte
+    // digits whatever its size, and the words made canonical (canon(): r in
+    // (-q, q)) all come from Montgomery-form passes.
+    if (kQrAny) {
+      const uint64_t Bq = (1ull << 28) + (1ull << 20) + (1ull << 15), c8 = (uint64_t)kQrC << 8, c24 = (uint64_t)kQrC << 24;
+      const uint64_t mu = (1ull << 48) / q, rho = (1ull << 48) % q;
+      const uint64_t neg = Bq + c24 + (((Bq - c8) * rho) >> 32) + 1;
+      const int64_t pos = (int64_t)(Bq + q + (((Bq + c8) * rho) >> 32) + 1) - (int64_t)c24;
+      const uint64_t rq = pos > (int64_t)neg ? (uint64_t)pos : neg, lim = 0x7F7F7F7Full;
+      const bool ok = mu <= 0x7FFFFFFFull && rq <= lim &&
+                      (host::u128)rq * q / ((host::u128)1 << 33) + q / 2 + 1 < lim &&
+                      (host::u128)rq * rq / ((host::u128)1 << 32) + q / 2 + 1 < lim;
+      if (!ok) {
+        *err = "MFMA tables: the quotient-estimate reduction's bound exceeds the packed digit range for this prime";
+        return -1;
+      }
+    }
     // pass 0's matrix by running its four CT stages on unit vectors
     uint64_t M0[16][16];
     for (int k = 0; k < 16; ++k) {
@@ -1515,6 +1694,20 @@ int mf_build(Tables* t, std::string* err) {
     for (int k = 0; k < 16; ++k)
       for (int j = 0; j < 16; ++j) W[k][j] = mulmod(powmod(beta1i, (uint64_t)k, q), Fi[k][j], q);
     expand(W, q, R, false, 0, slot(S_I1));
+    // the plain matrices of the recomb_q passes (factor 1 instead of 2^32)
+    if (kQrAny) {
+      expand(M0, q, 1, false, 0, slot(S_QF1));
+      expand(F, q, 1, true, 0, slot(S_QF3));
+      expand(F, q, 1, false, 1, slot(S_QF4));
+      expand(Fi, q, 1, true, 1, slot(S_QI4));
+      for (int U = 0; U < 16; ++U) {
+        const uint64_t bei = itw[128 + 8 * U];
+        for (int k = 0; k < 16; ++k)
+          for (int j = 0; j < 16; ++j) W[k][j] = mulmod(powmod(bei, (uint64_t)k, q), Fi[k][j], q);
+        expand(W, q, 1, false, 0, slot(S_QI2 + U));
+      }
+      lt[(size_t)kQConst * 4] = (int32_t)(uint32_t)((1ull << 48) / q);
+    }
     // input-bias compensations: the data digits carry x - 2^30
     const uint64_t bias = mulmod(R, (1ull << 30) % q, q);
     {
@@ -1535,6 +1728,31 @@ int mf_build(Tables* t, std::string* err) {
           c1[lam * 4 + i] = cf[4 * i + (lam >> 4)];
           c4[lam * 4 + i] = ci[lam & 15];
         }
+      // the plain ones (no factor 2^32), split v = v0 + 2^16 v2 so that
+      // neither half of T grows by more than 2^15
+      if (kQrAny) {
+        const uint64_t pb = (1ull << 30) % q;
+        int32_t* q1 = lt + (size_t)kQCompF1 * 4;
+        int32_t* q4 = lt + (size_t)kQCompI4 * 4;
+        auto split = [](int32_t v, int32_t* v0, int32_t* v2) {
+          *v2 = (v + 32768) >> 16;
+          *v0 = v - *v2 * 65536;
+        };
+        for (int j = 0; j < 16; ++j) {
+          uint64_t s0 = 0, s1 = 0;
+          for (int k = 0; k < 16; ++k) {
+            s0 = (s0 + M0[j][k]) % q;
+            s1 = (s1 + Fi[j][k]) % q;
+          }
+          cf[j] = centred(mulmod(pb, s0, q), q);
+          ci[j] = centred(mulmod(pb, s1, q), q);
+        }
+        for (int lam = 0; lam < 64; ++lam)
+          for (int i = 0; i < 4; ++i) {
+            split(cf[4 * i + (lam >> 4)], &q1[lam * 4 + i], &q1[(64 + lam) * 4 + i]);
+            split(ci[lam & 15], &q4[lam * 4 + i], &q4[(64 + lam) * 4 + i]);
+          }
+      }
     }
     // twists, centred: Montgomery form t 2^32 in a family's single table, or,
     // folded, plain t in its A table and t 2^16 in its B table (same order)
