@@ -92,7 +92,8 @@ int rnt_device_count(int* n);
  * "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd",
  * "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
  * "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown",
- * "moddown_auto", "moddown_rescale", "lincomb"), the launch count and summed device milliseconds since enabling. */
+ * "moddown_auto", "moddown_rescale", "lincomb", "dot_tensor"), the launch
+ * count and summed device milliseconds since enabling. */
 int rnt_profile_enable(const rnt_ctx* ctx, int enable);
 int rnt_profile_read(const rnt_ctx* ctx, const char* kernel, uint64_t* launches,
                      double* total_ms);
@@ -482,10 +483,11 @@ int rnt_ct_mul_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, con
  * beta' = ceil(level / alpha); its logical poly g beta' + d on working limb t
  * is the stored plane (r(t) m beta + g beta + d) N with r(t) the limb map
  * above: a set's steps keep the full key's poly stride beta.
- * A view is accepted as the key argument(s) of the seven hybrid calls
+ * A view is accepted as the key argument(s) of the nine hybrid calls
  * (rnt_keyswitch_hybrid, rnt_ct_rotate_hybrid, rnt_ct_mul_relin_hybrid,
  * rnt_ct_rotate_hybrid_hoisted, rnt_ct_linear_bsgs_hybrid,
- * rnt_ct_mul_relin_rescale_hybrid, rnt_ct_linear_bsgs_hybrid_rescale), and the
+ * rnt_ct_mul_relin_rescale_hybrid, rnt_ct_linear_bsgs_hybrid_rescale,
+ * rnt_ct_dot_relin_hybrid, rnt_ct_dot_relin_rescale_hybrid), and the
  * call is then, word for word, the same call with the restricted key on a
  * root context over the view's moduli.  Both halves (and both sets of a BSGS
  * call) must be views on the SAME level-context handle; a view at level == L
@@ -658,6 +660,52 @@ int rnt_ct_lincomb(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_bu
  * on two contexts -> RNT_ERR_BASIS_MISMATCH.  Not recordable, as above. */
 int rnt_ct_lincomb_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1,
                            size_t n_in, size_t n_out, const uint64_t* weights, const uint64_t* bias);
+/* ---- ciphertext inner products with one relinearisation (DESIGN.md "Hybrid
+ * inner product with a single relinearisation") ------------------------------
+ * A sum of n_terms ciphertext x ciphertext products whose three tensor
+ * components are summed BEFORE the key-switch (lazy relinearisation).  x0, x1,
+ * y0, y1: n_terms B polys over a context C with Lv limbs, coefficient domain,
+ * term i of ciphertext b at poly i B + b (the layout rnt_ct_lincomb reads and
+ * rnt_ct_rotate_hybrid_hoisted writes).  With negacyclic products, exact mod
+ * every q_t:
+ *   d0 = sum_i x0_i y0_i   d1 = sum_i (x0_i y1_i + x1_i y0_i)   d2 = sum_i x1_i y1_i
+ *   (acc0, acc1) = rnt_keyswitch_hybrid(d2; key_a, key_b, alpha)
+ *   out = (d0 + acc0, d1 + acc1)        B polys over C, canonical, coefficient domain.
+ * These ARE the words of the composition "coefficient-domain rnt_mul and
+ * rnt_add for d0, d1, d2, then rnt_keyswitch_hybrid and rnt_add", and with
+ * n_terms == 1 the words of rnt_ct_mul_relin_hybrid.  With n_terms > 1 they
+ * are NOT the words of the sum of n_terms rnt_ct_mul_relin_hybrid results -- a
+ * ModDown of a sum is not the sum of ModDowns -- but the same decryption, the
+ * key-switch error entering once instead of n_terms times.  Any n_terms >= 1
+ * is valid: the terms are transformed and summed in groups, the key-switch
+ * runs once a chunk of ciphertexts.
+ * y may be x: y0 == x0 together with y1 == x1 is a sum of squares (each plane
+ * is then transformed once).  The inputs are never written.  No output
+ * aliases an input or the other output -> RNT_ERR_BAD_ARGUMENT.
+ * Errors: n_terms == 0, input poly counts that differ or are no multiple of
+ * n_terms, outputs of other than B polys -> RNT_ERR_BAD_ARGUMENT; inputs on
+ * different contexts, or an output on another context than the inputs' ->
+ * RNT_ERR_BASIS_MISMATCH; an NTT-domain input -> RNT_ERR_DOMAIN_MISMATCH;
+ * rnt_keyswitch_hybrid's rules and statuses for alpha, degree, device, moduli
+ * prefix, word width, the key's poly count (RNT_ERR_CHANNEL_COUNT, fields:
+ * beta, got) and the key's domain.  A key level view is accepted in the key
+ * positions, where it behaves word for word like the restricted key; in any
+ * other position -> RNT_ERR_UNSUPPORTED.  A refused call leaves its outputs
+ * untouched.  No host array is read: recordable after one plain run of the
+ * (E, Lv, alpha) triple, like the other hybrid calls. */
+int rnt_ct_dot_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1,
+                            const rnt_buf* y0, const rnt_buf* y1, size_t n_terms,
+                            const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha);
+/* rnt_ct_dot_relin_hybrid followed by rnt_ct_rescale, word for word (with
+ * n_terms == 1 the words of rnt_ct_mul_relin_rescale_hybrid): out0, out1 hold B
+ * polys on ONE shared context that is drop_last(1) of C.  Errors as above,
+ * then rnt_ct_mul_relin_rescale_hybrid's output rules: Lv == 1 ->
+ * RNT_ERR_INVALID_MOD_DROP (fields: 1, Lv); an output whose context is not
+ * drop_last(1) of C, or outputs on two contexts -> RNT_ERR_BASIS_MISMATCH; an
+ * output of other than B polys -> RNT_ERR_BAD_ARGUMENT. */
+int rnt_ct_dot_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1,
+                                    const rnt_buf* y0, const rnt_buf* y1, size_t n_terms,
+                                    const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha);
 
 /* ---- limb-sharded building blocks ------------------------ */
 /* A rank owning a contiguous run of the global basis' limbs holds every

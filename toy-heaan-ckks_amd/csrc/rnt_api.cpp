@@ -98,7 +98,7 @@ const char* const kKernelNames[rnt::K_COUNT] = {
     "automorphism", "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt",
     "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
     "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto",
-    "moddown_rescale", "lincomb"};
+    "moddown_rescale", "lincomb", "dot_tensor"};
 
 // A profiling call failed: clear the runtime's slot, keep the first failure
 // in the profiler, and stop profiling (rnt_profile_read reports it).
@@ -589,6 +589,8 @@ int to_coeff_into(const rnt_buf* src, void* dst) {
   return RNT_OK;
 }
 
+void lincomb_forget_stream(hipStream_t s);  // (with rnt_ct_lincomb's staging slots, below)
+
 }  // namespace
 
 rnt::Tables::~Tables() {
@@ -598,6 +600,7 @@ rnt::Tables::~Tables() {
   if (own_stream) {
     cleanup(hipStreamSynchronize(own_stream), "hipStreamSynchronize(context teardown)");
     pool_forget_stream(own_stream);
+    lincomb_forget_stream(own_stream);
     cleanup(hipStreamDestroy(own_stream), "hipStreamDestroy(context teardown)");
   }
   for (auto& e : resc_ext) cleanup(hipFree(e.second), "hipFree(context tables)");
@@ -3162,7 +3165,179 @@ int rescaled_outputs_check(const rnt_buf* out0, const rnt_buf* out1, const rnt_b
   return RNT_OK;
 }
 
+// The fused tail of a chunk of c ciphertexts whose tensor (d0, d1, d2) stands
+// ready: ModUp of D2 (coefficient domain, limb stride c N) into HW (D | A0 |
+// A1), the forward transform of the digits, the key products, two inverses and
+// two k_moddown_rescale launches into out0 / out1 (limb stride out_ls, Lv - 1
+// limbs).  seeded: D0 == A0 and D1 == A1 hold d0^ 2^-w, d1^ 2^-w in the
+// accumulators' first Lv limbs (k_hoist_mac_seed); else D0, D1 are the
+// canonical coefficient-domain d0, d1, ModDown's addends.
+int hybrid_rescale_tail(const HybridPlan& pl, size_t c, char* HW, bool seeded, const char* D0, const char* D1,
+                        const char* D2, const rnt_buf* key_a, const rnt_buf* key_b, char* out0, char* out1,
+                        uint64_t out_ls) {
+  const rnt::Tables* tc = pl.C->t.get();
+  const size_t n = tc->n, wb = word_bytes(tc);
+  const void* rinv = rnt::resc_inv_row(tc, pl.Lv - 1, 0);
+  const void* rinvp = rnt::resc_inv_row(tc, pl.Lv - 1, 1);
+  const uint64_t cls = (uint64_t)c * n;
+  const rnt::Launch ke = hybrid_launch(pl, c);
+  char* D = HW;
+  char* A0 = D + pl.LE * pl.beta * c * n * wb;
+  char* A1 = A0 + pl.LE * c * n * wb;
+  LAUNCH_ON(tc, ke.s, rnt::K_MODUP, rnt::launch_modup(ke, D, D2, cls, pl.hc), "ModUp");
+  rnt::Launch kd = ke;
+  kd.B = pl.beta * c;
+  if (int rc = fwd_raw(kd, D, (uint64_t)kd.B * n, tc)) return rc;
+  rnt::Launch km = ke;
+  km.Ls = pl.beta;
+  if (seeded) {
+    LAUNCH_ON(tc, ke.s, rnt::K_HOIST_MAC,
+              rnt::launch_hoist_mac_seed(km, A0, A1, D, key_a->data, key_b->data, limb_stride(key_a), A1, A0, cls,
+                                         pl.hc),
+              "hybrid key products (seeded)");
+  } else {
+    void* a0[1] = {A0};
+    void* a1[1] = {A1};
+    const void* ka[1] = {key_a->data};
+    const void* kb[1] = {key_b->data};
+    LAUNCH_ON(tc, ke.s, rnt::K_HOIST_MAC, rnt::launch_hoist_mac(km, a0, a1, 1, D, ka, kb, limb_stride(key_a)),
+              "hybrid key products");
+  }
+  if (int rc = inv_raw(ke, A0, cls, tc)) return rc;
+  if (int rc = inv_raw(ke, A1, cls, tc)) return rc;
+  LAUNCH_ON(tc, ke.s, rnt::K_MODDOWN_RESCALE,
+            rnt::launch_moddown_rescale(ke, out0, out_ls, A0, cls, seeded ? nullptr : D0, cls, rinv, rinvp, pl.hc),
+            "ModDown and rescale");
+  LAUNCH_ON(tc, ke.s, rnt::K_MODDOWN_RESCALE,
+            rnt::launch_moddown_rescale(ke, out1, out_ls, A1, cls, seeded ? nullptr : D1, cls, rinv, rinvp, pl.hc),
+            "ModDown and rescale");
+  return RNT_OK;
+}
+
+// The shared body of rnt_ct_dot_relin_hybrid and its rescaling form.  Per
+// chunk of ciphertexts and group of up to kDotT terms: the group's planes are
+// gathered into call-scoped workspace (the inputs are const) and transformed
+// there, k_dot_tensor sums d0^, d1^, d2^ (2^-w scaled; groups after the first
+// accumulate); then one inverse and unscale of d2 and the tail of the hybrid
+// multiply -- for the rescaling call with the seeds in the accumulators'
+// first Lv limbs where hybrid_same_transforms holds.
+int ct_dot_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0,
+                       const rnt_buf* x1, const rnt_buf* y0, const rnt_buf* y1, size_t n_terms, const rnt_buf* key_a,
+                       const rnt_buf* key_b, size_t alpha) {
+  const rnt_buf* in[4] = {x0, x1, y0, y1};
+  for (const rnt_buf* b : {(const rnt_buf*)out0, (const rnt_buf*)out1, x0, x1, y0, y1})
+    if (int rc = check_buf(b, name)) return rc;
+  if (n_terms == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: n_terms must be at least 1", name);
+  if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
+  for (const rnt_buf* b : in)
+    if (out0 == b || out1 == b || out0->data == b->data || out1->data == b->data)
+      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output aliases an input", name);
+  for (int i = 1; i < 4; ++i)
+    if (int rc = check_same(x0, in[i], name)) return rc;
+  if (x0->n_polys % n_terms != 0)
+    return fail(RNT_ERR_BAD_ARGUMENT, "%s: inputs of %zu polys are no %zu terms of a batch", name, x0->n_polys,
+                n_terms);
+  const size_t B = x0->n_polys / n_terms;
+  HybridPlan pl;
+  if (int rc = hybrid_check(name, x0->ctx, key_a, key_b, alpha, &pl)) return rc;
+  for (const rnt_buf* b : in)
+    if (b->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: inputs must be in coefficient domain", name);
+  const size_t L = x0->ctx->L;
+  if (rescale && L < 2)  // poly.rs:191-197
+    return fail_fields(RNT_ERR_INVALID_MOD_DROP, 1, L, "invalid mod-drop count 1 for %zu channels", L);
+  for (const rnt_buf* o : {out0, out1}) {
+    if (rescale ? (o->ctx->t != x0->ctx->t || o->ctx->L != L - 1) : o->ctx != x0->ctx)
+      return fail(RNT_ERR_BASIS_MISMATCH, "%s: an output's basis is not %sthe inputs'", name,
+                  rescale ? "drop_last(1) of " : "");
+    if (o->n_polys != B)
+      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output of %zu polys for a batch of %zu", name, o->n_polys, B);
+  }
+  if (out0->ctx != out1->ctx)  // engine.rs:272-274: one shared new basis
+    return fail(RNT_ERR_BASIS_MISMATCH, "%s: outputs must share one basis", name);
+  if (int rc = set_device(x0->ctx)) return rc;
+  if (int rc = hybrid_prepare(&pl)) return rc;
+  rnt::Launch k = launch_for(x0);
+  const size_t n = k.t->n, wb = word_bytes(k.t);
+  const bool sq = y0->data == x0->data && y1->data == x1->data;  // a sum of squares: each plane transformed once
+  const size_t nx = sq ? 2 : 4;
+  const size_t gmax = std::min<size_t>(n_terms, rnt::kDotT);
+  const bool seeded = rescale && hybrid_same_transforms(pl);
+  const size_t nd = seeded ? 1 : 3;  // d2 (and, un-seeded, d0 and d1) over the ciphertext limbs
+  const size_t bc = hybrid_chunk(pl, B, (nx * gmax + nd) * L);
+  const size_t chunk_words = L * bc * n;
+  // ws: X0 | X1 | [Y0 | Y1] (gmax terms each) | D2 | [D0 | D1] | the chunk's D, A0, A1
+  CallWs cws(out0);
+  if (int rc = cws.get(std::max<size_t>(((nx * gmax + nd) * chunk_words + hybrid_planes(pl) * bc * n) * wb, 16)))
+    return rc;
+  char* X[4];
+  for (size_t j = 0; j < 4; ++j) X[j] = (char*)cws.p + (j % nx) * gmax * chunk_words * wb;
+  char* D2 = (char*)cws.p + nx * gmax * chunk_words * wb;
+  char* HW = D2 + nd * chunk_words * wb;
+  const uint64_t full_ls = limb_stride(x0), out_ls = limb_stride(out0);
+  for (size_t p0 = 0; p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    rnt::Launch kc = k;
+    kc.B = c;
+    const uint64_t cls = (uint64_t)c * n;
+    const size_t po = p0 * n * wb;
+    char* A0 = HW + pl.LE * pl.beta * c * n * wb;
+    char* A1 = A0 + pl.LE * c * n * wb;
+    char* D0 = seeded ? A0 : D2 + chunk_words * wb;
+    char* D1 = seeded ? A1 : D0 + chunk_words * wb;
+    for (size_t t0 = 0; t0 < n_terms; t0 += gmax) {
+      const size_t g = std::min(gmax, n_terms - t0);
+      rnt::Launch kg = k;
+      kg.B = g * c;
+      const uint64_t gls = (uint64_t)g * cls;
+      for (size_t j = 0; j < nx; ++j) {
+        // term t of the chunk: polys [t B + p0, t B + p0 + c) of every limb; one run a limb where the chunk is the batch
+        const size_t runs = c == B ? 1 : g;
+        for (size_t i = 0; i < runs; ++i)
+          LAUNCH(kc.t, rnt::K_COPY,
+                 rnt::launch_copy_rows(kc.s, X[j] + i * cls * wb, gls * wb,
+                                       (const char*)in[j]->data + ((t0 + i) * B + p0) * n * wb, full_ls * wb,
+                                       (c == B ? gls : cls) * wb, L),
+                 "term gather");
+        if (int rc = fwd_raw(kg, X[j], gls)) return rc;
+      }
+      LAUNCH(kc.t, rnt::K_DOT_TENSOR,
+             rnt::launch_dot_tensor(kc, D0, D1, D2, cls, X[0], X[1], X[2], X[3], gls, cls, g, t0 != 0), "dot tensor");
+    }
+    // INV(d^ 2^-w) 2^w = d, canonical: d2 for ModUp; un-seeded, d0 and d1 for ModDown's addends
+    for (char* Dx : {D2, D0, D1}) {
+      if (seeded && Dx != D2) continue;
+      if (int rc = inv_raw(kc, Dx, cls)) return rc;
+      LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 1, Dx, Dx, nullptr, 0, false), "seed unscale");
+    }
+    if (rescale) {
+      if (int rc = hybrid_rescale_tail(pl, c, HW, seeded, D0, D1, D2, key_a, key_b, (char*)out0->data + po,
+                                       (char*)out1->data + po, out_ls))
+        return rc;
+    } else {
+      if (int rc = hybrid_chunk_run(pl, c, HW, D2, cls, key_a, key_b, (char*)out0->data + po, (char*)out1->data + po,
+                                    out_ls, D0, D1, cls))
+        return rc;
+    }
+  }
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
 }  // namespace
+
+extern "C" int rnt_ct_dot_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1,
+                                       const rnt_buf* y0, const rnt_buf* y1, size_t n_terms, const rnt_buf* key_a,
+                                       const rnt_buf* key_b, size_t alpha) {
+  return ct_dot_hybrid_body("rnt_ct_dot_relin_hybrid", false, out0, out1, x0, x1, y0, y1, n_terms, key_a, key_b,
+                            alpha);
+}
+
+extern "C" int rnt_ct_dot_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1,
+                                               const rnt_buf* y0, const rnt_buf* y1, size_t n_terms,
+                                               const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha) {
+  return ct_dot_hybrid_body("rnt_ct_dot_relin_rescale_hybrid", true, out0, out1, x0, x1, y0, y1, n_terms, key_a,
+                            key_b, alpha);
+}
 
 extern "C" int rnt_keyswitch_hybrid(rnt_buf* acc0, rnt_buf* acc1, const rnt_buf* d, const rnt_buf* key_a,
                                     const rnt_buf* key_b, size_t alpha) {
@@ -3347,9 +3522,6 @@ extern "C" int rnt_ct_mul_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, con
   for (int i = 0; i < 4; ++i) T[i] = ws + i * chunk_words * wb;
   char* D2 = ws + nt * chunk_words * wb;
   char* HW = D2 + nd * chunk_words * wb;
-  const rnt::Tables* tc = pl.C->t.get();
-  const void* rinv = rnt::resc_inv_row(tc, L - 1, 0);
-  const void* rinvp = rnt::resc_inv_row(tc, L - 1, 1);
   const uint64_t full_ls = limb_stride(c0), out_ls = limb_stride(out0);
   for (size_t p0 = 0; p0 < B; p0 += bc) {
     const size_t c = std::min(bc, B - p0);
@@ -3358,9 +3530,7 @@ extern "C" int rnt_ct_mul_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, con
     const uint64_t cls = (uint64_t)c * n;
     const size_t po = p0 * n * wb;
     auto off = [&](const rnt_buf* b) { return (const char*)b->data + po; };
-    const rnt::Launch ke = hybrid_launch(pl, c);
-    char* D = HW;
-    char* A0 = D + pl.LE * pl.beta * c * n * wb;
+    char* A0 = HW + pl.LE * pl.beta * c * n * wb;
     char* A1 = A0 + pl.LE * c * n * wb;
     char* D0 = seeded ? A0 : D2 + chunk_words * wb;
     char* D1 = seeded ? A1 : D0 + chunk_words * wb;
@@ -3371,35 +3541,9 @@ extern "C" int rnt_ct_mul_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, con
         if (int rc = inv_raw(kc, Dx, cls)) return rc;
         LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 1, Dx, Dx, nullptr, 0, false), "seed unscale");
       }
-    LAUNCH_ON(tc, ke.s, rnt::K_MODUP, rnt::launch_modup(ke, D, D2, cls, pl.hc), "ModUp");
-    rnt::Launch kd = ke;
-    kd.B = pl.beta * c;
-    if (int rc = fwd_raw(kd, D, (uint64_t)kd.B * n, tc)) return rc;
-    rnt::Launch km = ke;
-    km.Ls = pl.beta;
-    if (seeded) {
-      LAUNCH_ON(tc, ke.s, rnt::K_HOIST_MAC,
-                rnt::launch_hoist_mac_seed(km, A0, A1, D, key_a->data, key_b->data, limb_stride(key_a), A1, A0, cls,
-                                           pl.hc),
-                "hybrid key products (seeded)");
-    } else {
-      void* a0[1] = {A0};
-      void* a1[1] = {A1};
-      const void* ka[1] = {key_a->data};
-      const void* kb[1] = {key_b->data};
-      LAUNCH_ON(tc, ke.s, rnt::K_HOIST_MAC, rnt::launch_hoist_mac(km, a0, a1, 1, D, ka, kb, limb_stride(key_a)),
-                "hybrid key products");
-    }
-    if (int rc = inv_raw(ke, A0, cls, tc)) return rc;
-    if (int rc = inv_raw(ke, A1, cls, tc)) return rc;
-    LAUNCH_ON(tc, ke.s, rnt::K_MODDOWN_RESCALE,
-              rnt::launch_moddown_rescale(ke, (char*)out0->data + po, out_ls, A0, cls, seeded ? nullptr : D0, cls, rinv,
-                                          rinvp, pl.hc),
-              "ModDown and rescale");
-    LAUNCH_ON(tc, ke.s, rnt::K_MODDOWN_RESCALE,
-              rnt::launch_moddown_rescale(ke, (char*)out1->data + po, out_ls, A1, cls, seeded ? nullptr : D1, cls, rinv,
-                                          rinvp, pl.hc),
-              "ModDown and rescale");
+    if (int rc = hybrid_rescale_tail(pl, c, HW, seeded, D0, D1, D2, key_a, key_b, (char*)out0->data + po,
+                                     (char*)out1->data + po, out_ls))
+      return rc;
   }
   out0->in_ntt = out1->in_ntt = 0;
   return RNT_OK;
@@ -4333,11 +4477,26 @@ struct LcSlot {
   void* p = nullptr;
   size_t bytes = 0;
   hipEvent_t ev = nullptr;
+  hipStream_t stream = nullptr;  // of the copy the event was last recorded behind
   int device = -1;
   bool busy = false;
 };
 thread_local LcSlot g_lc_slots[kLcSlots];
 thread_local unsigned g_lc_next = 0;
+
+// A stream about to be destroyed, already synchronised (pool_forget_stream's
+// rule: an event must not outlive the stream it was last recorded on -- the
+// runtime consults that stream when the event is waited for): the copies this
+// thread's slots queued on it are complete, so the slots drop their events.
+void lincomb_forget_stream(hipStream_t s) {
+  for (LcSlot& slot : g_lc_slots)
+    if (slot.ev && slot.stream == s) {
+      cleanup(hipEventDestroy(slot.ev), "hipEventDestroy(lincomb weights of a stream being destroyed)");
+      slot.ev = nullptr;
+      slot.stream = nullptr;
+      slot.busy = false;
+    }
+}
 
 int lincomb_stage(int device, size_t bytes, LcSlot** out) {
   LcSlot& s = g_lc_slots[g_lc_next++ % kLcSlots];
@@ -4443,6 +4602,7 @@ int lincomb_impl(const char* name, bool rescale, rnt_buf* out0, rnt_buf* out1, c
   if (int rc = cws.get(std::max<size_t>(words * wb, 16))) return rc;
   HIP_TRY(hipMemcpyAsync(cws.p, slot->p, words * wb, hipMemcpyHostToDevice, k.s), "hipMemcpyAsync(lincomb weights)");
   HIP_TRY(hipEventRecord(slot->ev, k.s), "hipEventRecord(lincomb weights)");
+  slot->stream = k.s;
   slot->busy = true;
   const char* w = (const char*)cws.p;
   const size_t nw = Lv * n_out * n_in * wb;

@@ -155,7 +155,7 @@ enum KernelId {
   K_AUTOMORPHISM, K_KS_DECOMPOSE, K_KS_ROWS, K_TENSOR_ROWS, K_IMPORT, K_EXPORT, K_CRT,
   K_SFFT, K_SAMPLE, K_COPY, K_PLANE_FUSED, K_MF_NTT_FWD, K_MF_NTT_INV, K_WHOLE_FWD, K_WHOLE_INV, K_WHOLE_MUL,
   K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_MODUP, K_MODDOWN,
-  K_MODDOWN_AUTO, K_MODDOWN_RESCALE, K_LINCOMB, K_COUNT
+  K_MODDOWN_AUTO, K_MODDOWN_RESCALE, K_LINCOMB, K_DOT_TENSOR, K_COUNT
 };
 
 struct Prof {
@@ -450,6 +450,17 @@ constexpr size_t kLincombMax = 16;
 hipError_t launch_lincomb(const Launch& k, void* out0, void* out1, uint64_t out_ls, const void* x0, const void* x1,
                           uint64_t in_ls, size_t n_in, size_t n_out, const void* w, const void* wp, const void* bias,
                           bool rescale);
+// launch_dot_tensor (k_dot_tensor): the tensor sums of nt <= kDotT terms of a
+// ciphertext inner product.  k.L = Lv limbs, k.B = the chunk's ciphertexts;
+// x0 / x1 / y0 / y1: NTT-domain planes at limb stride in_ls, term i at
+// + i term_words of a limb; d0 / d1 / d2: sum_i x0_i y0_i, sum_i (x0_i y1_i +
+// x1_i y0_i), sum_i x1_i y1_i, each times 2^-w, at limb stride out_ls -- added
+// to the words already there with `accum`.  y0 == x0 with y1 == x1 takes the
+// squares form (two loads a term).  The outputs alias no input.
+constexpr size_t kDotT = 4;
+hipError_t launch_dot_tensor(const Launch& k, void* d0, void* d1, void* d2, uint64_t out_ls, const void* x0,
+                             const void* x1, const void* y0, const void* y1, uint64_t in_ls, uint64_t term_words,
+                             size_t nt, bool accum);
 // launch_hoist_mac_seed (k_hoist_mac_seed): launch_hoist_mac for one step whose
 // sums start, on the limbs j < hc.Lv, from seed_b[j] (P 2^w mod q_j) and
 // seed_a[j] (P 2^w mod q_j) and from 0 on the special limbs; the seeds are

@@ -2649,6 +2649,90 @@ k_lincomb(W* __restrict__ out0, W* __restrict__ out1, const W* __restrict__ x0, 
   }
 }
 
+// The accumulated tensor of rnt_ct_dot_relin[_rescale]_hybrid: with x0^, x1^,
+// y0^, y1^ the forward-transformed planes of a group of nt <= DOT_T terms
+// ([L][nt c][N] at limb stride in_ls, term i of the chunk's c ciphertexts at
+// + i term_words of a limb plane),
+//   d0^ = sum_i x0^_i y0^_i   d1^ = sum_i (x0^_i y1^_i + x1^_i y0^_i)
+//   d2^ = sum_i x1^_i y1^_i,
+// each scaled by 2^-w (Montgomery products of plain NTT words: the seed
+// convention k_hoist_mac_seed consumes and k_tensor_rows produces), at limb
+// stride out_ls.  A lane owns one vector of the c N positions of the chunk on
+// limb blockIdx.y and loops over the terms; with `accum` (uniform) the sums
+// are added to the words already stored, so a group after the first extends
+// the sums of the groups before it.  SQ: y is x (a sum of squares), two loads
+// a term and d1^ = sum_i 2 x0^_i x1^_i.  Every product is reduced
+// (mont_mul: a, b < q -> < q) and every sum is an add_mod of two canonical
+// words, so no bound depends on the modulus or on the number of terms.  The
+// loop over the DOT_T terms is unrolled behind a uniform guard, so the loads of
+// the next terms are issued under the products of this one.
+constexpr int DOT_T = (int)kDotT;
+struct DotGeom {
+  uint64_t limb_words, term_words, in_ls, out_ls;
+  uint32_t nt, accum;
+};
+template <class W, bool VEC, bool SQ>
+__global__ void __launch_bounds__(256)
+k_dot_tensor(W* __restrict__ d0, W* __restrict__ d1, W* __restrict__ d2, const W* __restrict__ x0,
+             const W* __restrict__ x1, const W* y0, const W* y1, DotGeom a, TabPtrs<W> tp, LimbMap lm) {
+  // (y0, y1 without __restrict__: with SQ they are x0, x1 and are not read)
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint32_t l = blockIdx.y;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= a.limb_words) return;
+  const LimbConst<W> lc = tp.lc[root_limb(l, lm)];
+  const uint64_t in = (uint64_t)l * a.in_ls + i;
+  W s0[V], s1[V], s2[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) s0[v] = s1[v] = s2[v] = (W)0;
+#pragma unroll
+  for (int tt = 0; tt < DOT_T; ++tt) {
+    if ((uint32_t)tt < a.nt) {  // (uniform)
+      const uint64_t g = in + (uint64_t)tt * a.term_words;
+      W a0[V], a1[V];
+      ld_vec<W, VEC, V>(a0, x0 + g);
+      ld_vec<W, VEC, V>(a1, x1 + g);
+      if constexpr (SQ) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const W c = mont_mul<W>(a0[v], a1[v], lc.q, lc.qinv);
+          s0[v] = add_mod<W>(s0[v], mont_mul<W>(a0[v], a0[v], lc.q, lc.qinv), lc.q);
+          s1[v] = add_mod<W>(s1[v], add_mod<W>(c, c, lc.q), lc.q);
+          s2[v] = add_mod<W>(s2[v], mont_mul<W>(a1[v], a1[v], lc.q, lc.qinv), lc.q);
+        }
+      } else {
+        W b0[V], b1[V];
+        ld_vec<W, VEC, V>(b0, y0 + g);
+        ld_vec<W, VEC, V>(b1, y1 + g);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const W c = add_mod<W>(mont_mul<W>(a0[v], b1[v], lc.q, lc.qinv),
+                                 mont_mul<W>(a1[v], b0[v], lc.q, lc.qinv), lc.q);
+          s0[v] = add_mod<W>(s0[v], mont_mul<W>(a0[v], b0[v], lc.q, lc.qinv), lc.q);
+          s1[v] = add_mod<W>(s1[v], c, lc.q);
+          s2[v] = add_mod<W>(s2[v], mont_mul<W>(a1[v], b1[v], lc.q, lc.qinv), lc.q);
+        }
+      }
+    }
+  }
+  const uint64_t o = (uint64_t)l * a.out_ls + i;
+  if (a.accum) {  // (uniform)
+    W p0[V], p1[V], p2[V];
+    ld_vec<W, VEC, V>(p0, d0 + o);
+    ld_vec<W, VEC, V>(p1, d1 + o);
+    ld_vec<W, VEC, V>(p2, d2 + o);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      s0[v] = add_mod<W>(p0[v], s0[v], lc.q);
+      s1[v] = add_mod<W>(p1[v], s1[v], lc.q);
+      s2[v] = add_mod<W>(p2[v], s2[v], lc.q);
+    }
+  }
+  st_vec<W, VEC, V>(d0 + o, s0);
+  st_vec<W, VEC, V>(d1 + o, s1);
+  st_vec<W, VEC, V>(d2 + o, s2);
+}
+
 // Gather kernels: grid y = limb, x = the limb's B*N words (no per-thread
 // division).  XCD-aware deal along x: hardware block b of a row runs on XCD
 // b % 8 (gridDim.x is a multiple of 8), so logical block (b % 8) *
@@ -3492,6 +3576,43 @@ static hipError_t lincomb_t(const Launch& k, void* out0, void* out1, uint64_t ou
   return hipGetLastError();
 }
 
+// k.L = Lv limbs, k.B = the chunk's ciphertexts (rnt_internal.hpp).
+template <class W>
+static hipError_t dot_tensor_t(const Launch& k, void* d0, void* d1, void* d2, uint64_t out_ls, const void* x0,
+                               const void* x1, const void* y0, const void* y1, uint64_t in_ls, uint64_t term_words,
+                               size_t nt, bool accum) {
+  const uint64_t N = 1ull << k.t->log_n;
+  const uint64_t limb_words = (uint64_t)k.B * N;
+  if (nt == 0 || nt > kDotT || !limb_map_ok(k) || out_ls < limb_words || term_words < limb_words ||
+      in_ls < (nt - 1) * term_words + limb_words || !d0 || !d1 || !d2 || !x0 || !x1 || !y0 || !y1)
+    return hipErrorInvalidValue;
+  if (limb_words == 0 || k.L == 0) return hipSuccess;
+  constexpr int V = 16 / (int)sizeof(W);
+  // 16-byte accesses: whole vectors within a plane, every plane and term 16-byte aligned
+  const bool vec = N % V == 0 && in_ls % V == 0 && out_ls % V == 0 && term_words % V == 0 &&
+                   ((uintptr_t)d0 | (uintptr_t)d1 | (uintptr_t)d2 | (uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)y0 |
+                    (uintptr_t)y1) % 16 == 0;
+  const bool sq = x0 == y0 && x1 == y1;
+  const uint64_t per = vec ? limb_words / V : limb_words;
+  const uint64_t bx = (per + 255) / 256;
+  if (bx > 0x7fffffffull || k.L > 65535) return hipErrorInvalidConfiguration;
+  const dim3 grid((unsigned)bx, (unsigned)k.L);
+  DotGeom a;
+  a.limb_words = limb_words;
+  a.term_words = term_words;
+  a.in_ls = in_ls;
+  a.out_ls = out_ls;
+  a.nt = (uint32_t)nt;
+  a.accum = accum ? 1u : 0u;
+#define RNT_DT(VEC, SQ)                                                                                      \
+  hipLaunchKernelGGL((k_dot_tensor<W, VEC, SQ>), grid, dim3(256), 0, k.s, (W*)d0, (W*)d1, (W*)d2, (const W*)x0, \
+                     (const W*)x1, (const W*)y0, (const W*)y1, a, tab_ptrs<W>(k.t), limb_map(k))
+  if (vec) { if (sq) RNT_DT(true, true); else RNT_DT(true, false); }
+  else { if (sq) RNT_DT(false, true); else RNT_DT(false, false); }
+#undef RNT_DT
+  return hipGetLastError();
+}
+
 static uint64_t inv_mod_pow2(uint64_t h, uint64_t M) {
   // h odd, M power of two: Newton iteration for h^-1 mod 2^64, then mask.
   uint64_t x = h;  // correct to 3 bits
@@ -4044,6 +4165,12 @@ hipError_t launch_lincomb(const Launch& k, void* out0, void* out1, uint64_t out_
                           bool rescale) {
   RNT_WIDE(lincomb_t<uint32_t>(k, out0, out1, out_ls, x0, x1, in_ls, n_in, n_out, w, wp, bias, rescale),
            lincomb_t<uint64_t>(k, out0, out1, out_ls, x0, x1, in_ls, n_in, n_out, w, wp, bias, rescale));
+}
+hipError_t launch_dot_tensor(const Launch& k, void* d0, void* d1, void* d2, uint64_t out_ls, const void* x0,
+                             const void* x1, const void* y0, const void* y1, uint64_t in_ls, uint64_t term_words,
+                             size_t nt, bool accum) {
+  RNT_WIDE(dot_tensor_t<uint32_t>(k, d0, d1, d2, out_ls, x0, x1, y0, y1, in_ls, term_words, nt, accum),
+           dot_tensor_t<uint64_t>(k, d0, d1, d2, out_ls, x0, x1, y0, y1, in_ls, term_words, nt, accum));
 }
 hipError_t launch_hoist_mac_seed(const Launch& k, void* acc0, void* acc1, const void* d, const void* key_a,
                                  const void* key_b, uint64_t key_ls, const void* seed_a, const void* seed_b,

@@ -44,6 +44,7 @@ __all__ = [
     "linear_transform_bsgs_hybrid",
     "mul_ciphertexts_hybrid_rescale",
     "linear_transform_bsgs_hybrid_rescale",
+    "dot_ciphertexts_hybrid",
     "Ciphertext",
     "generate_primes",
     "is_ntt_friendly_prime",
@@ -1278,6 +1279,42 @@ def ct_lincomb(ct: Ciphertext, n_in: int, weights, bias=None, rescale: bool = Tr
     check(call(out0.handle, out1.handle, ct.c0.handle, ct.c1.handle, n_in, n_out, _u64p(w),
                None if b is None else _u64p(b)))
     return Ciphertext(out0, out1, ct.logp - bits_dropped, ct.logq - bits_dropped)
+
+
+def dot_ciphertexts_hybrid(ctx: Ciphertext, cty: Ciphertext, n_terms: int, rlk: RnsHybridKey,
+                           rescale: bool = True, out_basis: Optional[RnsBasis] = None) -> Ciphertext:
+    """``sum_i ctx_i * cty_i`` over the ``n_terms`` ciphertexts packed in each
+    operand (a batch of ``n_terms * B``, term i of ciphertext b at ``i * B +
+    b``, the layout ``ct_lincomb`` reads) with ONE relinearisation
+    (rnt_ct_dot_relin_hybrid / rnt_ct_dot_relin_rescale_hybrid): the three
+    tensor components are summed first, the key-switch runs on their d2, and
+    with ``rescale`` the result is rescaled in the closing kernels.  ``cty``
+    may be ``ctx`` itself (a sum of squares).  A batch of ``B`` comes back; its
+    words are those of the coefficient-domain composition, not of ``n_terms``
+    hybrid multiplies added up (the same message, the key-switch error once).
+    logp / logq as in :func:`mul_ciphertexts_hybrid_rescale`; ``out_basis``
+    likewise (``drop_last(1)`` of the inputs' with ``rescale``, else theirs)."""
+    _require_class(rlk, RnsHybridKey, "dot_ciphertexts_hybrid")
+    assert ctx.logq == cty.logq, "logq mismatch in hybrid inner product"
+    n_terms = int(n_terms)
+    if n_terms < 1 or ctx.c0.n_polys % n_terms != 0:
+        raise ValueError(f"dot_ciphertexts_hybrid: a batch of {ctx.c0.n_polys} polys is no {n_terms} terms of "
+                         "ciphertexts")
+    basis = ctx.c0.basis
+    rlk = _at_ct_level(rlk, basis)
+    bits_dropped = 0
+    if rescale:
+        bits_dropped = basis.moduli()[-1].bit_length()
+        new_basis = out_basis if out_basis is not None else basis.drop_last(1)
+    else:
+        new_basis = out_basis if out_basis is not None else basis
+    B = ctx.c0.n_polys // n_terms
+    out0 = RnsPoly(new_basis, B, _uninit=True)
+    out1 = RnsPoly(new_basis, B, _uninit=True)
+    call = load().rnt_ct_dot_relin_rescale_hybrid if rescale else load().rnt_ct_dot_relin_hybrid
+    check(call(out0.handle, out1.handle, ctx.c0.handle, ctx.c1.handle, cty.c0.handle, cty.c1.handle, n_terms,
+               rlk.a.handle, rlk.b.handle, rlk.alpha))
+    return Ciphertext(out0, out1, ctx.logp + cty.logp - bits_dropped, ctx.logq - bits_dropped)
 
 
 def rescale_ciphertext(ct: Ciphertext) -> Ciphertext:

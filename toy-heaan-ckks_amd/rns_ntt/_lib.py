@@ -164,6 +164,8 @@ SIGNATURES = {
                                                   c_size_t, _P, _P, _P, _P, _P, c_size_t]),
     "rnt_copy_polys": (c_int, [_P, c_size_t, _P, c_size_t, c_size_t]),
     "rnt_ct_rescale": (c_int, [_P, _P, _P, _P]),
+    "rnt_ct_dot_relin_hybrid": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, _P, _P, c_size_t]),
+    "rnt_ct_dot_relin_rescale_hybrid": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, _P, _P, c_size_t]),
     "rnt_ct_lincomb": (c_int, [_P, _P, _P, _P, c_size_t, c_size_t, _U64P, _U64P]),
     "rnt_ct_lincomb_rescale": (c_int, [_P, _P, _P, _P, c_size_t, c_size_t, _U64P, _U64P]),
     "rnt_encode": (c_int, [_P, c_void_p, c_size_t, c_uint32]),

@@ -24,7 +24,8 @@ from typing import Optional
 import numpy as np
 
 from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsGadgetKeySet, RnsHybridKey,
-               RnsHybridKeySet, RnsPoly, bsgs_diagonal_rows, check, ct_lincomb, linear_transform, linear_transform_bsgs,
+               RnsHybridKeySet, RnsPoly, bsgs_diagonal_rows, check, ct_lincomb, dot_ciphertexts_hybrid, linear_transform,
+               linear_transform_bsgs,
                linear_transform_bsgs_hoisted, linear_transform_bsgs_hybrid, linear_transform_bsgs_hybrid_rescale,
                linear_transform_hybrid, load, mul_ciphertexts_gadget, mul_ciphertexts_hybrid,
                mul_ciphertexts_hybrid_rescale, poly_eval_plan, rescale_ciphertext, rotate_ciphertext,
@@ -193,6 +194,7 @@ class CkksEngine:
     rotate_ciphertext_hybrid = staticmethod(rotate_ciphertext_hybrid)
     mul_ciphertexts_hybrid = staticmethod(mul_ciphertexts_hybrid)
     mul_ciphertexts_hybrid_rescale = staticmethod(mul_ciphertexts_hybrid_rescale)
+    dot_ciphertexts_hybrid = staticmethod(dot_ciphertexts_hybrid)
 
     def generate_hybrid_rotation_key_set(self, sk: RnsPoly, steps, rng, alpha: int,
                                          hoisted: bool = False) -> RnsHybridKeySet:
