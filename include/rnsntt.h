@@ -237,6 +237,11 @@ int rnt_crt_centered(const rnt_buf* buf, uint64_t* host, size_t n_polys, size_t 
  * rnt_buf_wrap makes a NON-owning buffer over caller device memory laid out
  * [L][n_polys][N] in the context's word width (device-internal order when
  * in_ntt); rnt_buf_device_ptr exposes a buffer's storage and word width.
+ * device_ptr must be aligned to that word width (rnt_buf_device_ptr's
+ * word_bytes: 4 or 8), else RNT_ERR_BAD_ARGUMENT; no more is asked, and every
+ * op accepts such a buffer.  16-byte alignment selects the faster
+ * instantiations of the kernels that have two ("Alignment of
+ * caller planes").
  * Library writes to that storage (including rnt_buf_alloc's zeroing) are
  * queued on the context's stream: order external reads after it (or call
  * rnt_sync). */

@@ -1207,6 +1207,11 @@ extern "C" int rnt_buf_wrap(const rnt_ctx* ctx, void* device_ptr, size_t n_polys
   if (ctx->is_level())
     return fail_fields(RNT_ERR_UNSUPPORTED, 0, 0, "rnt_buf_wrap: a level context holds key views alone");
   if (n_polys == 0) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_buf_wrap: empty batch");
+  // word alignment is the whole contract (rnsntt.h): the one-word kernel
+  // forms load and store W at a time, and a u64 word at % 8 == 4 is no word
+  const size_t wb = word_bytes(ctx->t.get());
+  if ((uintptr_t)device_ptr % wb != 0)
+    return fail(RNT_ERR_BAD_ARGUMENT, "rnt_buf_wrap: device_ptr is not aligned to the context's %zu-byte words", wb);
   rnt_buf* b = new (std::nothrow) rnt_buf;
   if (!b) return fail(RNT_ERR_OUT_OF_MEMORY, "rnt_buf_wrap");
   b->ctx = ctx;
