@@ -304,6 +304,15 @@ def test_errors(gpu):
     fails("DomainMismatch", rot, c1=ntt)
     fails("DomainMismatch", mul, c1=ntt)
     fails("DomainMismatch", mul, c0p=ntt)
+    # two faults at once: the multiply compares all six operands with out0,
+    # then checks alpha and the key, then the inputs' domain
+    apart = rn.RnsPoly(rn.RnsBasis(c.mod, n), B)  # the right limbs on a root of their own
+    fails("BasisMismatch", mul, c1p=apart, alpha=0)
+    fails("BasisMismatch", mul, c0=apart, ka=keypoly(c.beta + 1))
+    fails("BadArgument", mul, c1=rn.RnsPoly(Bd, B + 1), kb=keypoly(c.beta, ntt=False))
+    fails("BadArgument", mul, c1=ntt, alpha=0)
+    fails("ChannelCountMismatch", mul, {"expected": c.beta, "actual": c.beta + 1}, c0=ntt, ka=keypoly(c.beta + 1))
+    fails("BasisMismatch", mul, c0p=ntt, ka=keypoly(c.beta, Bd), kb=keypoly(c.beta, Bd))
     # the valid calls still run after all that
     v0, v1 = rn.RnsPoly(Bd, B), rn.RnsPoly(Bd, B)
     rn.check(rot(out0=v0, out1=v1))

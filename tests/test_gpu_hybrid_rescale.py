@@ -374,6 +374,25 @@ def test_errors(gpu):
     one = Case(gpu, 8, 1, 1, 1, B, 31, seed=6)
     fails("InvalidModDrop", mul, {"drop_count": 1, "channel_count": 1}, c0=one.ct.c0, c1=one.ct.c1, c0p=one.ctp.c0,
           c1p=one.ctp.c1, ka=one.key.a, kb=one.key.b, alpha=1)
+    # two faults at once: the multiply compares the inputs with c0, then checks
+    # alpha and the key, then the inputs' domain, and the outputs last
+    ntt = c.ct.c0.clone()
+    ntt.to_ntt_domain()
+    apart = rn.RnsPoly(rn.RnsBasis(c.mod, n), B)  # the right limbs on a root of their own
+    fails("BasisMismatch", mul, c1p=apart, alpha=0)
+    fails("BadArgument", mul, c0p=rn.RnsPoly(Bd, B + 1), ka=keypoly(c.beta + 1, c.ext))
+    fails("BadArgument", mul, out0=rn.RnsPoly(Bd, B), alpha=0)
+    fails("DomainMismatch", mul, out0=rn.RnsPoly(Bd, B), c0=ntt)
+    fails("DomainMismatch", mul, out1=rn.RnsPoly(low, B + 1), kb=keypoly(c.beta, c.ext, ntt=False))
+    fails("ChannelCountMismatch", mul, {"expected": c.beta, "actual": c.beta + 1}, c0=ntt,
+          ka=keypoly(c.beta + 1, c.ext))
+    fails("ChannelCountMismatch", mul, {"expected": c.beta, "actual": 1}, out0=rn.RnsPoly(low, B + 1),
+          kb=keypoly(1, c.ext))
+    fails("BasisMismatch", mul, out0=rn.RnsPoly(Bd, B + 1))  # an output's basis before its size
+    one_ntt = one.ct.c1.clone()
+    one_ntt.to_ntt_domain()
+    fails("DomainMismatch", mul, c0=one.ct.c0, c1=one_ntt, c0p=one.ctp.c0, c1p=one.ctp.c1, ka=one.key.a,
+          kb=one.key.b, alpha=1)  # a one-limb ciphertext in the NTT domain
     one_b = BsgsCase(gpu, 8, 1, 1, 1, B, 31, baby=[0, 1], giant=[0, 2], seed=6)
     fails("InvalidModDrop", lin, {"drop_count": 1, "channel_count": 1}, c0=one_b.ct.c0, c1=one_b.ct.c1, d=one_b.d,
           bka=one_b.bset.a, bkb=one_b.bset.b, gka=one_b.gset.a, gkb=one_b.gset.b, alpha=1)

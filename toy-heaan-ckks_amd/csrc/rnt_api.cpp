@@ -2147,6 +2147,61 @@ extern "C" int rnt_keyswitch_ext(rnt_buf* acc0, rnt_buf* acc1, const void* src, 
   return RNT_OK;
 }
 
+namespace {
+
+// Scratch blocks (of the outputs' size) the tensor needs: none on the
+// whole-plane rings, one for the matrix-core tensor (N = 2^16, u32; it uses
+// plane_scratch_planes(L B) <= L B planes of it), the four-step path's four
+// column outputs.
+size_t tensor_blocks(const rnt::Launch& k) { return rnt::tensor_whole_ok(k.t) ? 0 : use_mf(k) ? 1 : 4; }
+
+// The tensor of every multiply for kc.B polys (inputs in the coefficient
+// domain at limb stride in_ls, read in place): d0^, d1^ (NTT domain, scaled by
+// 2^-w as the key-switch seeds are, engine.rs:486-493) and the
+// coefficient-domain d2, each at limb stride ls.  T: tensor_blocks(kc) scratch
+// blocks.  The gadget key-switch's diagonal (kc.d2hat) travels in kc.
+int tensor(const rnt::Launch& kc, char* const* T, void* D0, void* D1, void* D2, uint64_t ls, const void* c0,
+           const void* c1, const void* c0p, const void* c1p, uint64_t in_ls) {
+  switch (tensor_blocks(kc)) {
+    case 0:
+      LAUNCH(kc.t, rnt::K_TENSOR_WHOLE, rnt::launch_tensor_whole(kc, D0, D1, D2, ls, c0, c1, c0p, c1p, in_ls),
+             "tensor whole");
+      break;
+    case 1:
+      LAUNCH(kc.t, rnt::K_MF_TENSOR, rnt::launch_mf_tensor(kc, D0, D1, D2, ls, c0, c1, c0p, c1p, in_ls, T[0]),
+             "MFMA tensor");
+      break;
+    default:
+      LAUNCH(kc.t, rnt::K_COL_FWD, rnt::launch_col_fwd(kc, T[0], c0, T[1], c1, in_ls, ls), "tensor column");
+      LAUNCH(kc.t, rnt::K_COL_FWD, rnt::launch_col_fwd(kc, T[2], c0p, T[3], c1p, in_ls, ls), "tensor column");
+      LAUNCH(kc.t, rnt::K_TENSOR_ROWS, rnt::launch_tensor_rows(kc, D0, D1, D2, T[0], T[1], T[2], T[3], ls),
+             "tensor rows");
+      // d2 -> coefficient domain (engine.rs:493), in place
+      LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, D2, ls, D2, ls, 1, nullptr), "d2 inverse");
+  }
+  return RNT_OK;
+}
+
+// The output rules of a call that ends in a rescale: both outputs on one
+// drop_last(1) context of the input's, n_polys polys each.
+int rescaled_outputs_check(const char* name, const rnt_buf* out0, const rnt_buf* out1, const rnt_buf* in,
+                           size_t n_polys) {
+  const size_t L = in->ctx->L;
+  if (L < 2)  // poly.rs:191-197
+    return fail_fields(RNT_ERR_INVALID_MOD_DROP, 1, L, "invalid mod-drop count 1 for %zu channels", L);
+  for (const rnt_buf* o : {out0, out1}) {
+    if (o->ctx->t != in->ctx->t || o->ctx->L != L - 1)
+      return fail(RNT_ERR_BASIS_MISMATCH, "%s: an output's basis is not drop_last(1) of the inputs'", name);
+    if (o->n_polys != n_polys)
+      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output of %zu polys for a batch of %zu", name, o->n_polys, n_polys);
+  }
+  if (out0->ctx != out1->ctx)  // engine.rs:272-274: one shared new basis
+    return fail(RNT_ERR_BASIS_MISMATCH, "%s: outputs must share one basis", name);
+  return RNT_OK;
+}
+
+}  // namespace
+
 extern "C" int rnt_ct_tensor(rnt_buf* d0, rnt_buf* d1, rnt_buf* d2, const rnt_buf* c0,
                              const rnt_buf* c1, const rnt_buf* c0p, const rnt_buf* c1p) {
   const rnt_buf* all[7] = {d0, d1, d2, c0, c1, c0p, c1p};
@@ -2162,35 +2217,16 @@ extern "C" int rnt_ct_tensor(rnt_buf* d0, rnt_buf* d1, rnt_buf* d2, const rnt_bu
         return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_tensor: outputs must not alias other operands");
   if (int rc = set_device(c0->ctx)) return rc;
   rnt::Launch k = launch_for(c0);
-  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t);
+  const size_t plane = k.t->n * word_bytes(k.t), block = k.L * c0->n_polys * plane;
   const uint64_t ls = limb_stride(c0);
-  if (rnt::tensor_whole_ok(k.t)) {
-    LAUNCH(k.t, rnt::K_TENSOR_WHOLE,
-           rnt::launch_tensor_whole(k, d0->data, d1->data, d2->data, ls, c0->data, c1->data, c0p->data, c1p->data, ls),
-           "tensor whole");
-    d0->in_ntt = d1->in_ntt = 1;
-    d2->in_ntt = 0;
-    return RNT_OK;
-  }
+  const size_t nt = tensor_blocks(k);
   CallWs ws(d0);
-  if (use_mf(k)) {  // N = 2^16, u32: the matrix-core tensor, one launch
-    if (int rc = ws.get(rnt::plane_scratch_planes((uint64_t)L * c0->n_polys) * n * wb)) return rc;
-    LAUNCH(k.t, rnt::K_MF_TENSOR,
-           rnt::launch_mf_tensor(k, d0->data, d1->data, d2->data, ls, c0->data, c1->data, c0p->data, c1p->data,
-                                 ls, ws.p),
-           "MFMA tensor");
-    d0->in_ntt = d1->in_ntt = 1;
-    d2->in_ntt = 0;
-    return RNT_OK;
-  }
-  if (int rc = ws.get(4 * L * c0->n_polys * n * wb)) return rc;
-  char* T[4];
-  for (int i = 0; i < 4; ++i) T[i] = (char*)ws.p + i * L * c0->n_polys * n * wb;
-  LAUNCH(k.t, rnt::K_COL_FWD, rnt::launch_col_fwd(k, T[0], c0->data, T[1], c1->data, ls, ls), "tensor column");
-  LAUNCH(k.t, rnt::K_COL_FWD, rnt::launch_col_fwd(k, T[2], c0p->data, T[3], c1p->data, ls, ls), "tensor column");
-  LAUNCH(k.t, rnt::K_TENSOR_ROWS,
-         rnt::launch_tensor_rows(k, d0->data, d1->data, d2->data, T[0], T[1], T[2], T[3], ls), "tensor rows");
-  LAUNCH(k.t, rnt::K_COL_INV, rnt::launch_col_inv(k, d2->data, ls, d2->data, ls, 1, nullptr), "d2 inverse");
+  // (the matrix-core tensor's scratch at its own size, not a whole block)
+  if (nt)
+    if (int rc = ws.get(nt == 1 ? rnt::plane_scratch_planes((uint64_t)k.L * c0->n_polys) * plane : 4 * block)) return rc;
+  char* T[4] = {};
+  for (size_t i = 0; i < nt; ++i) T[i] = (char*)ws.p + i * block;
+  if (int rc = tensor(k, T, d0->data, d1->data, d2->data, ls, c0->data, c1->data, c0p->data, c1p->data, ls)) return rc;
   d0->in_ntt = d1->in_ntt = 1;
   d2->in_ntt = 0;
   return RNT_OK;
@@ -2211,14 +2247,11 @@ static int ct_mul_relin_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
   // ws: [T0..T3 (column outputs, chunk-local)] | D0 | D1 | D2 | key-switch (S|U0|U1)
   // [| LAST0 | LAST1 with resc]
   // (the whole-plane tensor reads the ciphertexts directly: no T)
-  const bool whole = rnt::tensor_whole_ok(k.t);
-  const bool mf = !whole && use_mf(k);
   const size_t chunk_words = L * bc * n;
-  // (the matrix-core tensor's scratch: plane_scratch_planes(L bc) <= L bc planes)
-  const size_t nt = whole ? 0 : mf ? 1 : 4;
+  const size_t nt = tensor_blocks(k);
   // the key-switch's diagonal from the tensor's d2^ (one more chunk plane
   // set, D2H): the four-step key-switch on tiled grids, whose tensor writes it
-  const bool diag = k.t->ks_diag && !whole && !rnt::ks_whole_ok(k.t) && rnt::col_resc_ok(k.t);
+  const bool diag = k.t->ks_diag && nt != 0 && !rnt::ks_whole_ok(k.t) && rnt::col_resc_ok(k.t);
   const size_t need = ((nt + 3 + (diag ? 1 : 0)) * chunk_words + ks_scratch_words(k.t, L, bc) +
                        (resc ? 2 * bc * n : 0)) * wb;
   CallWs cws(out0);
@@ -2245,24 +2278,8 @@ static int ct_mul_relin_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
       kc.d2hat_ls = cls;
     }
     auto off = [&](const rnt_buf* b) { return (const char*)b->data + p0 * n * wb; };
-    if (whole) {
-      // d0^, d1^ NTT-resident and d2 in coefficient domain (engine.rs:486-493), one
-      // launch reading the ciphertexts in place (full limb stride) into D0..D2 (chunk's)
-      LAUNCH(kc.t, rnt::K_TENSOR_WHOLE,
-             rnt::launch_tensor_whole(kc, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls),
-             "tensor whole");
-    } else if (mf) {
-      // the same on the matrix-core transforms (N = 2^16), T0.. as its scratch
-      LAUNCH(kc.t, rnt::K_MF_TENSOR,
-             rnt::launch_mf_tensor(kc, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls, T[0]),
-             "MFMA tensor");
-    } else {
-    LAUNCH(kc.t, rnt::K_COL_FWD, rnt::launch_col_fwd(kc, T[0], off(c0), T[1], off(c1), full_ls, cls), "tensor column");
-    LAUNCH(kc.t, rnt::K_COL_FWD, rnt::launch_col_fwd(kc, T[2], off(c0p), T[3], off(c1p), full_ls, cls), "tensor column");
-    LAUNCH(kc.t, rnt::K_TENSOR_ROWS, rnt::launch_tensor_rows(kc, D0, D1, D2, T[0], T[1], T[2], T[3], cls), "tensor rows");
-    // d2 -> coefficient domain (engine.rs:493), in place in D2
-    LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, D2, cls, D2, cls, 1, nullptr), "d2 inverse");
-    }
+    // the ciphertexts read in place (full limb stride) into the chunk's D0..D2
+    if (int rc = tensor(kc, T, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls)) return rc;
     if (resc) {
       // gadget sum into the chunk's NTT-row accumulators, then the inverse
       // with the rescale fused (engine.rs:263-282 after :530-531)
@@ -2339,16 +2356,7 @@ extern "C" int rnt_ct_mul_relin_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_
                                         const rnt_buf* c1, const rnt_buf* c0p, const rnt_buf* c1p,
                                         const rnt_buf* key_a, const rnt_buf* key_b) {
   if (int rc = ct_mul_check(out0, out1, c0, c1, c0p, c1p, key_a, key_b, "rnt_ct_mul_relin_rescale")) return rc;
-  const size_t L = c0->ctx->L;
-  if (L < 2)  // poly.rs:191-197
-    return fail_fields(RNT_ERR_INVALID_MOD_DROP, 1, L, "invalid mod-drop count 1 for %zu channels", L);
-  for (const rnt_buf* o : {(const rnt_buf*)out0, (const rnt_buf*)out1}) {
-    if (o->ctx->t != c0->ctx->t || o->ctx->L != L - 1)
-      return fail(RNT_ERR_BASIS_MISMATCH, "rescale: output basis is not drop_last(1) of the input's");
-    if (o->n_polys != c0->n_polys) return fail(RNT_ERR_BAD_ARGUMENT, "rescale: batch sizes differ");
-  }
-  if (out0->ctx != out1->ctx)  // engine.rs:272-274: one shared new basis
-    return fail(RNT_ERR_BASIS_MISMATCH, "rescale_ciphertext: outputs must share one basis");
+  if (int rc = rescaled_outputs_check("rnt_ct_mul_relin_rescale", out0, out1, c0, c0->n_polys)) return rc;
   if (rnt::col_resc_ok(c0->ctx->t.get()) && !rnt::ks_whole_ok(c0->ctx->t.get()))
     return ct_mul_relin_body(out0, out1, c0, c1, c0p, c1p, key_a, key_b, true);
   // small rings (the whole-plane key-switch, no column inverse): the product,
@@ -3089,61 +3097,129 @@ size_t hybrid_chunk(const HybridPlan& pl, size_t B, size_t extra) {
   return std::min(std::max<size_t>(B, 1), std::max<size_t>(t->ks_ws_bytes / per, 1));
 }
 
-// One chunk of c polys: x (coefficient domain, the chunk's first poly, limb
-// stride x_ls over the ciphertext's limbs) -> out0 = ModDown(sum_d ModUp_d(x)
-// key_b[d]) (+ add0), out1 with key_a (+ add1), at limb stride out_ls; the
-// addends (optional, coefficient domain) at add_ls.  ws: D | A0 | A1.  Every
-// launch runs on the ciphertext context's stream and counts in its profile;
-// the transforms and constants are the key basis'.
-int hybrid_chunk_run(const HybridPlan& pl, size_t c, char* ws, const void* x, uint64_t x_ls, const rnt_buf* key_a,
-                     const rnt_buf* key_b, void* out0, void* out1, uint64_t out_ls, const void* add0,
-                     const void* add1, uint64_t add_ls) {
+// The key-switch workspace of a chunk of c polys, carved from one block: the
+// raised digits D ([LE][beta c][N]) | the accumulators A0 | A1 ([LE][c][N]),
+// over the key basis.  hybrid_planes() is its size in planes per poly.
+struct HybridWs {
+  char *D, *A0, *A1;
+  HybridWs(const HybridPlan& pl, size_t c, void* ws) : D((char*)ws) {
+    const size_t pe = pl.LE * c * pl.C->t->n * word_bytes(pl.C->t.get());
+    A0 = D + pl.beta * pe;
+    A1 = A0 + pe;
+  }
+};
+
+// The stages of every hybrid call, for c polys.  Every launch runs on the
+// ciphertext context's stream and counts in its profile; the transforms, the
+// limb map and the constants are the key basis'.
+//
+// Raise: D = the forward transforms of ModUp_d(x), x in the coefficient domain
+// at limb stride x_ls over the ciphertext's limbs.
+int hybrid_raise(const HybridPlan& pl, size_t c, char* D, const void* x, uint64_t x_ls) {
   const rnt::Tables* tc = pl.C->t.get();
-  const rnt::Tables* te = pl.E->t.get();
-  const size_t n = te->n, wb = word_bytes(te);
   const rnt::Launch k = hybrid_launch(pl, c);
-  char* D = ws;
-  char* A0 = D + pl.LE * pl.beta * c * n * wb;
-  char* A1 = A0 + pl.LE * c * n * wb;
-  const uint64_t cls = (uint64_t)c * n;
   LAUNCH_ON(tc, k.s, rnt::K_MODUP, rnt::launch_modup(k, D, x, x_ls, pl.hc), "ModUp");
   rnt::Launch kd = k;
   kd.B = pl.beta * c;
-  if (int rc = fwd_raw(kd, D, (uint64_t)kd.B * n, tc)) return rc;
-  rnt::Launch km = k;
+  return fwd_raw(kd, D, (uint64_t)kd.B * tc->n, tc);
+}
+
+// Products: A0 = sum_d D_d key_b[d], A1 with key_a (one key: beta polys at
+// limb stride key_ls) -- stored, added to what A0 / A1 hold, or started from
+// the seeds d0^ 2^-w, d1^ 2^-w that stand in the accumulators' first Lv limbs
+// (k_hoist_mac_seed: A = sum + P d, so ModDown(A) = ModDown(sum) + d).
+enum class HybridMac { set, accumulate, seeded };
+int hybrid_products(const HybridPlan& pl, size_t c, const char* D, char* A0, char* A1, const void* key_a,
+                    const void* key_b, uint64_t key_ls, HybridMac mode) {
+  const rnt::Tables* tc = pl.C->t.get();
+  rnt::Launch km = hybrid_launch(pl, c);
   km.Ls = pl.beta;
   void* a0[1] = {A0};
   void* a1[1] = {A1};
-  const void* ka[1] = {key_a->data};
-  const void* kb[1] = {key_b->data};
-  LAUNCH_ON(tc, k.s, rnt::K_HOIST_MAC, rnt::launch_hoist_mac(km, a0, a1, 1, D, ka, kb, limb_stride(key_a)),
-            "hybrid key products");
-  if (int rc = inv_raw(k, A0, cls, tc)) return rc;
-  if (int rc = inv_raw(k, A1, cls, tc)) return rc;
-  LAUNCH_ON(tc, k.s, rnt::K_MODDOWN, rnt::launch_moddown(k, out0, out_ls, A0, cls, add0, add_ls, pl.hc), "ModDown");
-  LAUNCH_ON(tc, k.s, rnt::K_MODDOWN, rnt::launch_moddown(k, out1, out_ls, A1, cls, add1, add_ls, pl.hc), "ModDown");
+  const void* ka[1] = {key_a};
+  const void* kb[1] = {key_b};
+  switch (mode) {
+    case HybridMac::set:
+      LAUNCH_ON(tc, km.s, rnt::K_HOIST_MAC, rnt::launch_hoist_mac(km, a0, a1, 1, D, ka, kb, key_ls),
+                "hybrid key products");
+      break;
+    case HybridMac::accumulate:
+      LAUNCH_ON(tc, km.s, rnt::K_HOIST_MAC, rnt::launch_hoist_mac_acc(km, a0, a1, 1, D, ka, kb, key_ls),
+                "hybrid key products (accumulating)");
+      break;
+    case HybridMac::seeded:
+      LAUNCH_ON(tc, km.s, rnt::K_HOIST_MAC,
+                rnt::launch_hoist_mac_seed(km, A0, A1, D, key_a, key_b, key_ls, A1, A0, (uint64_t)c * tc->n, pl.hc),
+                "hybrid key products (seeded)");
+  }
   return RNT_OK;
 }
 
-// The tensor of the hybrid multiplies for one chunk (kc.B polys, inputs at
-// limb stride in_ls): d0^, d1^ (NTT domain, scaled by 2^-w) and the
-// coefficient-domain d2, each at limb stride cls.  T: the four-step path's
-// column outputs (four chunk blocks), the matrix-core path's scratch (one).
-int hybrid_tensor(const rnt::Launch& kc, bool whole, bool mf, char* const* T, char* D0, char* D1, char* D2,
-                  uint64_t cls, const char* c0, const char* c1, const char* c0p, const char* c1p, uint64_t in_ls) {
-  if (whole) {
-    LAUNCH(kc.t, rnt::K_TENSOR_WHOLE, rnt::launch_tensor_whole(kc, D0, D1, D2, cls, c0, c1, c0p, c1p, in_ls),
-           "tensor whole");
-  } else if (mf) {
-    LAUNCH(kc.t, rnt::K_MF_TENSOR, rnt::launch_mf_tensor(kc, D0, D1, D2, cls, c0, c1, c0p, c1p, in_ls, T[0]),
-           "MFMA tensor");
-  } else {
-    LAUNCH(kc.t, rnt::K_COL_FWD, rnt::launch_col_fwd(kc, T[0], c0, T[1], c1, in_ls, cls), "tensor column");
-    LAUNCH(kc.t, rnt::K_COL_FWD, rnt::launch_col_fwd(kc, T[2], c0p, T[3], c1p, in_ls, cls), "tensor column");
-    LAUNCH(kc.t, rnt::K_TENSOR_ROWS, rnt::launch_tensor_rows(kc, D0, D1, D2, T[0], T[1], T[2], T[3], cls), "tensor rows");
-    LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, D2, cls, D2, cls, 1, nullptr), "d2 inverse");
+// Lower: both accumulators back to the coefficient domain, then out0 =
+// ModDown(A0) (+ add0), out1 = ModDown(A1) (+ add1) at limb stride out_ls, the
+// optional coefficient-domain addends at add_ls; with `rescale` the results
+// are rescaled by their last limb on the way out (k_moddown_rescale, Lv - 1
+// output limbs).
+int hybrid_lower(const HybridPlan& pl, size_t c, char* A0, char* A1, void* out0, void* out1, uint64_t out_ls,
+                 const void* add0, const void* add1, uint64_t add_ls, bool rescale) {
+  const rnt::Tables* tc = pl.C->t.get();
+  const rnt::Launch k = hybrid_launch(pl, c);
+  const uint64_t cls = (uint64_t)c * tc->n;
+  if (int rc = inv_raw(k, A0, cls, tc)) return rc;
+  if (int rc = inv_raw(k, A1, cls, tc)) return rc;
+  const char* A[2] = {A0, A1};
+  void* out[2] = {out0, out1};
+  const void* add[2] = {add0, add1};
+  for (int o = 0; o < 2; ++o) {
+    if (rescale) {
+      LAUNCH_ON(tc, k.s, rnt::K_MODDOWN_RESCALE,
+                rnt::launch_moddown_rescale(k, out[o], out_ls, A[o], cls, add[o], add_ls,
+                                            rnt::resc_inv_row(tc, pl.Lv - 1, 0), rnt::resc_inv_row(tc, pl.Lv - 1, 1),
+                                            pl.hc),
+                "ModDown and rescale");
+    } else {
+      LAUNCH_ON(tc, k.s, rnt::K_MODDOWN, rnt::launch_moddown(k, out[o], out_ls, A[o], cls, add[o], add_ls, pl.hc),
+                "ModDown");
+    }
   }
   return RNT_OK;
+}
+
+// One chunk of c polys through the three stages with one key: raise x, the
+// products (seeded: from the seeds the caller's tensor left in ws.A0 / ws.A1),
+// lower into out0 / out1.
+int hybrid_chunk_run(const HybridPlan& pl, size_t c, const HybridWs& ws, const void* x, uint64_t x_ls,
+                     const rnt_buf* key_a, const rnt_buf* key_b, void* out0, void* out1, uint64_t out_ls,
+                     const void* add0, const void* add1, uint64_t add_ls, bool rescale = false,
+                     bool seeded = false) {
+  if (int rc = hybrid_raise(pl, c, ws.D, x, x_ls)) return rc;
+  if (int rc = hybrid_products(pl, c, ws.D, ws.A0, ws.A1, key_a->data, key_b->data, limb_stride(key_a),
+                               seeded ? HybridMac::seeded : HybridMac::set))
+    return rc;
+  return hybrid_lower(pl, c, ws.A0, ws.A1, out0, out1, out_ls, add0, add1, add_ls, rescale);
+}
+
+// INV(d^ 2^-w) 2^w = d, canonical: a tensor output (kc.B polys at limb stride
+// ls) back to the coefficient domain, in place.
+int seeds_to_coeff(const rnt::Launch& kc, char* Dx, uint64_t ls) {
+  if (int rc = inv_raw(kc, Dx, ls)) return rc;
+  LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 1, Dx, Dx, nullptr, 0, false), "seed unscale");
+  return RNT_OK;
+}
+
+// The relinearisation of a chunk of kc.B ciphertexts whose tensor stands ready
+// at limb stride kc.B N: d2 (coefficient domain) through the stages.  seeded:
+// D0 == ws.A0 and D1 == ws.A1 hold d0^ 2^-w, d1^ 2^-w and seed the products;
+// else D0, D1 go back to the coefficient domain and are ModDown's addends.
+int hybrid_relin_chunk(const HybridPlan& pl, const rnt::Launch& kc, const HybridWs& ws, bool rescale, bool seeded,
+                       char* D0, char* D1, const char* D2, const rnt_buf* key_a, const rnt_buf* key_b, void* out0,
+                       void* out1, uint64_t out_ls) {
+  const uint64_t cls = (uint64_t)kc.B * kc.t->n;
+  if (!seeded)
+    for (char* Dx : {D0, D1})
+      if (int rc = seeds_to_coeff(kc, Dx, cls)) return rc;
+  return hybrid_chunk_run(pl, kc.B, ws, D2, cls, key_a, key_b, out0, out1, out_ls, seeded ? nullptr : D0,
+                          seeded ? nullptr : D1, cls, rescale, seeded);
 }
 
 // Whether an NTT-domain plane of the ciphertext context's transforms is, on a
@@ -3154,70 +3230,6 @@ int hybrid_tensor(const rnt::Launch& kc, bool whole, bool mf, char* const* T, ch
 // is set exactly where mf_supported() holds.  What is left is `plane`, read
 // from the environment when a root context is created.
 bool hybrid_same_transforms(const HybridPlan& pl) { return pl.C->t->plane == pl.E->t->plane; }
-
-// The output rules of a call that ends in a rescale (rnt_ct_mul_relin_rescale's).
-int rescaled_outputs_check(const rnt_buf* out0, const rnt_buf* out1, const rnt_buf* c0) {
-  const size_t L = c0->ctx->L;
-  if (L < 2)  // poly.rs:191-197
-    return fail_fields(RNT_ERR_INVALID_MOD_DROP, 1, L, "invalid mod-drop count 1 for %zu channels", L);
-  for (const rnt_buf* o : {out0, out1}) {
-    if (o->ctx->t != c0->ctx->t || o->ctx->L != L - 1)
-      return fail(RNT_ERR_BASIS_MISMATCH, "rescale: output basis is not drop_last(1) of the input's");
-    if (o->n_polys != c0->n_polys) return fail(RNT_ERR_BAD_ARGUMENT, "rescale: batch sizes differ");
-  }
-  if (out0->ctx != out1->ctx)  // engine.rs:272-274: one shared new basis
-    return fail(RNT_ERR_BASIS_MISMATCH, "rescale_ciphertext: outputs must share one basis");
-  return RNT_OK;
-}
-
-// The fused tail of a chunk of c ciphertexts whose tensor (d0, d1, d2) stands
-// ready: ModUp of D2 (coefficient domain, limb stride c N) into HW (D | A0 |
-// A1), the forward transform of the digits, the key products, two inverses and
-// two k_moddown_rescale launches into out0 / out1 (limb stride out_ls, Lv - 1
-// limbs).  seeded: D0 == A0 and D1 == A1 hold d0^ 2^-w, d1^ 2^-w in the
-// accumulators' first Lv limbs (k_hoist_mac_seed); else D0, D1 are the
-// canonical coefficient-domain d0, d1, ModDown's addends.
-int hybrid_rescale_tail(const HybridPlan& pl, size_t c, char* HW, bool seeded, const char* D0, const char* D1,
-                        const char* D2, const rnt_buf* key_a, const rnt_buf* key_b, char* out0, char* out1,
-                        uint64_t out_ls) {
-  const rnt::Tables* tc = pl.C->t.get();
-  const size_t n = tc->n, wb = word_bytes(tc);
-  const void* rinv = rnt::resc_inv_row(tc, pl.Lv - 1, 0);
-  const void* rinvp = rnt::resc_inv_row(tc, pl.Lv - 1, 1);
-  const uint64_t cls = (uint64_t)c * n;
-  const rnt::Launch ke = hybrid_launch(pl, c);
-  char* D = HW;
-  char* A0 = D + pl.LE * pl.beta * c * n * wb;
-  char* A1 = A0 + pl.LE * c * n * wb;
-  LAUNCH_ON(tc, ke.s, rnt::K_MODUP, rnt::launch_modup(ke, D, D2, cls, pl.hc), "ModUp");
-  rnt::Launch kd = ke;
-  kd.B = pl.beta * c;
-  if (int rc = fwd_raw(kd, D, (uint64_t)kd.B * n, tc)) return rc;
-  rnt::Launch km = ke;
-  km.Ls = pl.beta;
-  if (seeded) {
-    LAUNCH_ON(tc, ke.s, rnt::K_HOIST_MAC,
-              rnt::launch_hoist_mac_seed(km, A0, A1, D, key_a->data, key_b->data, limb_stride(key_a), A1, A0, cls,
-                                         pl.hc),
-              "hybrid key products (seeded)");
-  } else {
-    void* a0[1] = {A0};
-    void* a1[1] = {A1};
-    const void* ka[1] = {key_a->data};
-    const void* kb[1] = {key_b->data};
-    LAUNCH_ON(tc, ke.s, rnt::K_HOIST_MAC, rnt::launch_hoist_mac(km, a0, a1, 1, D, ka, kb, limb_stride(key_a)),
-              "hybrid key products");
-  }
-  if (int rc = inv_raw(ke, A0, cls, tc)) return rc;
-  if (int rc = inv_raw(ke, A1, cls, tc)) return rc;
-  LAUNCH_ON(tc, ke.s, rnt::K_MODDOWN_RESCALE,
-            rnt::launch_moddown_rescale(ke, out0, out_ls, A0, cls, seeded ? nullptr : D0, cls, rinv, rinvp, pl.hc),
-            "ModDown and rescale");
-  LAUNCH_ON(tc, ke.s, rnt::K_MODDOWN_RESCALE,
-            rnt::launch_moddown_rescale(ke, out1, out_ls, A1, cls, seeded ? nullptr : D1, cls, rinv, rinvp, pl.hc),
-            "ModDown and rescale");
-  return RNT_OK;
-}
 
 // The shared body of rnt_ct_dot_relin_hybrid and its rescaling form.  Per
 // chunk of ciphertexts and group of up to kDotT terms: the group's planes are
@@ -3248,17 +3260,15 @@ int ct_dot_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt_buf* o
   for (const rnt_buf* b : in)
     if (b->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: inputs must be in coefficient domain", name);
   const size_t L = x0->ctx->L;
-  if (rescale && L < 2)  // poly.rs:191-197
-    return fail_fields(RNT_ERR_INVALID_MOD_DROP, 1, L, "invalid mod-drop count 1 for %zu channels", L);
-  for (const rnt_buf* o : {out0, out1}) {
-    if (rescale ? (o->ctx->t != x0->ctx->t || o->ctx->L != L - 1) : o->ctx != x0->ctx)
-      return fail(RNT_ERR_BASIS_MISMATCH, "%s: an output's basis is not %sthe inputs'", name,
-                  rescale ? "drop_last(1) of " : "");
-    if (o->n_polys != B)
-      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output of %zu polys for a batch of %zu", name, o->n_polys, B);
+  if (rescale) {
+    if (int rc = rescaled_outputs_check(name, out0, out1, x0, B)) return rc;
+  } else {
+    for (const rnt_buf* o : {out0, out1}) {
+      if (o->ctx != x0->ctx) return fail(RNT_ERR_BASIS_MISMATCH, "%s: an output's basis is not the inputs'", name);
+      if (o->n_polys != B)
+        return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output of %zu polys for a batch of %zu", name, o->n_polys, B);
+    }
   }
-  if (out0->ctx != out1->ctx)  // engine.rs:272-274: one shared new basis
-    return fail(RNT_ERR_BASIS_MISMATCH, "%s: outputs must share one basis", name);
   if (int rc = set_device(x0->ctx)) return rc;
   if (int rc = hybrid_prepare(&pl)) return rc;
   rnt::Launch k = launch_for(x0);
@@ -3285,10 +3295,9 @@ int ct_dot_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt_buf* o
     kc.B = c;
     const uint64_t cls = (uint64_t)c * n;
     const size_t po = p0 * n * wb;
-    char* A0 = HW + pl.LE * pl.beta * c * n * wb;
-    char* A1 = A0 + pl.LE * c * n * wb;
-    char* D0 = seeded ? A0 : D2 + chunk_words * wb;
-    char* D1 = seeded ? A1 : D0 + chunk_words * wb;
+    const HybridWs hw(pl, c, HW);
+    char* D0 = seeded ? hw.A0 : D2 + chunk_words * wb;
+    char* D1 = seeded ? hw.A1 : D0 + chunk_words * wb;
     for (size_t t0 = 0; t0 < n_terms; t0 += gmax) {
       const size_t g = std::min(gmax, n_terms - t0);
       rnt::Launch kg = k;
@@ -3308,21 +3317,10 @@ int ct_dot_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt_buf* o
       LAUNCH(kc.t, rnt::K_DOT_TENSOR,
              rnt::launch_dot_tensor(kc, D0, D1, D2, cls, X[0], X[1], X[2], X[3], gls, cls, g, t0 != 0), "dot tensor");
     }
-    // INV(d^ 2^-w) 2^w = d, canonical: d2 for ModUp; un-seeded, d0 and d1 for ModDown's addends
-    for (char* Dx : {D2, D0, D1}) {
-      if (seeded && Dx != D2) continue;
-      if (int rc = inv_raw(kc, Dx, cls)) return rc;
-      LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 1, Dx, Dx, nullptr, 0, false), "seed unscale");
-    }
-    if (rescale) {
-      if (int rc = hybrid_rescale_tail(pl, c, HW, seeded, D0, D1, D2, key_a, key_b, (char*)out0->data + po,
-                                       (char*)out1->data + po, out_ls))
-        return rc;
-    } else {
-      if (int rc = hybrid_chunk_run(pl, c, HW, D2, cls, key_a, key_b, (char*)out0->data + po, (char*)out1->data + po,
-                                    out_ls, D0, D1, cls))
-        return rc;
-    }
+    if (int rc = seeds_to_coeff(kc, D2, cls)) return rc;  // for ModUp
+    if (int rc = hybrid_relin_chunk(pl, kc, hw, rescale, seeded, D0, D1, D2, key_a, key_b, (char*)out0->data + po,
+                                    (char*)out1->data + po, out_ls))
+      return rc;
   }
   out0->in_ntt = out1->in_ntt = 0;
   return RNT_OK;
@@ -3367,7 +3365,7 @@ extern "C" int rnt_keyswitch_hybrid(rnt_buf* acc0, rnt_buf* acc1, const rnt_buf*
   for (size_t p0 = 0; p0 < B; p0 += bc) {
     const size_t c = std::min(bc, B - p0);
     const size_t off = p0 * n * wb;
-    if (int rc = hybrid_chunk_run(pl, c, (char*)ws.p, (const char*)d->data + off, ls, key_a, key_b,
+    if (int rc = hybrid_chunk_run(pl, c, HybridWs(pl, c, ws.p), (const char*)d->data + off, ls, key_a, key_b,
                                   (char*)acc0->data + off, (char*)acc1->data + off, ls, nullptr, nullptr, 0))
       return rc;
   }
@@ -3417,7 +3415,7 @@ extern "C" int rnt_ct_rotate_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf*
   for (size_t p0 = 0; p0 < B; p0 += bc) {
     const size_t c = std::min(bc, B - p0);
     const size_t off = p0 * n * wb;
-    if (int rc = hybrid_chunk_run(pl, c, HW, sig1 + off, ls, key_a, key_b, (char*)out0->data + off,
+    if (int rc = hybrid_chunk_run(pl, c, HybridWs(pl, c, HW), sig1 + off, ls, key_a, key_b, (char*)out0->data + off,
                                   (char*)out1->data + off, ls, sig0 + off, nullptr, ls))
       return rc;
   }
@@ -3425,97 +3423,41 @@ extern "C" int rnt_ct_rotate_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf*
   return RNT_OK;
 }
 
-extern "C" int rnt_ct_mul_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
-                                       const rnt_buf* c0p, const rnt_buf* c1p, const rnt_buf* key_a,
-                                       const rnt_buf* key_b, size_t alpha) {
-  const char* name = "rnt_ct_mul_relin_hybrid";
+// The shared body of rnt_ct_mul_relin_hybrid and its rescaling form, which is
+// that call followed by rnt_ct_rescale, word for word.  Per chunk: the tensor
+// of rnt_ct_mul_relin (d0^, d1^ in the NTT domain, scaled by 2^-w, and d2),
+// then d2 through the three stages.  The plain call takes d0, d1 back to the
+// coefficient domain as ModDown's addends.  The rescaling call has the tensor
+// write d0^ 2^-w, d1^ 2^-w into the first Lv limbs of the accumulators A0, A1
+// themselves and seeds the products with them: no seed inverse, no unscale
+// pass, no addend, no level-Lv product in memory.  Where the two contexts'
+// transforms may differ (hybrid_same_transforms) its seeds take the plain
+// call's way and only the ModDown is fused with the rescale.
+//
+// The two calls validate in their own orders: the plain one compares all six
+// operands with out0 before it looks at the key; the rescaling one compares
+// the inputs with c0, then checks the key and the domain, and its outputs last.
+static int ct_mul_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0,
+                              const rnt_buf* c1, const rnt_buf* c0p, const rnt_buf* c1p, const rnt_buf* key_a,
+                              const rnt_buf* key_b, size_t alpha) {
   const rnt_buf* all[6] = {out0, out1, c0, c1, c0p, c1p};
   for (const rnt_buf* b : all)
     if (int rc = check_buf(b, name)) return rc;
   if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
-  for (int i = 1; i < 6; ++i)
-    if (int rc = check_same(all[0], all[i], name)) return rc;
+  for (int i = rescale ? 3 : 1; i < 6; ++i)
+    if (int rc = check_same(rescale ? c0 : out0, all[i], name)) return rc;
   HybridPlan pl;
   if (int rc = hybrid_check(name, c0->ctx, key_a, key_b, alpha, &pl)) return rc;
   if (c0->in_ntt || c1->in_ntt || c0p->in_ntt || c1p->in_ntt)
     return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: inputs must be in coefficient domain", name);
+  if (rescale)
+    if (int rc = rescaled_outputs_check(name, out0, out1, c0, c0->n_polys)) return rc;
   if (int rc = set_device(c0->ctx)) return rc;
   if (int rc = hybrid_prepare(&pl)) return rc;
   rnt::Launch k = launch_for(c0);
   const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
-  // the tensor of rnt_ct_mul_relin per chunk: d0^, d1^ (NTT domain, scaled by
-  // 2^-w as its key-switch seeds are) and d2; here d0, d1 go back to the
-  // coefficient domain and are ModDown's addends
-  const bool whole = rnt::tensor_whole_ok(k.t);
-  const bool mf = !whole && use_mf(k);
-  const size_t nt = whole ? 0 : mf ? 1 : 4;
-  const size_t bc = hybrid_chunk(pl, B, (nt + 3) * L);
-  const size_t chunk_words = L * bc * n;
-  // ws: [T0..T3] | D0 | D1 | D2 | the chunk's D, A0, A1
-  CallWs cws(out0);
-  if (int rc = cws.get(std::max<size_t>(((nt + 3) * chunk_words + hybrid_planes(pl) * bc * n) * wb, 16))) return rc;
-  char* ws = (char*)cws.p;
-  char* T[4];
-  for (int i = 0; i < 4; ++i) T[i] = ws + i * chunk_words * wb;
-  char* D0 = ws + nt * chunk_words * wb;
-  char* D1 = D0 + chunk_words * wb;
-  char* D2 = D1 + chunk_words * wb;
-  char* HW = D2 + chunk_words * wb;
-  const uint64_t full_ls = limb_stride(c0);
-  for (size_t p0 = 0; p0 < B; p0 += bc) {
-    const size_t c = std::min(bc, B - p0);
-    rnt::Launch kc = k;
-    kc.B = c;
-    const uint64_t cls = (uint64_t)c * n;
-    const size_t po = p0 * n * wb;
-    auto off = [&](const rnt_buf* b) { return (const char*)b->data + po; };
-    if (int rc = hybrid_tensor(kc, whole, mf, T, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls))
-      return rc;
-    for (char* Dx : {D0, D1}) {  // INV(d^ 2^-w) 2^w = d, canonical
-      if (int rc = inv_raw(kc, Dx, cls)) return rc;
-      LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 1, Dx, Dx, nullptr, 0, false), "seed unscale");
-    }
-    if (int rc = hybrid_chunk_run(pl, c, HW, D2, cls, key_a, key_b, (char*)out0->data + po, (char*)out1->data + po,
-                                  full_ls, D0, D1, cls))
-      return rc;
-  }
-  out0->in_ntt = out1->in_ntt = 0;
-  return RNT_OK;
-}
-
-// rnt_ct_mul_relin_hybrid followed by rnt_ct_rescale, word for word.  Per
-// chunk: the tensor writes d0^ 2^-w, d1^ 2^-w into the first Lv limbs of the
-// accumulators A0, A1 themselves; k_modup and the forward transform of d2's
-// digits; k_hoist_mac_seed, whose sums start from those seeds times P 2^w (so
-// A = sum + P d in the NTT domain, ModDown(A) = ModDown(sum) + d); two inverses
-// over the key basis; two k_moddown_rescale launches into the outputs.  No
-// seed inverse, no unscale pass, no addend, no level-Lv product in memory.
-// Where the two contexts' transforms may differ (hybrid_same_transforms) the
-// seeds take rnt_ct_mul_relin_hybrid's way -- inverse, unscale, ModDown's
-// addends -- and only the tail is fused.
-extern "C" int rnt_ct_mul_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
-                                               const rnt_buf* c0p, const rnt_buf* c1p, const rnt_buf* key_a,
-                                               const rnt_buf* key_b, size_t alpha) {
-  const char* name = "rnt_ct_mul_relin_rescale_hybrid";
-  const rnt_buf* all[6] = {out0, out1, c0, c1, c0p, c1p};
-  for (const rnt_buf* b : all)
-    if (int rc = check_buf(b, name)) return rc;
-  if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
-  for (int i = 3; i < 6; ++i)
-    if (int rc = check_same(c0, all[i], name)) return rc;
-  HybridPlan pl;
-  if (int rc = hybrid_check(name, c0->ctx, key_a, key_b, alpha, &pl)) return rc;
-  if (c0->in_ntt || c1->in_ntt || c0p->in_ntt || c1p->in_ntt)
-    return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: inputs must be in coefficient domain", name);
-  if (int rc = rescaled_outputs_check(out0, out1, c0)) return rc;
-  if (int rc = set_device(c0->ctx)) return rc;
-  if (int rc = hybrid_prepare(&pl)) return rc;
-  rnt::Launch k = launch_for(c0);
-  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
-  const bool seeded = hybrid_same_transforms(pl);
-  const bool whole = rnt::tensor_whole_ok(k.t);
-  const bool mf = !whole && use_mf(k);
-  const size_t nt = whole ? 0 : mf ? 1 : 4;
+  const bool seeded = rescale && hybrid_same_transforms(pl);
+  const size_t nt = tensor_blocks(k);
   const size_t nd = seeded ? 1 : 3;  // d2 (and, un-seeded, d0 and d1) over the ciphertext limbs
   const size_t bc = hybrid_chunk(pl, B, (nt + nd) * L);
   const size_t chunk_words = L * bc * n;
@@ -3535,23 +3477,29 @@ extern "C" int rnt_ct_mul_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, con
     const uint64_t cls = (uint64_t)c * n;
     const size_t po = p0 * n * wb;
     auto off = [&](const rnt_buf* b) { return (const char*)b->data + po; };
-    char* A0 = HW + pl.LE * pl.beta * c * n * wb;
-    char* A1 = A0 + pl.LE * c * n * wb;
-    char* D0 = seeded ? A0 : D2 + chunk_words * wb;
-    char* D1 = seeded ? A1 : D0 + chunk_words * wb;
-    if (int rc = hybrid_tensor(kc, whole, mf, T, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls))
-      return rc;
-    if (!seeded)
-      for (char* Dx : {D0, D1}) {  // INV(d^ 2^-w) 2^w = d, canonical
-        if (int rc = inv_raw(kc, Dx, cls)) return rc;
-        LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 1, Dx, Dx, nullptr, 0, false), "seed unscale");
-      }
-    if (int rc = hybrid_rescale_tail(pl, c, HW, seeded, D0, D1, D2, key_a, key_b, (char*)out0->data + po,
-                                     (char*)out1->data + po, out_ls))
+    const HybridWs hw(pl, c, HW);
+    char* D0 = seeded ? hw.A0 : D2 + chunk_words * wb;
+    char* D1 = seeded ? hw.A1 : D0 + chunk_words * wb;
+    if (int rc = tensor(kc, T, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls)) return rc;
+    if (int rc = hybrid_relin_chunk(pl, kc, hw, rescale, seeded, D0, D1, D2, key_a, key_b, (char*)out0->data + po,
+                                    (char*)out1->data + po, out_ls))
       return rc;
   }
   out0->in_ntt = out1->in_ntt = 0;
   return RNT_OK;
+}
+
+extern "C" int rnt_ct_mul_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                       const rnt_buf* c0p, const rnt_buf* c1p, const rnt_buf* key_a,
+                                       const rnt_buf* key_b, size_t alpha) {
+  return ct_mul_hybrid_body("rnt_ct_mul_relin_hybrid", false, out0, out1, c0, c1, c0p, c1p, key_a, key_b, alpha);
+}
+
+extern "C" int rnt_ct_mul_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                               const rnt_buf* c0p, const rnt_buf* c1p, const rnt_buf* key_a,
+                                               const rnt_buf* key_b, size_t alpha) {
+  return ct_mul_hybrid_body("rnt_ct_mul_relin_rescale_hybrid", true, out0, out1, c0, c1, c0p, c1p, key_a, key_b,
+                            alpha);
 }
 
 // ---------------------------------------------------------------------------
@@ -3998,13 +3946,14 @@ namespace {
 
 // The argument rules of one stage's hybrid key set (n steps, n beta polys over
 // E): hybrid_check's on a one-key view, then the key-count rule of
-// rnt_ct_rotate_hoisted.  *have: the stage has keys (else nothing is checked:
-// every step is 0 and both buffers are NULL).
+// rnt_ct_rotate_hoisted.  *nz: the steps that rotate.  *have: the stage has
+// keys (else nothing is checked: every step is 0 and both buffers are NULL).
 int hybrid_set_check(const char* name, const rnt_ctx* C, const int32_t* steps, size_t n_steps,
-                     const rnt_buf* keys_a, const rnt_buf* keys_b, size_t alpha, HybridPlan* pl, bool* have) {
-  size_t nz = 0;
-  for (size_t t = 0; t < n_steps; ++t) nz += steps[t] != 0;
-  *have = nz || keys_a || keys_b;
+                     const rnt_buf* keys_a, const rnt_buf* keys_b, size_t alpha, HybridPlan* pl, size_t* nz,
+                     bool* have) {
+  *nz = 0;
+  for (size_t t = 0; t < n_steps; ++t) *nz += steps[t] != 0;
+  *have = *nz || keys_a || keys_b;
   if (!*have) return RNT_OK;
   if (int rc = check_key_buf(keys_a, name)) return rc;
   if (int rc = check_key_buf(keys_b, name)) return rc;
@@ -4045,6 +3994,43 @@ bool tail_fused(const rnt::Tables* tc, size_t Lv, size_t bc) {
   return Lv * bc * tc->n * word_bytes(tc) < kMdAutoBytes;
 }
 
+// The chunk of a hoisted call on B ciphertexts within the key-switch workspace
+// cap.  Per ciphertext: D (LE beta planes), the accumulator pairs of one
+// k_hoist_mac group of tg steps (2 tg LE), the caller's c_planes over C and,
+// where the tail is not k_moddown_auto, its two staging blocks (tmp_planes =
+// 2 Lv).  Two passes: the tail is chosen for the chunk that fits without the
+// staging, and an un-fused tail then shrinks the chunk to make room for it.
+struct HoistSize {
+  size_t bc;
+  bool fused;
+  size_t tmp_planes;
+};
+HoistSize hoist_size(const HybridPlan& pl, size_t B, size_t tg, size_t c_planes) {
+  const size_t acc_planes = 2 * (tg - 1) * pl.LE;  // (hybrid_planes() holds one pair)
+  HoistSize h{hybrid_chunk(pl, B, acc_planes + c_planes), true, 0};
+  h.fused = tail_fused(pl.C->t.get(), pl.Lv, h.bc);
+  if (!h.fused) {
+    h.tmp_planes = 2 * pl.Lv;
+    h.bc = hybrid_chunk(pl, B, acc_planes + c_planes + h.tmp_planes);
+  }
+  return h;
+}
+
+// The key-basis part of a hoisted call's workspace for chunks of bc
+// ciphertexts: D (beta blocks) | ACC (tg accumulator pairs), a block being pe
+// bytes ([LE][bc][N]).  Sized first, placed once the workspace is there.
+struct HoistWs {
+  size_t pe = 0, bytes = 0;
+  char *D = nullptr, *ACC = nullptr;
+  HoistWs() = default;
+  HoistWs(const HybridPlan& pl, size_t bc, size_t tg)
+      : pe(pl.LE * bc * pl.C->t->n * word_bytes(pl.C->t.get())), bytes((pl.beta + 2 * tg) * pe) {}
+  void place(const HybridPlan& pl, void* ws) {
+    D = (char*)ws;
+    ACC = D + pl.beta * pe;
+  }
+};
+
 // The per-step tail: dst = sigma_g(ModDown(A) (+ add)) at limb stride dst_ls,
 // A the coefficient-domain accumulator of c polys over E.  fused: one
 // k_moddown_auto; else k_moddown into TMP, the automorphism launch into TMP +
@@ -4078,23 +4064,18 @@ int hybrid_tail(const HybridPlan& pl, size_t c, char* dst, uint64_t dst_ls, cons
 // then one k_hoist_mac launch per group of kHoistT nonzero steps into ACC
 // (2 kHoistT blocks of [LE][c][N]), both accumulators taken back to the
 // coefficient domain, and finish(t, A0, A1) for every step t of the group:
-// A0 = sum_d D_d sigma_t^-1(key_b[t][d]) over E.
+// A0 = sum_d D_d sigma_t^-1(key_b[t][d]) over E.  The caller has seen a step
+// that rotates.
 template <class Finish>
-int hybrid_hoist_chunk(const HybridPlan& pl, size_t c, char* D, char* ACC, const void* x1, uint64_t x1_ls,
+int hybrid_hoist_chunk(const HybridPlan& pl, size_t c, const HoistWs& ws, const void* x1, uint64_t x1_ls,
                        const int32_t* steps, size_t n_steps, const rnt_buf* keys_a, const rnt_buf* keys_b,
                        Finish&& finish) {
   const rnt::Tables* tc = pl.C->t.get();
   const size_t n = tc->n, wb = word_bytes(tc);
   const rnt::Launch k = hybrid_launch(pl, c);
-  const size_t pe = pl.LE * c * n * wb;
+  const size_t pe = pl.LE * c * n * wb;  // (the chunk's own pitch: a last chunk packs its pairs closer)
   const uint64_t cls = (uint64_t)c * n;
-  bool any_rot = false;
-  for (size_t t = 0; t < n_steps; ++t) any_rot = any_rot || steps[t] != 0;
-  if (!any_rot) return RNT_OK;
-  LAUNCH_ON(tc, k.s, rnt::K_MODUP, rnt::launch_modup(k, D, x1, x1_ls, pl.hc), "ModUp");
-  rnt::Launch kd = k;
-  kd.B = pl.beta * c;
-  if (int rc = fwd_raw(kd, D, (uint64_t)kd.B * n, tc)) return rc;
+  if (int rc = hybrid_raise(pl, c, ws.D, x1, x1_ls)) return rc;
   rnt::Launch km = k;
   km.Ls = pl.beta;
   for (size_t t = 0; t < n_steps;) {
@@ -4107,14 +4088,14 @@ int hybrid_hoist_chunk(const HybridPlan& pl, size_t c, char* D, char* ACC, const
     for (; t < n_steps && nt < rnt::kHoistT; ++t) {
       if (steps[t] == 0) continue;
       idx[nt] = t;
-      a0[nt] = ACC + 2 * nt * pe;
-      a1[nt] = ACC + (2 * nt + 1) * pe;
+      a0[nt] = ws.ACC + 2 * nt * pe;
+      a1[nt] = ws.ACC + (2 * nt + 1) * pe;
       ka[nt] = (const char*)keys_a->data + t * key_step_polys(keys_a, pl) * n * wb;
       kb[nt] = (const char*)keys_b->data + t * key_step_polys(keys_b, pl) * n * wb;
       ++nt;
     }
     if (nt == 0) break;
-    LAUNCH_ON(tc, k.s, rnt::K_HOIST_MAC, rnt::launch_hoist_mac(km, a0, a1, nt, D, ka, kb, limb_stride(keys_a)),
+    LAUNCH_ON(tc, k.s, rnt::K_HOIST_MAC, rnt::launch_hoist_mac(km, a0, a1, nt, ws.D, ka, kb, limb_stride(keys_a)),
               "hoisted hybrid key products");
     for (uint32_t u = 0; u < nt; ++u) {
       if (int rc = inv_raw(k, a0[u], cls, tc)) return rc;
@@ -4145,16 +4126,15 @@ extern "C" int rnt_ct_rotate_hybrid_hoisted(rnt_buf* out0, rnt_buf* out1, const 
     return fail(RNT_ERR_BAD_ARGUMENT, "%s: outputs of %zu and %zu polys for %zu steps of %zu", name, out0->n_polys,
                 out1->n_polys, n_steps, B);
   HybridPlan pl;
+  size_t nz = 0;
   bool have = false;
-  if (int rc = hybrid_set_check(name, c0->ctx, steps, n_steps, keys_a, keys_b, alpha, &pl, &have)) return rc;
+  if (int rc = hybrid_set_check(name, c0->ctx, steps, n_steps, keys_a, keys_b, alpha, &pl, &nz, &have)) return rc;
   if (c0->in_ntt || c1->in_ntt)
     return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the ciphertext must be in coefficient domain", name);
   if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
   for (const rnt_buf* in : {c0, c1, keys_a, keys_b})
     if (in && (out0 == in || out1 == in || out0->data == in->data || out1->data == in->data))
       return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output aliases an input", name);
-  size_t nz = 0;
-  for (size_t t = 0; t < n_steps; ++t) nz += steps[t] != 0;
   if (int rc = set_device(c0->ctx)) return rc;
   if (nz)
     if (int rc = hybrid_prepare(&pl)) return rc;
@@ -4163,21 +4143,18 @@ extern "C" int rnt_ct_rotate_hybrid_hoisted(rnt_buf* out0, rnt_buf* out1, const 
   const uint64_t full_ls = limb_stride(c0), out_ls = limb_stride(out0), two_n = 2 * (uint64_t)n;
   const rnt_buf* src[2] = {c0, c1};
   rnt_buf* out[2] = {out0, out1};
-  // per ciphertext of a chunk: D (LE beta planes), the accumulator pairs of one
-  // k_hoist_mac group (2 tg LE) and, without k_moddown_auto, the tail's two
-  // staging blocks (2 Lv), within the key-switch workspace cap
-  const size_t tg = std::min<size_t>(nz, rnt::kHoistT);
-  size_t bc = nz ? hybrid_chunk(pl, B, 2 * (tg - 1) * pl.LE) : B;
-  const bool fused = tail_fused(k.t, Lv, bc);
-  const size_t tmp_planes = fused ? 0 : 2 * Lv;
-  if (nz && !fused) bc = hybrid_chunk(pl, B, 2 * (tg - 1) * pl.LE + tmp_planes);
-  const size_t pe = pl.LE * bc * n * wb;
+  // ws: D | ACC | TMP, and only where a step rotates
+  HoistSize hs{B, true, 0};
+  HoistWs hw;
   CallWs ws(out0);
-  if (nz)
-    if (int rc = ws.get(pl.beta * pe + 2 * tg * pe + tmp_planes * bc * n * wb)) return rc;
-  char* D = (char*)ws.p;
-  char* ACC = D + pl.beta * pe;
-  char* TMP = ACC + 2 * tg * pe;
+  if (nz) {
+    const size_t tg = std::min<size_t>(nz, rnt::kHoistT);
+    hs = hoist_size(pl, B, tg, 0);
+    hw = HoistWs(pl, hs.bc, tg);
+    if (int rc = ws.get(hw.bytes + hs.tmp_planes * hs.bc * n * wb)) return rc;
+    hw.place(pl, ws.p);
+  }
+  char* TMP = hw.D + hw.bytes;
   for (size_t t = 0; t < n_steps; ++t) {
     if (steps[t] != 0) continue;
     for (int o = 0; o < 2; ++o)
@@ -4186,16 +4163,16 @@ extern "C" int rnt_ct_rotate_hybrid_hoisted(rnt_buf* out0, rnt_buf* out1, const 
                                    full_ls * wb, full_ls * wb, Lv),
              "step-0 copy");
   }
-  for (size_t p0 = 0; nz && p0 < B; p0 += bc) {
-    const size_t c = std::min(bc, B - p0);
+  for (size_t p0 = 0; nz && p0 < B; p0 += hs.bc) {
+    const size_t c = std::min(hs.bc, B - p0);
     const char* x0 = (const char*)c0->data + p0 * n * wb;
     auto finish = [&](size_t t, char* A0, char* A1) -> int {
       const uint64_t g = rotation_exponent(steps[t], two_n);
       const size_t off = (t * B + p0) * n * wb;
-      if (int rc = hybrid_tail(pl, c, (char*)out0->data + off, out_ls, A0, x0, full_ls, g, TMP, fused)) return rc;
-      return hybrid_tail(pl, c, (char*)out1->data + off, out_ls, A1, nullptr, 0, g, TMP, fused);
+      if (int rc = hybrid_tail(pl, c, (char*)out0->data + off, out_ls, A0, x0, full_ls, g, TMP, hs.fused)) return rc;
+      return hybrid_tail(pl, c, (char*)out1->data + off, out_ls, A1, nullptr, 0, g, TMP, hs.fused);
     };
-    if (int rc = hybrid_hoist_chunk(pl, c, D, ACC, (const char*)c1->data + p0 * n * wb, full_ls, steps, n_steps,
+    if (int rc = hybrid_hoist_chunk(pl, c, hw, (const char*)c1->data + p0 * n * wb, full_ls, steps, n_steps,
                                     keys_a, keys_b, finish))
       return rc;
   }
@@ -4230,10 +4207,13 @@ static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* o
   if (n_baby > SIZE_MAX / n_giant || diag->n_polys != n_baby * n_giant)
     return fail(RNT_ERR_BAD_ARGUMENT, "%s: %zu plaintexts for %zu x %zu steps", name, diag->n_polys, n_giant, n_baby);
   HybridPlan plb, plg;
+  size_t nzb = 0, nzg = 0;
   bool have_b = false, have_g = false;
-  if (int rc = hybrid_set_check(name, c0->ctx, baby_steps, n_baby, baby_keys_a, baby_keys_b, alpha, &plb, &have_b))
+  if (int rc = hybrid_set_check(name, c0->ctx, baby_steps, n_baby, baby_keys_a, baby_keys_b, alpha, &plb, &nzb,
+                                &have_b))
     return rc;
-  if (int rc = hybrid_set_check(name, c0->ctx, giant_steps, n_giant, giant_keys_a, giant_keys_b, alpha, &plg, &have_g))
+  if (int rc = hybrid_set_check(name, c0->ctx, giant_steps, n_giant, giant_keys_a, giant_keys_b, alpha, &plg, &nzg,
+                                &have_g))
     return rc;
   if (have_b && have_g && plb.E != plg.E)
     return fail(RNT_ERR_BASIS_MISMATCH, "%s: the baby and giant keys belong to different key bases", name);
@@ -4241,7 +4221,7 @@ static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* o
   if (c0->in_ntt || c1->in_ntt)
     return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the ciphertext must be in coefficient domain", name);
   if (rescale)
-    if (int rc = rescaled_outputs_check(out0, out1, c0)) return rc;
+    if (int rc = rescaled_outputs_check(name, out0, out1, c0, c0->n_polys)) return rc;
   const rnt_buf* ins[7] = {c0, c1, diag, baby_keys_a, baby_keys_b, giant_keys_a, giant_keys_b};
   if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
   for (int i = 0; i < 7; ++i) {
@@ -4254,9 +4234,7 @@ static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* o
   } catch (...) {
     return fail(RNT_ERR_OUT_OF_MEMORY, "host allocation failed");
   }
-  size_t nzb = 0;
-  for (size_t i = 0; i < n_baby; ++i) nzb += baby_steps[i] != 0;
-  const bool hyb = nzb != 0 || plan.any_rot;
+  const bool hyb = nzb != 0 || nzg != 0;
   HybridPlan pl = have_b ? plb : plg;
   if (int rc = set_device(c0->ctx)) return rc;
   if (hyb)
@@ -4271,26 +4249,21 @@ static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* o
   // accumulator pairs -- the baby stage's k_hoist_mac group, then the giant
   // stage's one A0 / A1 in the same place
   const size_t tg = std::max<size_t>(std::min<size_t>(nzb, rnt::kHoistT), 1);
-  size_t c_planes = (2 * n_baby + 2 * plan.nv + 3) * Lv;
-  size_t bc = B;
-  bool fused = true;
-  size_t tmp_planes = 0;
+  const size_t c_planes = (2 * n_baby + 2 * plan.nv + 3) * Lv;
+  HoistSize hs{B, true, 0};
+  HoistWs hw;
   if (hyb) {
-    bc = hybrid_chunk(pl, B, 2 * (tg - 1) * pl.LE + c_planes);
-    fused = tail_fused(k.t, Lv, bc);
-    if (!fused) {
-      tmp_planes = 2 * Lv;
-      c_planes += tmp_planes;
-      bc = hybrid_chunk(pl, B, 2 * (tg - 1) * pl.LE + c_planes);
-    }
+    hs = hoist_size(pl, B, tg, c_planes);
+    hw = HoistWs(pl, hs.bc, tg);
   } else {
-    bc = std::min(B, std::max<size_t>(k.t->ks_ws_bytes / (c_planes * n * wb), 1));
+    hs.bc = std::min(B, std::max<size_t>(k.t->ks_ws_bytes / (c_planes * n * wb), 1));
   }
+  const size_t bc = hs.bc;
+  const bool fused = hs.fused;
   const size_t pw = Lv * bc * n * wb;
-  const size_t pe = hyb ? pl.LE * bc * n * wb : 0;
   const size_t dm_bytes = Lv * n_terms * n * wb;
   CallWs ws(out0);
-  if (int rc = ws.get(dm_bytes + c_planes * bc * n * wb + (hyb ? pl.beta * pe + 2 * tg * pe : 0))) return rc;
+  if (int rc = ws.get(dm_bytes + (c_planes + hs.tmp_planes) * bc * n * wb + hw.bytes)) return rc;
   // the plaintexts in Montgomery form (m^ 2^w mod q), once per call: the inner
   // sums' Montgomery products are then the canonical products
   char* dm = (char*)ws.p;
@@ -4304,8 +4277,7 @@ static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* o
   char* SIG0 = SIG1 + pw;
   char* S0X = SIG0 + pw;
   char* TMP = S0X + pw;
-  char* D = TMP + tmp_planes * bc * n * wb;
-  char* ACC = D + (hyb ? pl.beta * pe : 0);
+  hw.place(pl, TMP + hs.tmp_planes * bc * n * wb);
   rnt_buf* out[2] = {out0, out1};
   for (size_t p0 = 0; p0 < B; p0 += bc) {
     const size_t c = std::min(bc, B - p0);
@@ -4331,7 +4303,7 @@ static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* o
         if (int rc = fwd_raw(kc, R0, cls)) return rc;
         return fwd_raw(kc, R0 + pw, cls);
       };
-      if (int rc = hybrid_hoist_chunk(pl, c, D, ACC, x[1], full_ls, baby_steps, n_baby, baby_keys_a, baby_keys_b,
+      if (int rc = hybrid_hoist_chunk(pl, c, hw, x[1], full_ls, baby_steps, n_baby, baby_keys_a, baby_keys_b,
                                       finish))
         return rc;
     }
@@ -4342,8 +4314,8 @@ static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* o
     // giant stage: sigma(V1_j) -> ModUp -> forward -> products summed into ONE
     // A0, A1 over E; sigma(V0_j) summed over C into S0, ModDown's addend
     char* S0 = plan.any_zero ? VB + 2 * plan.zslot * pw : S0X;
-    char* A0 = ACC;
-    char* A1 = ACC + pe;
+    char* A0 = hw.ACC;
+    char* A1 = hw.ACC + hw.pe;
     bool first = true;
     for (size_t j = 0; j < n_giant; ++j) {
       if (giant_steps[j] == 0) continue;
@@ -4356,25 +4328,12 @@ static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* o
         LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG0, V0, g), "automorphism");
         LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_elementwise(kc, 0, S0, S0, SIG0), "add_assign");
       }
-      const rnt::Launch ke = hybrid_launch(pl, c);
-      LAUNCH_ON(kc.t, ke.s, rnt::K_MODUP, rnt::launch_modup(ke, D, SIG1, cls, pl.hc), "ModUp");
-      rnt::Launch kd = ke;
-      kd.B = pl.beta * c;
-      if (int rc = fwd_raw(kd, D, (uint64_t)kd.B * n, kc.t)) return rc;
-      rnt::Launch km = ke;
-      km.Ls = pl.beta;
-      void* a0[1] = {A0};
-      void* a1[1] = {A1};
-      const void* ka[1] = {(const char*)giant_keys_a->data + j * key_step_polys(giant_keys_a, pl) * n * wb};
-      const void* kb[1] = {(const char*)giant_keys_b->data + j * key_step_polys(giant_keys_b, pl) * n * wb};
-      if (first) {
-        LAUNCH_ON(kc.t, ke.s, rnt::K_HOIST_MAC,
-                  rnt::launch_hoist_mac(km, a0, a1, 1, D, ka, kb, limb_stride(giant_keys_a)), "giant key products");
-      } else {
-        LAUNCH_ON(kc.t, ke.s, rnt::K_HOIST_MAC,
-                  rnt::launch_hoist_mac_acc(km, a0, a1, 1, D, ka, kb, limb_stride(giant_keys_a)),
-                  "giant key products (accumulating)");
-      }
+      if (int rc = hybrid_raise(pl, c, hw.D, SIG1, cls)) return rc;
+      if (int rc = hybrid_products(pl, c, hw.D, A0, A1,
+                                   (const char*)giant_keys_a->data + j * key_step_polys(giant_keys_a, pl) * n * wb,
+                                   (const char*)giant_keys_b->data + j * key_step_polys(giant_keys_b, pl) * n * wb,
+                                   limb_stride(giant_keys_a), first ? HybridMac::set : HybridMac::accumulate))
+        return rc;
       first = false;
     }
     char* dst[2] = {(char*)out[0]->data + p0 * n * wb, (char*)out[1]->data + p0 * n * wb};
@@ -4388,25 +4347,9 @@ static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* o
         }
       }
     } else {
-      const rnt::Launch ke = hybrid_launch(pl, c);
-      if (int rc = inv_raw(ke, A0, cls, kc.t)) return rc;
-      if (int rc = inv_raw(ke, A1, cls, kc.t)) return rc;
+      // (both outputs have the batch's polys, on the ciphertext's limbs or on one fewer: one limb stride)
       const char* Z1 = plan.any_zero ? VB + (2 * plan.zslot + 1) * pw : nullptr;
-      if (rescale) {
-        const void* rinv = rnt::resc_inv_row(kc.t, Lv - 1, 0);
-        const void* rinvp = rnt::resc_inv_row(kc.t, Lv - 1, 1);
-        LAUNCH_ON(kc.t, ke.s, rnt::K_MODDOWN_RESCALE,
-                  rnt::launch_moddown_rescale(ke, dst[0], limb_stride(out[0]), A0, cls, S0, cls, rinv, rinvp, pl.hc),
-                  "ModDown and rescale");
-        LAUNCH_ON(kc.t, ke.s, rnt::K_MODDOWN_RESCALE,
-                  rnt::launch_moddown_rescale(ke, dst[1], limb_stride(out[1]), A1, cls, Z1, cls, rinv, rinvp, pl.hc),
-                  "ModDown and rescale");
-      } else {
-        LAUNCH_ON(kc.t, ke.s, rnt::K_MODDOWN, rnt::launch_moddown(ke, dst[0], full_ls, A0, cls, S0, cls, pl.hc),
-                  "ModDown");
-        LAUNCH_ON(kc.t, ke.s, rnt::K_MODDOWN, rnt::launch_moddown(ke, dst[1], full_ls, A1, cls, Z1, cls, pl.hc),
-                  "ModDown");
-      }
+      if (int rc = hybrid_lower(pl, c, A0, A1, dst[0], dst[1], limb_stride(out0), S0, Z1, cls, rescale)) return rc;
     }
   }
   out0->in_ntt = out1->in_ntt = 0;
