@@ -225,12 +225,21 @@ int rnt_copy(rnt_buf* dst, const rnt_buf* src); /* Clone */
  * value centred in (-Q/2, Q/2] (reconstruct_centered_coeff, basis.rs:158-180)
  * as int64_t[n_polys][N] -- the value's low 64 bits in two's complement,
  * exactly the reference's result wherever it is defined (Q < 2^128).  An
- * NTT-domain buffer is converted on a temporary copy. */
+ * NTT-domain buffer is converted on a temporary copy; the buffer itself is
+ * left as it is.
+ * Limits (also of rnt_crt_centered and rnt_decode): Q, the product of the
+ * context's moduli, has at most 128 32-bit words (4096 bits); a longer Q, a
+ * null `host` or an `n_polys` other than the buffer's ->
+ * RNT_ERR_BAD_ARGUMENT.  The context of a longer basis is still created and
+ * serves every other call. */
 int rnt_to_coeffs(const rnt_buf* buf, int64_t* host, size_t n_polys);
-/* The same centred CRT value without truncation: `words` 64-bit
- * little-endian two's-complement words per coefficient,
+/* The same centred CRT value, in (-Q/2, Q/2], without truncation: `words`
+ * 64-bit little-endian two's-complement words per coefficient,
  * uint64_t[n_polys][N][words] (the reference's u128 path
- * cannot represent Q >= 2^128).  1 <= words <= 64. */
+ * cannot represent Q >= 2^128).  1 <= words <= 64, anything else ->
+ * RNT_ERR_BAD_ARGUMENT; words past the value's own are its sign extension,
+ * fewer words than it needs keep its low ones.  64 words hold any value of
+ * the longest Q served (128 32-bit words), sign included. */
 int rnt_crt_centered(const rnt_buf* buf, uint64_t* host, size_t n_polys, size_t words);
 /* Device-memory interop for multi-GPU pipelines (collectives run by the
  * caller, e.g. RCCL through torch.distributed):

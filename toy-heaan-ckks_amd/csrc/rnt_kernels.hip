@@ -4002,12 +4002,9 @@ k_crt(uint64_t* __restrict__ out, const W* __restrict__ in, CrtConsts cc, TabPtr
         acc[w + half] = (uint32_t)t;
         carry = t >> 32;
       }
-#pragma unroll
-      for (int w = MW - half; w <= MW; ++w) {  // propagate into the top word(s)
-        const uint64_t t = (uint64_t)acc[w] + carry;
-        acc[w] = (uint32_t)t;
-        carry = t >> 32;
-      }
+      // both halves stop at acc[MW - 1] (the high half has one product
+      // fewer), so the carry out belongs in the top word either way
+      acc[MW] += (uint32_t)carry;
     }
   }
   // subtract k*Q, k = floor(f) < L; then correct by at most one Q either way
