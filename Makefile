@@ -19,16 +19,18 @@ DEP_rnt_plane   := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp $(CSRC)/rnt
 DEP_rnt_mfma    := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_hostmath.hpp $(CSRC)/rnt_modarith.hpp $(CSRC)/rnt_device.hpp
 DEP_rnt_encode  := $(CSRC)/rnt_internal.hpp
 DEP_rnt_sample  := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp
+DEP_rnt_raise   := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp $(CSRC)/rnt_device.hpp
 DEP_rnt_api     := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_hostmath.hpp include/rnsntt.h
 
 OBJS := $(LIBDIR)/rnt_kernels.o $(LIBDIR)/rnt_plane.o $(LIBDIR)/rnt_mfma.o $(LIBDIR)/rnt_encode.o \
-        $(LIBDIR)/rnt_sample.o $(LIBDIR)/rnt_api.o
+        $(LIBDIR)/rnt_sample.o $(LIBDIR)/rnt_raise.o $(LIBDIR)/rnt_api.o
 
 $(LIBDIR)/rnt_kernels.o: $(CSRC)/rnt_kernels.hip $(DEP_rnt_kernels)
 $(LIBDIR)/rnt_plane.o: $(CSRC)/rnt_plane.hip $(DEP_rnt_plane)
 $(LIBDIR)/rnt_mfma.o: $(CSRC)/rnt_mfma.hip $(DEP_rnt_mfma)
 $(LIBDIR)/rnt_encode.o: $(CSRC)/rnt_encode.hip $(DEP_rnt_encode)
 $(LIBDIR)/rnt_sample.o: $(CSRC)/rnt_sample.hip $(DEP_rnt_sample)
+$(LIBDIR)/rnt_raise.o: $(CSRC)/rnt_raise.hip $(DEP_rnt_raise)
 $(LIBDIR)/rnt_api.o: $(CSRC)/rnt_api.cpp $(DEP_rnt_api)
 
 $(OBJS):

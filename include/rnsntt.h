@@ -285,6 +285,35 @@ int rnt_automorphism(rnt_buf* out, const rnt_buf* in, uint64_t g);
 /* rotate_slots (poly.rs:546-569): g = 5^k mod 2N (k >= 0); for k < 0 the
  * reference's automorphism(5^|k|) then automorphism(2N-1). */
 int rnt_rotate_slots(rnt_buf* out, const rnt_buf* in, int32_t k);
+/* ModRaise (no reference counterpart): `in` holds B coefficient-domain polys
+ * on a context C0 over q_0..q_{l0-1}, 1 <= l0 <= 4; `out` holds B polys on a
+ * context C over q_0..q_{L-1}, L > l0, whose first l0 moduli equal C0's BY
+ * VALUE -- C0 may be a drop_last view of C, a view of another root or an
+ * unrelated root of the same degree, device and device word width.  With x
+ * the CRT value of a coefficient's l0 residues centred in (-Q0/2, Q0/2], Q0 =
+ * q_0...q_{l0-1} (rnt_crt_centered's convention), limb j of `out` is x mod
+ * q_j, canonical; limbs j < l0 are therefore `in`'s words.  `out` is in the
+ * coefficient domain.  One launch, l0 planes read and L written, on C's
+ * stream (ordered after the work queued on C0's where that is another one).
+ * Errors: a null argument, l0 >= L or batch sizes that differ ->
+ * RNT_ERR_BAD_ARGUMENT; degree, device or moduli-prefix mismatch ->
+ * RNT_ERR_BASIS_MISMATCH; different device word widths, or l0 > 4 ->
+ * RNT_ERR_UNSUPPORTED (fields 0, 0); an NTT-domain `in` ->
+ * RNT_ERR_DOMAIN_MISMATCH; a key level view in any position ->
+ * RNT_ERR_UNSUPPORTED.  A refused call leaves `out` untouched.  The constants
+ * of (C's root, l0) are built by the first call that needs them, which
+ * therefore CANNOT be recorded (rnt_capture_begin: run the call once first),
+ * as for the hybrid calls.  Profile name: "mod_raise". */
+int rnt_mod_raise(rnt_buf* out, const rnt_buf* in);
+/* out = in * X^k in Z_q[X]/(X^N + 1) for every limb and poly, k taken mod 2N
+ * (negative k allowed): with k in [0, 2N), coefficient j of `in` lands at
+ * (j + k) mod N, negated when floor((j + k) / N) is odd; canonical (0 stays
+ * 0).  Both buffers on one context, coefficient domain; recordable.  out == in
+ * -> RNT_ERR_BAD_ARGUMENT (the buffers must not overlap); an NTT-domain `in`
+ * -> RNT_ERR_DOMAIN_MISMATCH.  In the CKKS embedding X^(N/2) is i in every
+ * slot, so k = N/2 and k = 3N/2 multiply a plaintext's slots by i and -i
+ * exactly.  Profile name: "mul_monomial". */
+int rnt_mul_monomial(rnt_buf* out, const rnt_buf* in, int64_t k);
 
 /* ---- samplers (PolySampler, src/rings/traits.rs:74-127) */
 /* Fill every poly of `out` (coefficient domain) from the counter-based

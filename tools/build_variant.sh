@@ -10,7 +10,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 C=$ROOT/toy-heaan-ckks_amd/csrc; L=$ROOT/toy-heaan-ckks_amd/lib; V=$L/variants
 mkdir -p $V
 HF="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$C"
-OBJS_REST="$L/rnt_encode.o $L/rnt_sample.o $L/rnt_api.o"
+OBJS_REST="$L/rnt_encode.o $L/rnt_sample.o $L/rnt_raise.o $L/rnt_api.o"
 if [ "${MF_ONLY:-0}" = "1" ]; then
   # only rnt_mfma.hip with the flags (KSRC=<file>: another version of it), the rest as built
   /opt/rocm/bin/hipcc $HF "$@" -c ${KSRC:-$C/rnt_mfma.hip} -o $V/m_$NAME.o

@@ -98,7 +98,7 @@ const char* const kKernelNames[rnt::K_COUNT] = {
     "automorphism", "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt",
     "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
     "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto",
-    "moddown_rescale", "lincomb", "dot_tensor"};
+    "moddown_rescale", "lincomb", "dot_tensor", "mod_raise", "mul_monomial"};
 
 // A profiling call failed: clear the runtime's slot, keep the first failure
 // in the profiler, and stop profiling (rnt_profile_read reports it).
@@ -606,6 +606,7 @@ rnt::Tables::~Tables() {
   for (auto& e : resc_ext) cleanup(hipFree(e.second), "hipFree(context tables)");
   for (auto& e : crt_cache) cleanup(hipFree(e.second.dev), "hipFree(context tables)");
   for (auto& e : hyb_cache) cleanup(hipFree(e.dev), "hipFree(context tables)");
+  for (auto& e : raise_cache) cleanup(hipFree(e.dev), "hipFree(context tables)");
   for (void* p : {tw_fwd, tw_inv, sfft_tw, lconst, resc, resc_p, mf})
     cleanup(hipFree(p), "hipFree(context tables)");
   if (prof) {
@@ -1942,6 +1943,138 @@ static uint64_t rotation_exponent(int32_t k, uint64_t two_n) {
 extern "C" int rnt_rotate_slots(rnt_buf* out, const rnt_buf* in, int32_t k) {
   if (int rc = check_buf(in, "rnt_rotate_slots")) return rc;
   return rnt_automorphism(out, in, rotation_exponent(k, 2 * (uint64_t)in->ctx->t->n));
+}
+
+// ---------------------------------------------------------------------------
+// ModRaise and the monomial product (rnt_raise.hip)
+// ---------------------------------------------------------------------------
+// a / m for a little-endian a of 32-bit words, in place; returns a mod m.
+static uint64_t big_divmod_small(Big& a, uint64_t m) {
+  rnt::host::u128 rem = 0;
+  for (size_t w = a.size(); w-- > 0;) {
+    rem = (rem << 32) | a[w];
+    a[w] = (uint32_t)(rem / m);  // rem < m before the shift: the quotient fits a word
+    rem %= m;
+  }
+  return (uint64_t)rem;
+}
+
+// The constants of a raise from the first l0 limbs of `t` onto all of it,
+// cached on the tables per l0 (they depend on nothing else: the input basis
+// has those l0 moduli by value).  The first use allocates and copies, so it
+// cannot be recorded into a graph (one un-recorded run first).
+static int raise_tables(rnt::Tables* t, size_t l0, rnt::RaiseConsts* out) {
+  std::lock_guard<std::mutex> g(t->resc_mu);
+  for (auto& e : t->raise_cache)
+    if (e.l0 == l0) {
+      *out = e.rc;
+      return RNT_OK;
+    }
+  const size_t L = t->L, M = rnt::kRaiseMax;
+  const unsigned wbits = t->wide ? 64 : 32;
+  const std::vector<uint64_t>& q = t->moduli;
+  std::vector<uint64_t> h(L * (2 * M + 1), 0);  // rad[L][M], radp[L][M], q0m[L]
+  for (size_t j = 0; j < L; ++j) {
+    uint64_t r = 1 % q[j];
+    for (size_t i = 0; i < l0; ++i) {
+      h[j * M + i] = r;
+      h[L * M + j * M + i] = rnt::host::shoup_companion(r, q[j], wbits);
+      r = rnt::host::mulmod(r, q[i] % q[j], q[j]);
+    }
+    h[2 * L * M + j] = r;
+  }
+  rnt::RaiseDev rd;
+  rd.l0 = l0;
+  for (size_t i = 1; i < l0; ++i) {
+    for (size_t k = 0; k < i; ++k) {
+      rd.rc.g.pre[i][k] = h[i * M + k];
+      rd.rc.g.prep[i][k] = h[L * M + i * M + k];
+    }
+    rd.rc.g.ginv[i] = rnt::host::invmod(h[i * M + i], q[i]);
+    if (rd.rc.g.ginv[i] == 0) return fail(RNT_ERR_BAD_ARGUMENT, "mod_raise: the moduli are not pairwise coprime");
+    rd.rc.g.ginvp[i] = rnt::host::shoup_companion(rd.rc.g.ginv[i], q[i], wbits);
+  }
+  Big half{1};
+  for (size_t i = 0; i < l0; ++i) big_mul_small(half, q[i]);
+  for (size_t w = 0; w < half.size(); ++w)  // floor(Q0 / 2)
+    half[w] = (half[w] >> 1) | (w + 1 < half.size() ? half[w + 1] << 31 : 0);
+  for (size_t i = 0; i < l0; ++i) rd.rc.g.half[i] = big_divmod_small(half, q[i]);
+  const size_t wb = word_bytes(t);
+  void* d = nullptr;
+  HIP_TRY(hipMalloc(&d, h.size() * wb), "hipMalloc(mod_raise constants)");
+  hipError_t e;
+  if (wb == 4) {
+    std::vector<uint32_t> h32(h.begin(), h.end());
+    e = hipMemcpy(d, h32.data(), h.size() * 4, hipMemcpyHostToDevice);
+  } else {
+    e = hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    cleanup(hipFree(d), "hipFree(mod_raise constants)");
+    return hip_fail(e, "hipMemcpy(mod_raise constants)");
+  }
+  rd.dev = d;
+  rd.rc.rad = d;
+  rd.rc.radp = (const char*)d + L * M * wb;
+  rd.rc.q0m = (const char*)d + 2 * L * M * wb;
+  t->raise_cache.push_back(rd);
+  *out = rd.rc;
+  return RNT_OK;
+}
+
+extern "C" int rnt_mod_raise(rnt_buf* out, const rnt_buf* in) {
+  if (int rc = check_buf(out, "rnt_mod_raise")) return rc;
+  if (int rc = check_buf(in, "rnt_mod_raise")) return rc;
+  rnt::Tables* tc = out->ctx->t.get();
+  const rnt::Tables* t0 = in->ctx->t.get();
+  const size_t l0 = in->ctx->L, L = out->ctx->L;
+  if (t0->log_n != tc->log_n || t0->device != tc->device)
+    return fail(RNT_ERR_BASIS_MISMATCH, "mod_raise: the two bases differ in degree or device");
+  if (l0 >= L)
+    return fail(RNT_ERR_BAD_ARGUMENT, "mod_raise: the input has %zu limbs, the output %zu (nothing to raise onto)", l0,
+                L);
+  for (size_t l = 0; l < l0; ++l)
+    if (t0->moduli[l] != tc->moduli[l])
+      return fail(RNT_ERR_BASIS_MISMATCH, "mod_raise: limb %zu of the input basis is %" PRIu64 ", the output's %" PRIu64,
+                  l, t0->moduli[l], tc->moduli[l]);
+  if (t0->wide != tc->wide)
+    return fail_fields(RNT_ERR_UNSUPPORTED, 0, 0, "mod_raise: the two bases have different device word widths");
+  if (l0 > rnt::kRaiseMax)
+    return fail_fields(RNT_ERR_UNSUPPORTED, 0, 0, "mod_raise: %zu input limbs (at most %zu)", l0, rnt::kRaiseMax);
+  if (out->n_polys != in->n_polys)
+    return fail(RNT_ERR_BAD_ARGUMENT, "mod_raise: batch sizes differ (%zu vs %zu)", out->n_polys, in->n_polys);
+  if (in->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "mod_raise: the input must be in the coefficient domain");
+  if (int rc = set_device(out->ctx)) return rc;
+  rnt::RaiseConsts rc;
+  if (int r = raise_tables(tc, l0, &rc)) return r;
+  if (t0 != tc && t0->stream != tc->stream && g_capture == nullptr) {
+    // the input may still be in the making on its own basis' stream
+    hipEvent_t ev = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate(mod_raise order)");
+    hipError_t e = hipEventRecord(ev, t0->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(tc->stream, ev, 0);
+    cleanup(hipEventDestroy(ev), "hipEventDestroy(mod_raise order)");
+    HIP_TRY(e, "hipStreamWaitEvent(mod_raise order)");
+  }
+  rnt::Launch k = launch_for(out);
+  LAUNCH(k.t, rnt::K_MOD_RAISE, rnt::launch_mod_raise(k, out->data, in->data, l0, rc), "mod_raise");
+  out->in_ntt = 0;
+  return RNT_OK;
+}
+
+extern "C" int rnt_mul_monomial(rnt_buf* out, const rnt_buf* in, int64_t k) {
+  if (int rc = check_buf(out, "rnt_mul_monomial")) return rc;
+  if (int rc = check_buf(in, "rnt_mul_monomial")) return rc;
+  if (out == in) return fail(RNT_ERR_BAD_ARGUMENT, "mul_monomial: out and in are one buffer");
+  if (int rc = check_same(out, in, "rnt_mul_monomial")) return rc;
+  if (in->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "mul_monomial: the input must be in the coefficient domain");
+  if (int rc = set_device(in->ctx)) return rc;
+  rnt::Launch l = launch_for(in);
+  const int64_t two_n = 2 * (int64_t)l.t->n;
+  const uint64_t shift = (uint64_t)(((k % two_n) + two_n) % two_n);
+  LAUNCH(l.t, rnt::K_MUL_MONOMIAL, rnt::launch_mul_monomial(l, out->data, in->data, shift), "mul_monomial");
+  out->in_ntt = 0;
+  return RNT_OK;
 }
 
 // ---------------------------------------------------------------------------

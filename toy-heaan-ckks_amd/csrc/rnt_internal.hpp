@@ -102,6 +102,32 @@ struct HybridDev {
   HybridConsts hc{};
 };
 
+// The constants of rnt_mod_raise (rnt_raise.hip k_mod_raise) from the first
+// l0 <= kRaiseMax limbs of a basis onto all of it.  RaiseDigits goes to the
+// kernel by value (words of the basis' width held in u64): for i >= 1 the
+// Garner digit is d_i = (x_i - sum_{k<i} d_k pre[i][k]) ginv[i] mod q_i with
+// pre[i][k] = q_0 .. q_{k-1} mod q_i and ginv[i] = (q_0 .. q_{i-1})^-1 mod q_i;
+// half[i] are the mixed-radix digits of floor(Q0 / 2).  The device arrays run
+// over the ROOT limbs j of the tables: rad[j][i] = q_0 .. q_{i-1} mod q_j and
+// its Shoup companion ([L][kRaiseMax]), q0m[j] = Q0 mod q_j.
+constexpr size_t kRaiseMax = 4;
+struct RaiseDigits {
+  uint64_t pre[kRaiseMax][kRaiseMax], prep[kRaiseMax][kRaiseMax];
+  uint64_t ginv[kRaiseMax], ginvp[kRaiseMax];
+  uint64_t half[kRaiseMax];
+};
+struct RaiseConsts {
+  RaiseDigits g{};
+  const void* rad = nullptr;
+  const void* radp = nullptr;
+  const void* q0m = nullptr;
+};
+struct RaiseDev {
+  size_t l0 = 0;
+  void* dev = nullptr;
+  RaiseConsts rc{};
+};
+
 struct Tables {
   int device = 0;
   int wide = 0;            // 0: W = u32, 1: W = u64
@@ -138,6 +164,8 @@ struct Tables {
   // hybrid key-switch constants (rnt_*_hybrid) of a key basis, per (key limbs,
   // ciphertext limbs, alpha, limb map); under resc_mu, built on first use
   std::vector<struct HybridDev> hyb_cache;
+  // rnt_mod_raise constants per input limb count (under resc_mu, built on first use)
+  std::vector<struct RaiseDev> raise_cache;
   // CKKS special-FFT twiddles (rnt_encode.hip), [N/2] double2, built on
   // first encode/decode
   std::mutex sfft_mu;
@@ -155,7 +183,7 @@ enum KernelId {
   K_AUTOMORPHISM, K_KS_DECOMPOSE, K_KS_ROWS, K_TENSOR_ROWS, K_IMPORT, K_EXPORT, K_CRT,
   K_SFFT, K_SAMPLE, K_COPY, K_PLANE_FUSED, K_MF_NTT_FWD, K_MF_NTT_INV, K_WHOLE_FWD, K_WHOLE_INV, K_WHOLE_MUL,
   K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_MODUP, K_MODDOWN,
-  K_MODDOWN_AUTO, K_MODDOWN_RESCALE, K_LINCOMB, K_DOT_TENSOR, K_COUNT
+  K_MODDOWN_AUTO, K_MODDOWN_RESCALE, K_LINCOMB, K_DOT_TENSOR, K_MOD_RAISE, K_MUL_MONOMIAL, K_COUNT
 };
 
 struct Prof {
@@ -461,6 +489,14 @@ constexpr size_t kDotT = 4;
 hipError_t launch_dot_tensor(const Launch& k, void* d0, void* d1, void* d2, uint64_t out_ls, const void* x0,
                              const void* x1, const void* y0, const void* y1, uint64_t in_ls, uint64_t term_words,
                              size_t nt, bool accum);
+// launch_mod_raise (rnt_raise.hip k_mod_raise): k.t the OUTPUT basis' tables,
+// k.L its limbs, k.B polys; `in` holds l0 < k.L coefficient-domain limbs of k.B
+// polys (limb stride k.B N, as `out`) whose moduli are the tables' first l0.
+// Limb j of out = (the centred CRT value of in) mod q_j, canonical.
+hipError_t launch_mod_raise(const Launch& k, void* out, const void* in, size_t l0, const RaiseConsts& rc);
+// launch_mul_monomial (k_mul_monomial): out = in X^shift over k.L x k.B x N
+// contiguous words, shift in [0, 2N); out and in do not overlap.
+hipError_t launch_mul_monomial(const Launch& k, void* out, const void* in, uint64_t shift);
 // launch_hoist_mac_seed (k_hoist_mac_seed): launch_hoist_mac for one step whose
 // sums start, on the limbs j < hc.Lv, from seed_b[j] (P 2^w mod q_j) and
 // seed_a[j] (P 2^w mod q_j) and from 0 on the special limbs; the seeds are

@@ -263,6 +263,20 @@ class RnsPoly {
     return out;
   }
 
+  // ModRaise (rnt_mod_raise): the centred value of this polynomial's 1..4
+  // limbs on `basis`, a longer basis whose first moduli are this one's
+  RnsPoly mod_raise(BasisRef<N> basis) const {
+    RnsPoly out(std::move(basis));
+    check(rnt_mod_raise(out.buf_, buf_));
+    return out;
+  }
+  // self * X^k in Z_q[X]/(X^N + 1), k mod 2N (rnt_mul_monomial)
+  RnsPoly mul_monomial(int64_t k) const {
+    RnsPoly out(basis_);
+    check(rnt_mul_monomial(out.buf_, buf_, k));
+    return out;
+  }
+
   // automorphism / rotate_slots (poly.rs:492-569)
   RnsPoly automorphism(uint64_t g) const {
     RnsPoly out(basis_);

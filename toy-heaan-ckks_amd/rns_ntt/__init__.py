@@ -26,6 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RnsNttError, check, load
+from .homdft import HomDftPlan, homdft_plan
 from .poly_eval import PolyEvalPlan, poly_eval_plan
 
 __all__ = [
@@ -45,6 +46,12 @@ __all__ = [
     "mul_ciphertexts_hybrid_rescale",
     "linear_transform_bsgs_hybrid_rescale",
     "dot_ciphertexts_hybrid",
+    "conjugate_hybrid",
+    "mul_i",
+    "split_real_imag_hybrid",
+    "merge_real_imag",
+    "homdft_plan",
+    "HomDftPlan",
     "Ciphertext",
     "generate_primes",
     "is_ntt_friendly_prime",
@@ -564,6 +571,21 @@ class RnsPoly:
         check(load().rnt_mod_drop_last(out._h, self._h))
         return out
 
+    def mod_raise(self, basis: RnsBasis) -> "RnsPoly":
+        """ModRaise (rnt_mod_raise): this polynomial, on 1..4 limbs in the
+        coefficient domain, as the same centred integers on ``basis`` -- a
+        longer basis whose first moduli are this one's, by value."""
+        out = self._like(basis)
+        check(load().rnt_mod_raise(out._h, self._h))
+        return out
+
+    def mul_monomial(self, k: int) -> "RnsPoly":
+        """``self * X^k`` in Z_q[X]/(X^N + 1) (rnt_mul_monomial), k mod 2N:
+        an exact negacyclic shift; coefficient domain."""
+        out = self._like()
+        check(load().rnt_mul_monomial(out._h, self._h, int(k)))
+        return out
+
     # -- automorphisms (poly.rs:482-570) ------------------------------------
     def automorphism(self, exponent: int) -> "RnsPoly":
         out = self._like()
@@ -867,6 +889,50 @@ def mul_ciphertexts_hybrid(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsHybridKey) 
     check(load().rnt_ct_mul_relin_hybrid(out0.handle, out1.handle, ct1.c0.handle, ct1.c1.handle,
                                          ct2.c0.handle, ct2.c1.handle, rlk.a.handle, rlk.b.handle, rlk.alpha))
     return Ciphertext(out0, out1, ct1.logp + ct2.logp, ct1.logq)
+
+
+def conjugate_hybrid(ct: Ciphertext, conj_key: RnsHybridKey) -> Ciphertext:
+    """The complex conjugate of every slot: :func:`rotate_ciphertext_hybrid`
+    with the hybrid rotation key of step ``-N/2``.  ``rotation_exponent(-N/2)``
+    is ``5^(N/2) (2N - 1) = 2N - 1 mod 2N`` (5 has order N/2), the conjugation
+    ``X -> X^-1``, so that key IS a conjugation key
+    (``CkksEngine.generate_hybrid_conjugation_key``)."""
+    _require_class(conj_key, RnsHybridKey, "conjugate_hybrid")
+    if conj_key.rotation != -(ct.c0.basis.degree // 2):
+        raise ValueError(f"conjugate_hybrid: needs the rotation key of step -N/2 = {-(ct.c0.basis.degree // 2)}, "
+                         f"got step {conj_key.rotation}")
+    return rotate_ciphertext_hybrid(ct, conj_key)
+
+
+def mul_i(ct: Ciphertext, sign: int = 1) -> Ciphertext:
+    """Every slot times ``i`` (``sign = +1``) or ``-i`` (``-1``): both
+    components times ``X^(N/2)`` or ``X^(3N/2)`` (rnt_mul_monomial).  X^(N/2)
+    evaluates to i in every slot (5^k = 1 mod 4), so this is an exact
+    negacyclic shift: no level, no noise, logp and logq unchanged."""
+    if sign not in (1, -1):
+        raise ValueError("mul_i: sign is +1 or -1")
+    n = ct.c0.basis.degree
+    k = n // 2 if sign == 1 else 3 * n // 2
+    return Ciphertext(ct.c0.mul_monomial(k), ct.c1.mul_monomial(k), ct.logp, ct.logq)
+
+
+def split_real_imag_hybrid(ct: Ciphertext, conj_key: RnsHybridKey) -> tuple[Ciphertext, Ciphertext]:
+    """``(ct_re, ct_im)`` with ``ct_re = ct + conj(ct)`` and ``ct_im = (ct -
+    conj(ct)) X^(3N/2)``: ``2 Re`` and ``2 Im`` of the slots, carried as ``logp
+    = ct.logp + 1`` so that they decode to ``Re`` and ``Im`` -- the factor 2 is
+    exact and costs no level.  One key-switch."""
+    cj = conjugate_hybrid(ct, conj_key)
+    re = Ciphertext(ct.c0 + cj.c0, ct.c1 + cj.c1, ct.logp + 1, ct.logq)
+    im = mul_i(Ciphertext(ct.c0 - cj.c0, ct.c1 - cj.c1, ct.logp + 1, ct.logq), -1)
+    return re, im
+
+
+def merge_real_imag(ct_re: Ciphertext, ct_im: Ciphertext) -> Ciphertext:
+    """``ct_re + X^(N/2) ct_im``: slots ``re + i im``.  No key."""
+    if ct_re.logp != ct_im.logp or ct_re.logq != ct_im.logq:
+        raise ValueError("merge_real_imag: the two parts differ in logp or logq")
+    t = mul_i(ct_im, 1)
+    return Ciphertext(ct_re.c0 + t.c0, ct_re.c1 + t.c1, ct_re.logp, ct_re.logq)
 
 
 class RnsHybridKeySet:
@@ -1209,10 +1275,12 @@ def mul_ciphertexts_hybrid_rescale(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsHyb
 
 
 def linear_transform_bsgs_hybrid_rescale(ct: Ciphertext, diag: RnsPoly, baby_keyset: RnsHybridKeySet,
-                                         giant_keyset: RnsHybridKeySet) -> Ciphertext:
+                                         giant_keyset: RnsHybridKeySet,
+                                         out_basis: Optional[RnsBasis] = None) -> Ciphertext:
     """:func:`linear_transform_bsgs_hybrid` then rescale_ciphertext as one op
     (rnt_ct_linear_bsgs_hybrid_rescale): equal word for word to the two
-    calls, the closing ModDowns and the rescale in one kernel each."""
+    calls, the closing ModDowns and the rescale in one kernel each.
+    ``out_basis`` as in :func:`mul_ciphertexts_hybrid_rescale`."""
     _require_hybrid_set(baby_keyset, True, "linear_transform_bsgs_hybrid_rescale (baby keys)")
     _require_hybrid_set(giant_keyset, False, "linear_transform_bsgs_hybrid_rescale (giant keys)")
     if baby_keyset.alpha != giant_keyset.alpha:
@@ -1221,7 +1289,7 @@ def linear_transform_bsgs_hybrid_rescale(ct: Ciphertext, diag: RnsPoly, baby_key
     giant_keyset = _at_ct_level(giant_keyset, ct.c0.basis)
     q_last = ct.c0.basis.moduli()[-1]
     bits_dropped = q_last.bit_length()
-    new_basis = ct.c0.basis.drop_last(1)
+    new_basis = out_basis if out_basis is not None else ct.c0.basis.drop_last(1)
     out0, out1 = ct.c0._like(new_basis), ct.c0._like(new_basis)
     baby = (ctypes.c_int32 * len(baby_keyset.steps))(*baby_keyset.steps)
     giant = (ctypes.c_int32 * len(giant_keyset.steps))(*giant_keyset.steps)

@@ -139,6 +139,8 @@ SIGNATURES = {
     "rnt_mod_drop_last": (c_int, [_P, _P]),
     "rnt_automorphism": (c_int, [_P, _P, c_uint64]),
     "rnt_rotate_slots": (c_int, [_P, _P, c_int32]),
+    "rnt_mod_raise": (c_int, [_P, _P]),
+    "rnt_mul_monomial": (c_int, [_P, _P, c_int64]),
     "rnt_key_prepare": (c_int, [_P, _P]),
     "rnt_keyswitch": (c_int, [_P, _P, _P, _P, _P]),
     "rnt_ct_mul_relin": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
@@ -174,6 +176,15 @@ SIGNATURES = {
     "rnt_sample_gaussian": (c_int, [_P, ctypes.c_double, c_uint64, c_uint64]),
     "rnt_sample_ternary": (c_int, [_P, c_size_t, c_uint64, c_uint64]),
 }
+
+# the kernel names rnt_profile_read knows (kKernelNames, rnt_api.cpp), in id order
+PROFILE_NAMES = (
+    "col_fwd", "row_fwd", "row_inv", "row_mul", "col_inv", "elementwise", "rescale", "automorphism", "ks_decompose",
+    "ks_rows", "tensor_rows", "import", "export", "crt", "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd",
+    "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul", "bsgs_mac",
+    "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto", "moddown_rescale", "lincomb", "dot_tensor",
+    "mod_raise", "mul_monomial",
+)
 
 _lib = None
 

@@ -24,12 +24,25 @@ from typing import Optional
 import numpy as np
 
 from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsGadgetKeySet, RnsHybridKey,
-               RnsHybridKeySet, RnsPoly, bsgs_diagonal_rows, check, ct_lincomb, dot_ciphertexts_hybrid, linear_transform,
-               linear_transform_bsgs,
+               RnsHybridKeySet, RnsPoly, bsgs_diagonal_rows, check, conjugate_hybrid, ct_lincomb,
+               dot_ciphertexts_hybrid, linear_transform, linear_transform_bsgs, merge_real_imag, mul_i,
+               split_real_imag_hybrid,
                linear_transform_bsgs_hoisted, linear_transform_bsgs_hybrid, linear_transform_bsgs_hybrid_rescale,
                linear_transform_hybrid, load, mul_ciphertexts_gadget, mul_ciphertexts_hybrid,
                mul_ciphertexts_hybrid_rescale, poly_eval_plan, rescale_ciphertext, rotate_ciphertext,
                rotate_ciphertext_hoisted, rotate_ciphertext_hybrid, rotate_ciphertext_hybrid_hoisted)
+
+
+@dataclass
+class PreparedHomDft:
+    """A ``homdft_plan`` made ready for one top basis (``CkksEngine.prepare_homdft``):
+    ``bases[s]`` is the ONE basis object of level s (group s reads its input on
+    ``bases[s]`` and writes onto ``bases[s + 1]``), ``plaintexts[s]`` the BSGS
+    diagonal plaintexts of group s, NTT domain, on ``bases[s]``."""
+
+    plan: object
+    bases: list
+    plaintexts: list
 
 
 @dataclass
@@ -191,6 +204,26 @@ class CkksEngine:
     def generate_hybrid_rotation_key(self, sk: RnsPoly, rotation: int, rng, alpha: int) -> RnsHybridKey:
         return self._hybrid_key(sk, sk.rotate_slots(rotation), rng, alpha, rotation)
 
+    def generate_hybrid_conjugation_key(self, sk: RnsPoly, rng, alpha: int) -> RnsHybridKey:
+        """The hybrid rotation key of step ``-N/2``: its automorphism exponent
+        is ``5^(N/2) (2N - 1) = 2N - 1 mod 2N``, the conjugation, so every
+        hybrid rotation call conjugates with it (``conjugate_hybrid``)."""
+        return self.generate_hybrid_rotation_key(sk, -(self.degree // 2), rng, alpha)
+
+    conjugate_hybrid = staticmethod(conjugate_hybrid)
+    mul_i = staticmethod(mul_i)
+    split_real_imag_hybrid = staticmethod(split_real_imag_hybrid)
+    merge_real_imag = staticmethod(merge_real_imag)
+
+    def mod_raise(self, ct: Ciphertext, basis: Optional[RnsBasis] = None) -> Ciphertext:
+        """ModRaise: both components of a ciphertext on 1..4 limbs as the same
+        centred integers on ``basis`` (default: the engine's), rnt_mod_raise.
+        The result decrypts to ``m + Q0 I`` with a small integer polynomial I
+        (|I| <= (h + 1) / 2 for a secret of Hamming weight h): the input of
+        CoeffToSlot.  logp is unchanged, logq the new basis' bits."""
+        b = basis if basis is not None else self.basis
+        return Ciphertext(ct.c0.mod_raise(b), ct.c1.mod_raise(b), ct.logp, b.total_bits())
+
     rotate_ciphertext_hybrid = staticmethod(rotate_ciphertext_hybrid)
     mul_ciphertexts_hybrid = staticmethod(mul_ciphertexts_hybrid)
     mul_ciphertexts_hybrid_rescale = staticmethod(mul_ciphertexts_hybrid_rescale)
@@ -238,13 +271,113 @@ class CkksEngine:
     @staticmethod
     def linear_transform_bsgs_hybrid_rescale(ct: Ciphertext, diag_plaintexts: Plaintext,
                                              baby_keyset: RnsHybridKeySet,
-                                             giant_keyset: RnsHybridKeySet) -> Ciphertext:
+                                             giant_keyset: RnsHybridKeySet,
+                                             out_basis: Optional[RnsBasis] = None) -> Ciphertext:
         """``linear_transform_bsgs_hybrid`` then ``rescale_ciphertext`` as one
         op, word for word: logp grows by the diagonals' scale and drops, with
-        logq, by the bits of the limb rescaled away."""
-        out = linear_transform_bsgs_hybrid_rescale(ct, diag_plaintexts.poly, baby_keyset, giant_keyset)
+        logq, by the bits of the limb rescaled away.  ``out_basis`` (a
+        ``drop_last(1)`` of the input's basis) receives the result where a
+        circuit keeps one basis object per level."""
+        out = linear_transform_bsgs_hybrid_rescale(ct, diag_plaintexts.poly, baby_keyset, giant_keyset,
+                                                   out_basis=out_basis)
         out.logp += diag_plaintexts.scale_bits
         return out
+
+    # -- CoeffToSlot / SlotToCoeff (rns_ntt/homdft.py) ---------------------------
+    @staticmethod
+    def encode_diagonal_rows_bsgs(diags, baby_steps, giant_steps, encoder: CkksEncoder, basis: RnsBasis) -> Plaintext:
+        """The sparse twin of ``encode_diagonals_bsgs``: ``diags`` maps a step
+        in ``[0, slots)`` to that diagonal of the matrix (``d_k[s] = M[s][(s +
+        k) mod slots]``).  Row ``(j, i)`` is diagonal ``g_j + b_i`` rotated
+        back by ``g_j`` -- ``bsgs_diagonal_rows``' rule -- and a diagonal that
+        is absent a zero plaintext.  One batch on ``basis``, poly ``j n1 + i``,
+        NTT domain."""
+        slots = encoder.max_slots()
+        baby, giant = [int(b) for b in baby_steps], [int(g) for g in giant_steps]
+        if not baby or not giant:
+            raise ValueError("encode_diagonal_rows_bsgs: no steps")
+        if any(not 0 <= k < slots for k in baby + giant):
+            raise ValueError("encode_diagonal_rows_bsgs: every step must be in [0, slots) (slots - k for a rotation "
+                             "by -k)")
+        rows = np.zeros((len(giant), len(baby), slots), dtype=np.complex128)
+        seen = {}
+        for j, g in enumerate(giant):
+            for i, b in enumerate(baby):
+                d = (g + b) % slots
+                if d in seen:
+                    raise ValueError(f"encode_diagonal_rows_bsgs: pairs {seen[d]} and {(j, i)} both give diagonal {d}")
+                seen[d] = (j, i)
+                if d in diags:
+                    v = np.asarray(diags[d])
+                    if v.shape != (slots,):
+                        raise ValueError(f"encode_diagonal_rows_bsgs: diagonal {d} must hold {slots} values")
+                    rows[j, i] = np.roll(v, g)  # rows[j][i][s] = d[(s - g_j) mod slots]
+        missing = [d for d in diags if int(d) % slots not in seen and np.any(np.asarray(diags[d]) != 0)]
+        if missing:
+            raise ValueError(f"encode_diagonal_rows_bsgs: the grid does not name the nonzero diagonals {sorted(missing)}")
+        pt = encoder.encode_complex(rows.reshape(-1, slots), basis)
+        pt.poly.to_ntt_domain()
+        return pt
+
+    def prepare_homdft(self, plan, top_basis: RnsBasis) -> PreparedHomDft:
+        """Encode every group of ``plan`` on the level basis it runs on: group
+        s on ``top_basis`` less s limbs, ONE basis object per level, all kept.
+        Group s is encoded at ``scale_bits`` = the bit length of the prime q its
+        rescale removes, so logp leaves every group as it came; its diagonals
+        are first multiplied by ``q / 2^scale_bits``, which makes the encoding
+        scale q itself: the rescale divides by q, not by 2^scale_bits, and
+        without the factor every group would scale the whole plaintext -- the
+        large ``Q0 I`` of a raised ciphertext included -- by ``2^scale_bits / q``."""
+        mods = top_basis.moduli()
+        if len(mods) - plan.depth < 1:
+            raise ValueError(f"prepare_homdft: the plan consumes {plan.depth} levels, the basis has {len(mods)} limbs")
+        if top_basis.degree != plan.degree:
+            raise ValueError(f"prepare_homdft: the plan is for degree {plan.degree}, the basis has {top_basis.degree}")
+        bases = [top_basis] + [top_basis.drop_last(s) for s in range(1, plan.depth + 1)]
+        pts = []
+        for s, g in enumerate(plan.groups):
+            q = mods[len(mods) - 1 - s]
+            enc = CkksEncoder(plan.degree, q.bit_length())
+            drift = q / 2.0 ** q.bit_length()
+            diags = {k: v * drift for k, v in g.diags.items()}
+            pts.append(self.encode_diagonal_rows_bsgs(diags, g.baby_steps, g.giant_steps, enc, bases[s]))
+        return PreparedHomDft(plan, bases, pts)
+
+    def generate_homdft_key_sets(self, sk: RnsPoly, plan, rng, alpha: int) -> list:
+        """Per group ``(baby_keyset, giant_keyset)`` for the plan's steps: baby
+        keys in hoisting form, giant keys ordinary."""
+        return [(self.generate_hybrid_rotation_key_set(sk, g.baby_steps, rng, alpha, hoisted=True),
+                 self.generate_hybrid_rotation_key_set(sk, g.giant_steps, rng, alpha)) for g in plan.groups]
+
+    @staticmethod
+    def _homdft_hybrid(ct: Ciphertext, prepared: PreparedHomDft, keysets, direction: str, name: str) -> Ciphertext:
+        plan = prepared.plan
+        if plan.direction != direction:
+            raise ValueError(f"{name}: the plan's direction is {plan.direction!r}")
+        if len(keysets) != len(plan.groups):
+            raise ValueError(f"{name}: {len(keysets)} key set pairs for {len(plan.groups)} groups")
+        if ct.c0.basis is not prepared.bases[0]:
+            raise ValueError(f"{name}: the ciphertext is not on the basis object the plan was prepared for")
+        for s, (pt, (bk, gk)) in enumerate(zip(prepared.plaintexts, keysets)):
+            if list(bk.steps) != list(plan.groups[s].baby_steps) or list(gk.steps) != list(plan.groups[s].giant_steps):
+                raise ValueError(f"{name}: the key sets of group {s} are not for the plan's steps")
+            ct = CkksEngine.linear_transform_bsgs_hybrid_rescale(ct, pt, bk, gk, out_basis=prepared.bases[s + 1])
+        return ct
+
+    @staticmethod
+    def coeff_to_slot_hybrid(ct: Ciphertext, prepared: PreparedHomDft, keysets) -> Ciphertext:
+        """CoeffToSlot: the slots of the result hold ``a_j + i a_{j+n}`` over
+        ``2^logp`` (bit-reversed in j with ``order="bitrev"``) for the
+        polynomial ``a`` that ``ct`` decrypts to.  One
+        ``linear_transform_bsgs_hybrid_rescale`` per group; ``plan.depth``
+        levels down, logp unchanged."""
+        return CkksEngine._homdft_hybrid(ct, prepared, keysets, "coeff_to_slot", "coeff_to_slot_hybrid")
+
+    @staticmethod
+    def slot_to_coeff_hybrid(ct: Ciphertext, prepared: PreparedHomDft, keysets) -> Ciphertext:
+        """SlotToCoeff, the inverse: a ciphertext whose slots hold ``(a_j + i
+        a_{j+n}) / 2^logp`` becomes one that decrypts to ``a``."""
+        return CkksEngine._homdft_hybrid(ct, prepared, keysets, "slot_to_coeff", "slot_to_coeff_hybrid")
 
     # -- polynomial evaluation -------------------------------------------------
     ct_lincomb = staticmethod(ct_lincomb)
