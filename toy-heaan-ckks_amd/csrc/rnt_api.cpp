@@ -234,14 +234,15 @@ hipError_t prof_launch(const rnt::Tables* t, hipStream_t s, int id, F&& f) {
 
 
 
-inline rnt::Launch launch_for(const rnt_buf* b) {
+inline rnt::Launch launch_for(const rnt_ctx* ctx, size_t n_polys) {
   rnt::Launch k;
-  k.t = b->ctx->t.get();
-  k.L = b->ctx->L;
-  k.B = b->n_polys;
+  k.t = ctx->t.get();
+  k.L = ctx->L;
+  k.B = n_polys;
   k.s = k.t->stream;
   return k;
 }
+inline rnt::Launch launch_for(const rnt_buf* b) { return launch_for(b->ctx, b->n_polys); }
 
 inline size_t poly_words(const rnt_buf* b) { return b->ctx->L * b->n_polys * b->ctx->t->n; }
 inline uint64_t limb_stride(const rnt_buf* b) {
@@ -496,7 +497,8 @@ struct CallWs {
   hipStream_t s;
   void* p = nullptr;
   size_t bytes = 0;
-  explicit CallWs(const rnt_buf* b) : dev(b->ctx->t->device), s(b->ctx->t->stream) {}
+  explicit CallWs(const rnt_ctx* ctx) : dev(ctx->t->device), s(ctx->t->stream) {}
+  explicit CallWs(const rnt_buf* b) : CallWs(b->ctx) {}
   CallWs(const CallWs&) = delete;
   CallWs& operator=(const CallWs&) = delete;
   int get(size_t need) {
@@ -2095,91 +2097,151 @@ extern "C" int rnt_key_prepare(rnt_buf* key_a, rnt_buf* key_b) {
 
 namespace {
 
-int check_key(const rnt_buf* d, const rnt_buf* key_a, const rnt_buf* key_b) {
-  if (int rc = check_buf(key_a, "key")) return rc;
-  if (int rc = check_buf(key_b, "key")) return rc;
-  if (key_a->ctx != d->ctx || key_b->ctx != d->ctx)
-    return fail(RNT_ERR_BASIS_MISMATCH, "key-switch: key and ciphertext belong to different bases");
-  if (key_a->n_polys != d->ctx->L || key_b->n_polys != d->ctx->L)
-    return fail_fields(RNT_ERR_CHANNEL_COUNT, d->ctx->L,
-                       key_a->n_polys != d->ctx->L ? key_a->n_polys : key_b->n_polys,
-                       "gadget key must hold one poly per channel (%zu)", d->ctx->L);
-  if (!key_a->in_ntt || !key_b->in_ntt)
-    return fail(RNT_ERR_DOMAIN_MISMATCH, "key-switch: keys must be prepared (rnt_key_prepare)");
+// The key check of every gadget call: both halves are buffers of the basis
+// `ctx`, hold `polys` polys each and are NTT-resident.  stage: "", or "baby " /
+// "giant " of a two-stage call.
+int check_key_set(const char* name, const char* stage, const rnt_ctx* ctx, const rnt_buf* keys_a,
+                  const rnt_buf* keys_b, size_t polys) {
+  if (int rc = check_buf(keys_a, name)) return rc;
+  if (int rc = check_buf(keys_b, name)) return rc;
+  if (keys_a->ctx != ctx || keys_b->ctx != ctx)
+    return fail(RNT_ERR_BASIS_MISMATCH, "%s: the %skeys and the ciphertext belong to different bases", name, stage);
+  if (keys_a->n_polys != polys || keys_b->n_polys != polys)
+    return fail_fields(RNT_ERR_CHANNEL_COUNT, polys, keys_a->n_polys != polys ? keys_a->n_polys : keys_b->n_polys,
+                       "%s: the %skeys must hold one poly per step and source limb (%zu)", name, stage, polys);
+  if (!keys_a->in_ntt || !keys_b->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH,
+                "%s: the %skeys must be prepared (rnt_key_prepare; rnt_key_prepare_hoisted for a hoisted call)", name,
+                stage);
   return RNT_OK;
 }
 
-// polys per key-switch chunk so that S ([L][L][Bc][N]) stays <= ~1 GiB
-// Key-switch workspace cap: S ([L][L][Bc][N] words) of a chunk.  The key
-// rows are read once per chunk from HBM (the batch hits them in cache, see
-// row_pos_pfast), so bigger chunks cut key traffic per ciphertext; 4 GiB is
-// a small slice of the 288 GB.
+// One gadget key as the kernels read it: the first plane of either half and
+// the limb stride (words) of the buffers they stand in.  A key pair, or step t
+// of a packed key set ([L][n_steps L][N]: the set's stride, t L planes in).
+struct GadgetKey {
+  const void *a, *b;
+  uint64_t ls;
+  GadgetKey(const rnt_buf* keys_a, const rnt_buf* keys_b, size_t t = 0) : ls(limb_stride(keys_a)) {
+    const rnt::Tables* tb = keys_a->ctx->t.get();
+    const size_t off = t * keys_a->ctx->L * tb->n * word_bytes(tb);
+    a = (const char*)keys_a->data + off;
+    b = (const char*)keys_b->data + off;
+  }
+};
+
+// Polys per chunk of a batch of B within the key-switch workspace cap
+// (RNT_KS_WS_MB), at `planes` planes of N words per poly; one poly is the floor.
+// The key rows are read once per chunk from HBM (the batch hits them in cache,
+// see row_pos_pfast), so bigger chunks cut key traffic per ciphertext; the
+// default 4 GiB is a small slice of the 288 GB.
+size_t chunk_polys(const rnt::Tables* t, size_t planes, size_t B) {
+  return std::min(B, std::max<size_t>(t->ks_ws_bytes / (planes * t->n * word_bytes(t)), 1));
+}
+
+// The chunk of the calls that bound S ([L][L][Bc][N]) alone.  (The whole-plane
+// key-switch has no S: its chunk is bounded by the ct-mul's seven chunk-local
+// planes per limb instead.)
 size_t ks_chunk(const rnt::Tables* t, size_t L, size_t B) {
-  // (the whole-plane key-switch has no S: its chunk is bounded by the
-  // ct-mul's seven chunk-local planes per limb instead)
-  const size_t per = (rnt::ks_whole_ok(t) ? 7 * L : L * L) * t->n * (t->wide ? 8 : 4);
-  size_t c = t->ks_ws_bytes;
-  c = per ? c / per : B;
-  if (c < 1) c = 1;
-  return std::min(c, B);
+  return chunk_polys(t, rnt::ks_whole_ok(t) ? 7 * L : L * L, B);
 }
 
-// Key-switch scratch of a chunk of bc polys (words): S | U0 | U1, or none
-// for the whole-plane key-switch.
-size_t ks_scratch_words(const rnt::Tables* t, size_t L, size_t bc) {
-  return rnt::ks_whole_ok(t) ? 0 : (L * L + 2 * L) * bc * t->n;
+// The key-switch scratch of a chunk of kc.B polys, kc.L target limbs over
+// kc.src_limbs() source limbs, carved from one block: the decomposition S
+// ([Lt][Ls][Bc][N]) | the NTT-row accumulators U0 | U1 ([Lt][Bc][N], limb
+// stride ls).  gadget_ws_words() is its size for a chunk of bc polys; the
+// whole-plane key-switch has none.
+size_t gadget_ws_words(const rnt::Tables* t, size_t Lt, size_t Ls, size_t bc) {
+  return rnt::ks_whole_ok(t) ? 0 : (Lt * Ls + 2 * Lt) * bc * t->n;
 }
+struct GadgetWs {
+  char *S, *U0, *U1;
+  uint64_t ls;
+  GadgetWs(const rnt::Launch& kc, void* ws) : S((char*)ws), ls((uint64_t)kc.B * kc.t->n) {
+    const size_t acc = kc.L * ls * word_bytes(kc.t);
+    U0 = S + kc.src_limbs() * acc;
+    U1 = U0 + acc;
+  }
+};
 
-// Decomposition + key-switch rows of one chunk (k.B polys, k.L target limbs,
-// k.src_limbs() source limbs at src) into the NTT-row accumulators U0/U1.
+// The stages of every gadget call, for the kc.B polys of a chunk.
+//
+// Rows: the decomposition of src (coefficient domain, kc.src_limbs() limbs at
+// limb stride src_ls) into S, then the key-switch rows into U0/U1, seeded with
+// init0 / init1 (NTT rows, Montgomery-scaled, may be null); with `lin` the LIN
+// rows of one term of a linear combination (launch_ks_rows_lin).
 // (Running them per group of target limbs, so each S slice could stay in the
 // Infinity Cache between the two kernels, was slower: profiles/r02_ab_ks_groups.txt.)
-int ks_decompose_rows(const rnt::Launch& k, char* S, const char* src, uint64_t src_ls, char* U0,
-                      char* U1, uint64_t u_ls, const rnt_buf* key_a, const rnt_buf* key_b,
-                      const char* i0, const char* i1, uint64_t init_ls) {
-  LAUNCH(k.t, rnt::K_KS_DECOMPOSE, rnt::launch_ks_decompose(k, S, src, src_ls), "ks decompose");
-  LAUNCH(k.t, rnt::K_KS_ROWS,
-         rnt::launch_ks_rows(k, U0, U1, u_ls, S, key_a->data, key_b->data, limb_stride(key_a), i0, i1,
-                             init_ls),
-         "ks rows");
+int gadget_rows(const rnt::Launch& kc, const GadgetWs& ws, const void* src, uint64_t src_ls, const GadgetKey& key,
+                const void* init0, const void* init1, uint64_t init_ls, const rnt::KsLin* lin = nullptr) {
+  LAUNCH(kc.t, rnt::K_KS_DECOMPOSE, rnt::launch_ks_decompose(kc, ws.S, src, src_ls), "ks decompose");
+  if (lin) {
+    LAUNCH(kc.t, rnt::K_KS_ROWS,
+           rnt::launch_ks_rows_lin(kc, ws.U0, ws.U1, ws.ls, ws.S, key.a, key.b, key.ls, init0, init1, init_ls, *lin),
+           "ks rows");
+  } else {
+    LAUNCH(kc.t, rnt::K_KS_ROWS,
+           rnt::launch_ks_rows(kc, ws.U0, ws.U1, ws.ls, ws.S, key.a, key.b, key.ls, init0, init1, init_ls),
+           "ks rows");
+  }
   return RNT_OK;
 }
 
-// Gadget sum for polys [p0, p0+bc) of d into out0/out1 (full-batch layout):
-// out0 = INV(sum_i NTT(alpha_i) key_b[i] + init0) (+ add0), etc.
-// ws layout: S | U0 | U1.
-int ks_chunk_run(rnt::Launch k, void* ws, const rnt_buf* d, size_t p0, size_t bc,
-                 const rnt_buf* key_a, const rnt_buf* key_b, void* out0, void* out1,
-                 uint64_t out_ls, const void* init0, const void* init1, uint64_t init_ls,
-                 const void* add0, int with_init) {
-  const size_t n = k.t->n, L = k.L, wb = k.t->wide ? 8 : 4;
-  k.B = bc;
-  if (rnt::ks_whole_ok(k.t)) {
-    // 2^10 <= N <= 2^14: one launch, no S (ws unused)
-    const char* i0 = with_init && init0 ? (const char*)init0 + p0 * n * wb : nullptr;
-    const char* i1 = with_init && init1 ? (const char*)init1 + p0 * n * wb : nullptr;
-    const char* a0 = add0 ? (const char*)add0 + p0 * n * wb : nullptr;
-    LAUNCH(k.t, rnt::K_KS_WHOLE,
-           rnt::launch_ks_whole(k, (char*)out0 + p0 * n * wb, (char*)out1 + p0 * n * wb, out_ls,
-                                (const char*)d->data + p0 * n * wb, limb_stride(d), key_a->data, key_b->data,
-                                limb_stride(key_a), i0, i1, init_ls, a0),
+// Lower: the two inverse column passes, out0 = INV(U0) (+ add0), out1 =
+// INV(U1), at limb stride out_ls.
+int gadget_lower(const rnt::Launch& kc, const GadgetWs& ws, void* out0, void* out1, uint64_t out_ls,
+                 const void* add0) {
+  LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, out0, out_ls, ws.U0, ws.ls, 1, add0), "ks inverse");
+  LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, out1, out_ls, ws.U1, ws.ls, 1, nullptr), "ks inverse");
+  return RNT_OK;
+}
+
+// Lower with the rescale as the inverse's epilogue (engine.rs:263-282 after
+// :530-531), kc.L - 1 output limbs: per output the dropped limb's inverse runs
+// first, into the chunk plane LAST0 / LAST1 that the kept limbs' inverse reads.
+int gadget_lower_rescale(const rnt::Launch& kc, const GadgetWs& ws, char* LAST0, char* LAST1, void* out0, void* out1,
+                         uint64_t out_ls) {
+  const size_t L = kc.L;
+  rnt::Launch kl = kc;  // the dropped limb: its coefficient plane only
+  kl.L = 1;
+  rnt::ColRescArgs la;
+  la.limb0 = (uint32_t)(L - 1);
+  rnt::Launch kr = kc;  // the kept limbs, rescaled by it
+  kr.L = L - 1;
+  char* U[2] = {ws.U0, ws.U1};
+  char* LAST[2] = {LAST0, LAST1};
+  void* out[2] = {out0, out1};
+  for (int o = 0; o < 2; ++o) {
+    LAUNCH(kl.t, rnt::K_COL_INV,
+           rnt::launch_col_inv(kl, LAST[o], ws.ls, U[o] + (L - 1) * ws.ls * word_bytes(kc.t), ws.ls, 1, nullptr, false,
+                               la),
+           "ks inverse (dropped limb)");
+    rnt::ColRescArgs ra;
+    ra.last = LAST[o];
+    ra.inv = rnt::resc_inv_row(kc.t, L - 1, 0);
+    ra.invp = rnt::resc_inv_row(kc.t, L - 1, 1);
+    LAUNCH(kr.t, rnt::K_COL_INV, rnt::launch_col_inv(kr, out[o], out_ls, U[o], ws.ls, 1, nullptr, false, ra),
+           "ks inverse + rescale");
+  }
+  return RNT_OK;
+}
+
+// The gadget sum of one chunk: out0 = INV(sum_i NTT(alpha_i(src)) key_b[i] +
+// init0) (+ add0), out1 with key_a and init1 -- the whole-plane key-switch in
+// one launch (2^10 <= N <= 2^14: no S, ws unused), or rows and lower.
+int gadget_chunk_run(const rnt::Launch& kc, void* ws, const void* src, uint64_t src_ls, const GadgetKey& key,
+                     void* out0, void* out1, uint64_t out_ls, const void* init0, const void* init1,
+                     uint64_t init_ls, const void* add0) {
+  if (rnt::ks_whole_ok(kc.t)) {
+    LAUNCH(kc.t, rnt::K_KS_WHOLE,
+           rnt::launch_ks_whole(kc, out0, out1, out_ls, src, src_ls, key.a, key.b, key.ls, init0, init1, init_ls,
+                                add0),
            "whole-plane key-switch");
     return RNT_OK;
   }
-  char* S = (char*)ws;
-  char* U0 = S + L * L * bc * n * wb;
-  char* U1 = U0 + L * bc * n * wb;
-  const uint64_t cls = (uint64_t)bc * n;  // chunk-local limb stride
-  const uint64_t d_ls = limb_stride(d);
-  const char* i0 = with_init && init0 ? (const char*)init0 + p0 * n * wb : nullptr;
-  const char* i1 = with_init && init1 ? (const char*)init1 + p0 * n * wb : nullptr;
-  if (int rc = ks_decompose_rows(k, S, (const char*)d->data + p0 * n * wb, d_ls, U0, U1, cls, key_a,
-                                 key_b, i0, i1, init_ls))
-    return rc;
-  const char* a0 = add0 ? (const char*)add0 + p0 * n * wb : nullptr;
-  LAUNCH(k.t, rnt::K_COL_INV, rnt::launch_col_inv(k, (char*)out0 + p0 * n * wb, out_ls, U0, cls, 1, a0), "ks inverse");
-  LAUNCH(k.t, rnt::K_COL_INV, rnt::launch_col_inv(k, (char*)out1 + p0 * n * wb, out_ls, U1, cls, 1, nullptr), "ks inverse");
-  return RNT_OK;
+  const GadgetWs g(kc, ws);
+  if (int rc = gadget_rows(kc, g, src, src_ls, key, init0, init1, init_ls)) return rc;
+  return gadget_lower(kc, g, out0, out1, out_ls, add0);
 }
 
 }  // namespace
@@ -2191,20 +2253,23 @@ extern "C" int rnt_keyswitch(rnt_buf* acc0, rnt_buf* acc1, const rnt_buf* d, con
   if (int rc = check_buf(d, "rnt_keyswitch")) return rc;
   if (int rc = check_same(acc0, d, "rnt_keyswitch")) return rc;
   if (int rc = check_same(acc1, d, "rnt_keyswitch")) return rc;
-  if (int rc = check_key(d, key_a, key_b)) return rc;
+  if (int rc = check_key_set("rnt_keyswitch", "", d->ctx, key_a, key_b, d->ctx->L)) return rc;
   if (d->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "key-switch input must be in coefficient domain");
   if (acc0 == acc1 || acc0 == d || acc1 == d)
     return fail(RNT_ERR_BAD_ARGUMENT, "rnt_keyswitch: outputs must not alias each other or d");
   if (int rc = set_device(d->ctx)) return rc;
-  rnt::Launch k = launch_for(d);
+  const rnt::Launch k = launch_for(d);
   const size_t L = k.L, wb = word_bytes(k.t);
   const size_t bc = ks_chunk(k.t, L, d->n_polys);
+  const uint64_t ls = limb_stride(d);
   CallWs ws(acc0);
-  if (int rc = ws.get(std::max<size_t>(ks_scratch_words(k.t, L, bc) * wb, 16))) return rc;
+  if (int rc = ws.get(std::max<size_t>(gadget_ws_words(k.t, L, L, bc) * wb, 16))) return rc;
   for (size_t p0 = 0; p0 < d->n_polys; p0 += bc) {
-    const size_t c = std::min(bc, d->n_polys - p0);
-    if (int rc = ks_chunk_run(k, ws.p, d, p0, c, key_a, key_b, acc0->data, acc1->data,
-                              limb_stride(d), nullptr, nullptr, 0, nullptr, 0))
+    rnt::Launch kc = k;
+    kc.B = std::min(bc, d->n_polys - p0);
+    const size_t off = p0 * k.t->n * wb;
+    if (int rc = gadget_chunk_run(kc, ws.p, (const char*)d->data + off, ls, GadgetKey(key_a, key_b),
+                                  (char*)acc0->data + off, (char*)acc1->data + off, ls, nullptr, nullptr, 0, nullptr))
       return rc;
   }
   acc0->in_ntt = acc1->in_ntt = 0;
@@ -2218,16 +2283,7 @@ extern "C" int rnt_keyswitch_ext(rnt_buf* acc0, rnt_buf* acc1, const void* src, 
   if (int rc = check_buf(acc1, "rnt_keyswitch_ext")) return rc;
   if (int rc = check_same(acc0, acc1, "rnt_keyswitch_ext")) return rc;
   if (!src || src_limbs == 0) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_keyswitch_ext: empty source");
-  if (int rc = check_buf(key_a, "key")) return rc;
-  if (int rc = check_buf(key_b, "key")) return rc;
-  if (key_a->ctx != acc0->ctx || key_b->ctx != acc0->ctx)
-    return fail(RNT_ERR_BASIS_MISMATCH, "key-switch: key and accumulator belong to different bases");
-  if (key_a->n_polys != src_limbs || key_b->n_polys != src_limbs)
-    return fail_fields(RNT_ERR_CHANNEL_COUNT, src_limbs,
-                       key_a->n_polys != src_limbs ? key_a->n_polys : key_b->n_polys,
-                       "gadget key must hold one poly per source limb (%zu)", src_limbs);
-  if (!key_a->in_ntt || !key_b->in_ntt)
-    return fail(RNT_ERR_DOMAIN_MISMATCH, "key-switch: keys must be prepared (rnt_key_prepare)");
+  if (int rc = check_key_set("rnt_keyswitch_ext", "", acc0->ctx, key_a, key_b, src_limbs)) return rc;
   const rnt_buf* seeds[2] = {init0, init1};
   for (const rnt_buf* sd : seeds) {
     if (!sd) continue;
@@ -2238,43 +2294,25 @@ extern "C" int rnt_keyswitch_ext(rnt_buf* acc0, rnt_buf* acc1, const void* src, 
   if (acc0 == acc1) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_keyswitch_ext: outputs alias");
   if (int rc = set_device(acc0->ctx)) return rc;
   rnt::Launch k = launch_for(acc0);
+  k.Ls = src_limbs;
   const size_t Lt = k.L, Ls = src_limbs, n = k.t->n, wb = word_bytes(k.t), B = acc0->n_polys;
   const uint64_t src_ls = (uint64_t)B * n, full_ls = limb_stride(acc0);
-  if (rnt::ks_whole_ok(k.t)) {
-    // 2^10 <= N <= 2^14: the whole batch in one launch, no S
-    rnt::Launch kw = k;
-    kw.Ls = Ls;
-    LAUNCH(kw.t, rnt::K_KS_WHOLE,
-           rnt::launch_ks_whole(kw, acc0->data, acc1->data, full_ls, src, src_ls, key_a->data, key_b->data,
-                                limb_stride(key_a), init0 ? init0->data : nullptr, init1 ? init1->data : nullptr,
-                                full_ls, nullptr),
-           "whole-plane key-switch");
-    acc0->in_ntt = acc1->in_ntt = 0;
-    return RNT_OK;
-  }
-  // polys per chunk: S is [Lt][Ls][Bc][N]
-  size_t bc = std::max<size_t>(1, k.t->ks_ws_bytes / std::max<size_t>(1, Lt * Ls * n * wb));
-  bc = std::min(bc, B);
+  // polys per chunk: S is [Lt][Ls][Bc][N]; the whole-plane key-switch (2^10 <=
+  // N <= 2^14) has no S and takes the whole batch in one launch
+  const bool whole = rnt::ks_whole_ok(k.t);
+  const size_t bc = whole ? B : chunk_polys(k.t, Lt * Ls, B);
   CallWs ws(acc0);
-  if (int rc = ws.get((Lt * Ls + 2 * Lt) * bc * n * wb)) return rc;
+  if (!whole)
+    if (int rc = ws.get(gadget_ws_words(k.t, Lt, Ls, bc) * wb)) return rc;
   for (size_t p0 = 0; p0 < B; p0 += bc) {
     rnt::Launch kc = k;
     kc.B = std::min(bc, B - p0);
-    kc.Ls = Ls;
-    const uint64_t cls = (uint64_t)kc.B * n;
-    char* S = (char*)ws.p;
-    char* U0 = S + Lt * Ls * kc.B * n * wb;
-    char* U1 = U0 + Lt * kc.B * n * wb;
     const size_t off = p0 * n * wb;
     const char* i0 = init0 ? (const char*)init0->data + off : nullptr;
     const char* i1 = init1 ? (const char*)init1->data + off : nullptr;
-    if (int rc = ks_decompose_rows(kc, S, (const char*)src + off, src_ls, U0, U1, cls, key_a, key_b,
-                                   i0, i1, full_ls))
+    if (int rc = gadget_chunk_run(kc, ws.p, (const char*)src + off, src_ls, GadgetKey(key_a, key_b),
+                                  (char*)acc0->data + off, (char*)acc1->data + off, full_ls, i0, i1, full_ls, nullptr))
       return rc;
-    LAUNCH(kc.t, rnt::K_COL_INV,
-           rnt::launch_col_inv(kc, (char*)acc0->data + off, full_ls, U0, cls, 1, nullptr), "ks inverse");
-    LAUNCH(kc.t, rnt::K_COL_INV,
-           rnt::launch_col_inv(kc, (char*)acc1->data + off, full_ls, U1, cls, 1, nullptr), "ks inverse");
   }
   acc0->in_ntt = acc1->in_ntt = 0;
   return RNT_OK;
@@ -2385,8 +2423,8 @@ static int ct_mul_relin_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
   // the key-switch's diagonal from the tensor's d2^ (one more chunk plane
   // set, D2H): the four-step key-switch on tiled grids, whose tensor writes it
   const bool diag = k.t->ks_diag && nt != 0 && !rnt::ks_whole_ok(k.t) && rnt::col_resc_ok(k.t);
-  const size_t need = ((nt + 3 + (diag ? 1 : 0)) * chunk_words + ks_scratch_words(k.t, L, bc) +
-                       (resc ? 2 * bc * n : 0)) * wb;
+  const size_t ks_words = gadget_ws_words(k.t, L, L, bc);
+  const size_t need = ((nt + 3 + (diag ? 1 : 0)) * chunk_words + ks_words + (resc ? 2 * bc * n : 0)) * wb;
   CallWs cws(out0);
   if (int rc = cws.get(need)) return rc;
   char* ws = (char*)cws.p;
@@ -2396,11 +2434,11 @@ static int ct_mul_relin_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
   char* D1 = D0 + chunk_words * wb;
   char* D2 = D1 + chunk_words * wb;
   char* KS = D2 + chunk_words * wb;
-  char* D2H = nullptr;
-  if (diag) {
-    D2H = KS + ks_scratch_words(k.t, L, bc) * wb + (resc ? 2 * bc * n * wb : 0);
-  }
+  char* LAST0 = KS + ks_words * wb;  // (resc)
+  char* LAST1 = LAST0 + bc * n * wb;
+  char* D2H = diag ? KS + ks_words * wb + (resc ? 2 * bc * n * wb : 0) : nullptr;
   const uint64_t full_ls = limb_stride(c0);
+  const GadgetKey key(key_a, key_b);
   for (size_t p0 = 0; p0 < B; p0 += bc) {
     const size_t c = std::min(bc, B - p0);
     rnt::Launch kc = k;
@@ -2410,52 +2448,19 @@ static int ct_mul_relin_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
       kc.d2hat = D2H;  // written by the tensor, read by the key-switch rows
       kc.d2hat_ls = cls;
     }
-    auto off = [&](const rnt_buf* b) { return (const char*)b->data + p0 * n * wb; };
+    auto off = [&](const rnt_buf* b) { return (char*)b->data + p0 * n * wb; };
     // the ciphertexts read in place (full limb stride) into the chunk's D0..D2
     if (int rc = tensor(kc, T, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls)) return rc;
-    if (resc) {
-      // gadget sum into the chunk's NTT-row accumulators, then the inverse
-      // with the rescale fused (engine.rs:263-282 after :530-531)
-      char* S = KS;
-      char* U0 = S + L * L * c * n * wb;
-      char* U1 = U0 + L * c * n * wb;
-      char* LAST0 = KS + ks_scratch_words(k.t, L, bc) * wb;
-      char* LAST1 = LAST0 + bc * n * wb;
-      if (int rc = ks_decompose_rows(kc, S, D2, cls, U0, U1, cls, key_a, key_b, D0, D1, cls)) return rc;
-      rnt::Launch kl = kc;  // the dropped limb: its coefficient plane only
-      kl.L = 1;
-      rnt::ColRescArgs la;
-      la.limb0 = (uint32_t)(L - 1);
-      rnt::Launch kr = kc;  // the kept limbs, rescaled by it
-      kr.L = L - 1;
-      const uint64_t rls = limb_stride(out0);
-      char* U[2] = {U0, U1};
-      char* LAST[2] = {LAST0, LAST1};
-      rnt_buf* O[2] = {out0, out1};
-      for (int o = 0; o < 2; ++o) {
-        LAUNCH(kl.t, rnt::K_COL_INV,
-               rnt::launch_col_inv(kl, LAST[o], cls, U[o] + (L - 1) * cls * wb, cls, 1, nullptr, false, la),
-               "ks inverse (dropped limb)");
-        rnt::ColRescArgs ra;
-        ra.last = LAST[o];
-        ra.inv = rnt::resc_inv_row(k.t, L - 1, 0);
-        ra.invp = rnt::resc_inv_row(k.t, L - 1, 1);
-        LAUNCH(kr.t, rnt::K_COL_INV,
-               rnt::launch_col_inv(kr, (char*)O[o]->data + p0 * n * wb, rls, U[o], cls, 1, nullptr, false, ra),
-               "ks inverse + rescale");
-      }
+    // gadget sum with d0hat / d1hat as accumulator seeds (engine.rs:530-531)
+    if (!resc) {
+      if (int rc = gadget_chunk_run(kc, KS, D2, cls, key, off(out0), off(out1), full_ls, D0, D1, cls, nullptr))
+        return rc;
       continue;
     }
-    // gadget sum with d0hat / d1hat as accumulator seeds (engine.rs:530-531)
-    // d2 lives in a chunk-local buffer: present it as a full "buffer".
-    rnt_buf d2view;
-    d2view.ctx = c0->ctx;
-    d2view.n_polys = c;
-    d2view.data = D2;
-    if (int rc = ks_chunk_run(kc, KS, &d2view, 0, c, key_a, key_b, (char*)out0->data + p0 * n * wb,
-                              (char*)out1->data + p0 * n * wb, full_ls, D0, D1, cls, nullptr, 1))
-      return rc;
-    d2view.data = nullptr;  // not owned
+    // into the chunk's NTT-row accumulators, then the inverse with the rescale fused
+    const GadgetWs g(kc, KS);
+    if (int rc = gadget_rows(kc, g, D2, cls, key, D0, D1, cls)) return rc;
+    if (int rc = gadget_lower_rescale(kc, g, LAST0, LAST1, off(out0), off(out1), limb_stride(out0))) return rc;
   }
   out0->in_ntt = out1->in_ntt = 0;
   return RNT_OK;
@@ -2469,7 +2474,7 @@ static int ct_mul_check(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const r
     if (int rc = check_buf(b, name)) return rc;
   for (int i = 3; i < 6; ++i)
     if (int rc = check_same(c0, all[i], name)) return rc;
-  if (int rc = check_key(c0, key_a, key_b)) return rc;
+  if (int rc = check_key_set(name, "", c0->ctx, key_a, key_b, c0->ctx->L)) return rc;
   if (c0->in_ntt || c1->in_ntt || c0p->in_ntt || c1p->in_ntt)
     return fail(RNT_ERR_DOMAIN_MISMATCH, "mul_ciphertexts_gadget: inputs must be in coefficient domain");
   if (out0 == out1) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
@@ -2505,11 +2510,12 @@ extern "C" int rnt_ct_mul_relin_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_
   return rc;
 }
 
-// The rotation's body (arguments checked by the caller).  The keys are read
-// through their data pointer and limb stride only, so rnt_ct_linear passes one
-// term's slice of a packed key set as a view.
-static int ct_rotate_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
-                          int32_t kk, const rnt_buf* key_a, const rnt_buf* key_b);
+namespace {
+// The rotation's body on raw [L][B][N] blocks of the basis `ctx` (defined with
+// the linear transforms, which run it per term on the whole-plane rings).
+int ct_rotate_body(const rnt_ctx* ctx, size_t B, void* out0, void* out1, const void* c0, bool c0_ntt, const void* c1,
+                   bool c1_ntt, int32_t kk, const GadgetKey& key);
+}  // namespace
 
 extern "C" int rnt_ct_rotate(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
                              int32_t kk, const rnt_buf* key_a, const rnt_buf* key_b) {
@@ -2518,69 +2524,11 @@ extern "C" int rnt_ct_rotate(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
     if (int rc = check_buf(b, "rnt_ct_rotate")) return rc;
   for (int i = 1; i < 4; ++i)
     if (int rc = check_same(all[0], all[i], "rnt_ct_rotate")) return rc;
-  if (int rc = check_key(c0, key_a, key_b)) return rc;
+  if (int rc = check_key_set("rnt_ct_rotate", "", c0->ctx, key_a, key_b, c0->ctx->L)) return rc;
   if (out0 == out1) return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_rotate: out0 aliases out1");
-  return ct_rotate_body(out0, out1, c0, c1, kk, key_a, key_b);
-}
-
-static int ct_rotate_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
-                          int32_t kk, const rnt_buf* key_a, const rnt_buf* key_b) {
-  if (int rc = set_device(c0->ctx)) return rc;
-  rnt::Launch k = launch_for(c0);
-  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
-  const size_t words = L * B * n;
-  const uint64_t g = rotation_exponent(kk, 2 * (uint64_t)n);
-  // ws: SIG0 | SIG1 | [TMP when an input is NTT-domain] | key-switch chunk space
-  const size_t bc = ks_chunk(k.t, L, B);
-  const bool any_ntt = c0->in_ntt || c1->in_ntt;
-  // sigma(c0) needs no launch of its own on the tiled four-step key-switch:
-  // its inverse column pass gathers it from c0 as it adds it (k_colt_inv's
-  // addend with g^-1 mod 2N).  Only for one ciphertext by default
-  // (RNT_ROT_FUSE=1; 2: any batch, 0: never): the scattered 4-byte gather
-  // costs the inverse about what the automorphism launch costs, which at one
-  // ciphertext is mostly launch and tail (config 5: +2.0% at one ciphertext,
-  // -0.5% at eight, profiles/r06/ab_rot_fuse.txt).  Not in place on out0: a
-  // workgroup's gather would race the stores of the others on the same plane
-  const bool fuse0 = (k.t->rot_fuse == 2 || (k.t->rot_fuse == 1 && B == 1)) && (g & 1) && !c0->in_ntt &&
-                     !rnt::ks_whole_ok(k.t) && rnt::col_resc_ok(k.t) && out0->data != c0->data;
-  const size_t tmp_words = any_ntt ? words : 0;
-  CallWs ws(out0);
-  if (int rc = ws.get((2 * words + tmp_words + ks_scratch_words(k.t, L, bc)) * wb)) return rc;
-  char* sig0 = (char*)ws.p;
-  char* sig1 = sig0 + words * wb;
-  char* tmp = sig1 + words * wb;
-  char* KS = tmp + tmp_words * wb;
-  // sigma(c0), sigma(c1) in coefficient domain (engine.rs:417-419; poly.rs:494-504
-  // converts an NTT-domain input first)
-  for (int i = fuse0 ? 1 : 0; i < 2; ++i) {
-    const rnt_buf* src = i ? c1 : c0;
-    char* dst = i ? sig1 : sig0;
-    const void* s = src->data;
-    if (src->in_ntt) {
-      if (int rc = to_coeff_into(src, tmp)) return rc;
-      s = tmp;
-    }
-    LAUNCH(k.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(k, dst, s, g), "automorphism");
-  }
-  rnt_buf sview;
-  sview.ctx = c0->ctx;
-  sview.n_polys = B;
-  sview.data = sig1;
-  const uint64_t ls = limb_stride(c0);
-  rnt::Launch kr = k;
-  if (fuse0) {
-    // g^-1 mod 2N (g odd): Newton's iteration mod 2^64, then the mask
-    uint64_t x = g;
-    for (int it = 0; it < 6; ++it) x *= 2 - g * x;
-    kr.add_ginv = (uint32_t)(x & (2 * (uint64_t)n - 1));
-  }
-  for (size_t p0 = 0; p0 < B; p0 += bc) {
-    const size_t c = std::min(bc, B - p0);
-    if (int rc = ks_chunk_run(kr, KS, &sview, p0, c, key_a, key_b, out0->data, out1->data, ls,
-                              nullptr, nullptr, 0, fuse0 ? c0->data : sig0, 0))
-      return rc;
-  }
-  sview.data = nullptr;
+  if (int rc = ct_rotate_body(c0->ctx, c0->n_polys, out0->data, out1->data, c0->data, c0->in_ntt, c1->data,
+                              c1->in_ntt, kk, GadgetKey(key_a, key_b)))
+    return rc;
   out0->in_ntt = out1->in_ntt = 0;
   return RNT_OK;
 }
@@ -2691,6 +2639,60 @@ int inv_add_raw(const rnt::Launch& k, void* p, uint64_t ls, const void* addend) 
   return RNT_OK;
 }
 
+// The rotation's body (arguments checked by the caller): out = the key-switch
+// of sigma(c1) + sigma(c0), on contiguous [L][B][N] blocks of the basis `ctx`;
+// an input flagged NTT-domain is converted first.
+int ct_rotate_body(const rnt_ctx* ctx, size_t B, void* out0, void* out1, const void* c0, bool c0_ntt, const void* c1,
+                   bool c1_ntt, int32_t kk, const GadgetKey& key) {
+  if (int rc = set_device(ctx)) return rc;
+  const rnt::Launch k = launch_for(ctx, B);
+  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t);
+  const size_t words = L * B * n;
+  const uint64_t ls = (uint64_t)B * n, two_n = 2 * (uint64_t)n;
+  const uint64_t g = rotation_exponent(kk, two_n);
+  // ws: SIG0 | SIG1 | [TMP when an input is NTT-domain] | key-switch chunk space
+  const size_t bc = ks_chunk(k.t, L, B);
+  // sigma(c0) needs no launch of its own on the tiled four-step key-switch:
+  // its inverse column pass gathers it from c0 as it adds it (k_colt_inv's
+  // addend with g^-1 mod 2N).  Only for one ciphertext by default
+  // (RNT_ROT_FUSE=1; 2: any batch, 0: never): the scattered 4-byte gather
+  // costs the inverse about what the automorphism launch costs, which at one
+  // ciphertext is mostly launch and tail (config 5: +2.0% at one ciphertext,
+  // -0.5% at eight, profiles/r06/ab_rot_fuse.txt).  Not in place on out0: a
+  // workgroup's gather would race the stores of the others on the same plane
+  const bool fuse0 = (k.t->rot_fuse == 2 || (k.t->rot_fuse == 1 && B == 1)) && (g & 1) && !c0_ntt &&
+                     !rnt::ks_whole_ok(k.t) && rnt::col_resc_ok(k.t) && out0 != c0;
+  const size_t tmp_words = c0_ntt || c1_ntt ? words : 0;
+  CallWs ws(ctx);
+  if (int rc = ws.get((2 * words + tmp_words + gadget_ws_words(k.t, L, L, bc)) * wb)) return rc;
+  char* sig0 = (char*)ws.p;
+  char* sig1 = sig0 + words * wb;
+  char* tmp = sig1 + words * wb;
+  char* KS = tmp + tmp_words * wb;
+  // sigma(c0), sigma(c1) in coefficient domain (engine.rs:417-419; poly.rs:494-504
+  // converts an NTT-domain input first)
+  for (int i = fuse0 ? 1 : 0; i < 2; ++i) {
+    const void* s = i ? c1 : c0;
+    if (i ? c1_ntt : c0_ntt) {
+      if (int rc = copy_rows(k, tmp, ls, s, ls, ls, L)) return rc;
+      if (int rc = inv_raw(k, tmp, ls)) return rc;
+      s = tmp;
+    }
+    LAUNCH(k.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(k, i ? sig1 : sig0, s, g), "automorphism");
+  }
+  rnt::Launch kr = k;
+  if (fuse0) kr.add_ginv = (uint32_t)exponent_inverse(g, two_n);
+  const char* add0 = fuse0 ? (const char*)c0 : sig0;
+  for (size_t p0 = 0; p0 < B; p0 += bc) {
+    kr.B = std::min(bc, B - p0);
+    const size_t off = p0 * n * wb;
+    if (int rc = gadget_chunk_run(kr, KS, sig1 + off, ls, key, (char*)out0 + off, (char*)out1 + off, ls, nullptr,
+                                  nullptr, 0, add0 + off))
+      return rc;
+  }
+  return RNT_OK;
+}
+
 // The hoisted gadget sums of one chunk (kc.B polys of c1 at limb stride
 // c1_ls): the digits once -- D ([L][L kc.B][N]) <- NTT_j(c1_i 2^w mod q_j), a
 // buffer of L limbs and L kc.B polys through the ordinary forward transform,
@@ -2723,8 +2725,9 @@ int hoist_chunk(const rnt::Launch& kc, char* D, char* ACC, const void* c1, uint6
       idx[nt] = t;
       a0[nt] = ACC + 2 * nt * pw;
       a1[nt] = ACC + (2 * nt + 1) * pw;
-      ka[nt] = (const char*)keys_a->data + t * L * n * wb;
-      kb[nt] = (const char*)keys_b->data + t * L * n * wb;
+      const GadgetKey key(keys_a, keys_b, t);
+      ka[nt] = key.a;
+      kb[nt] = key.b;
       ++nt;
     }
     if (nt == 0) break;
@@ -2732,6 +2735,82 @@ int hoist_chunk(const rnt::Launch& kc, char* D, char* ACC, const void* c1, uint6
            "hoisted gadget sums");
     for (uint32_t u = 0; u < nt; ++u)
       if (int rc = finish(idx[u], (char*)a0[u], (char*)a1[u])) return rc;
+  }
+  return RNT_OK;
+}
+
+// Consecutive blocks of `unit` bytes carved from a workspace (none: nullptr).
+struct Carver {
+  char* p;
+  size_t unit;
+  char* take(size_t blocks = 1) {
+    char* r = blocks ? p : nullptr;
+    p += blocks * unit;
+    return r;
+  }
+};
+
+// The polys of a chunk stay where they are in the full batch (*x, limb stride
+// full_ls) or, with more than one chunk (X non-null), are gathered into X at
+// the chunk's own limb stride.
+int chunk_gather(const rnt::Launch& kc, char* X, const char** x, uint64_t full_ls) {
+  if (!X) return RNT_OK;
+  const uint64_t cls = (uint64_t)kc.B * kc.t->n;
+  if (int rc = copy_rows(kc, X, cls, *x, full_ls, cls, kc.L)) return rc;
+  *x = X;
+  return RNT_OK;
+}
+
+// One rotated term of a sum of rotations, into the chunk's accumulators:
+// sigma_g(x1) -> decomposition -> LIN rows with the seed NTT(sigma_g(x0)) 2^-w,
+// the Montgomery-form multiplier plane `mul` (limb stride mul_ls) and, with
+// `accum`, accumulation into U0/U1.  x0, x1 at the chunk's limb stride; SIG1,
+// SEED: chunk blocks.
+int lin_term(const rnt::Launch& kc, const GadgetWs& ws, char* SIG1, char* SEED, const void* x0, const void* x1,
+             uint64_t g, const GadgetKey& key, const void* mul, uint64_t mul_ls, bool accum) {
+  LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG1, x1, g), "automorphism");
+  LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SEED, x0, g), "automorphism");
+  if (int rc = fwd_raw(kc, SEED, ws.ls)) return rc;
+  LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 0, SEED, SEED, nullptr, 0, false), "seed scale");
+  rnt::KsLin lin;
+  lin.mul = mul;
+  lin.mul_ls = mul_ls;
+  lin.accum = accum ? 1u : 0u;
+  return gadget_rows(kc, ws, SIG1, ws.ls, key, SEED, nullptr, ws.ls, &lin);
+}
+
+// The epilogue of a chunk of such terms, per output o: without any rotated
+// term the unrotated sum Z[o] is the result; one chunk inverts U straight into
+// the output (limb stride full_ls), adding Z[o] (may be null); more chunks
+// invert into tmp[o] -- the addend shares the output's limb stride: a
+// chunk-local output -- and copy the rows out.
+int lin_finish(const rnt::Launch& kc, const GadgetWs& ws, bool any_rot, bool multi, char* const dst[2],
+               uint64_t full_ls, char* const Z[2], char* const tmp[2]) {
+  char* const U[2] = {ws.U0, ws.U1};
+  for (int o = 0; o < 2; ++o) {
+    if (!any_rot) {
+      if (int rc = copy_rows(kc, dst[o], full_ls, Z[o], ws.ls, ws.ls, kc.L)) return rc;
+    } else if (!multi) {
+      LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, dst[o], full_ls, U[o], ws.ls, 1, Z[o]), "ks inverse");
+    } else {
+      LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, tmp[o], ws.ls, U[o], ws.ls, 1, Z[o]), "ks inverse");
+      if (int rc = copy_rows(kc, dst[o], full_ls, tmp[o], ws.ls, ws.ls, kc.L)) return rc;
+    }
+  }
+  return RNT_OK;
+}
+
+// hoist_chunk's finish for a baby step of the BSGS bodies: the accumulators
+// back to coefficients (+ x0 on the first), sigma_g, and forward again into the
+// step's pair of baby blocks R, R + pw.
+int hoisted_baby_finish(const rnt::Launch& k, uint64_t ls, char* A0, char* A1, const void* x0, uint64_t g, char* R,
+                        size_t pw) {
+  if (int rc = inv_add_raw(k, A0, ls, x0)) return rc;
+  if (int rc = inv_raw(k, A1, ls)) return rc;
+  char* A[2] = {A0, A1};
+  for (int o = 0; o < 2; ++o) {
+    LAUNCH(k.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(k, R + o * pw, A[o], g), "automorphism");
+    if (int rc = fwd_raw(k, R + o * pw, ls)) return rc;
   }
   return RNT_OK;
 }
@@ -2749,28 +2828,15 @@ int ct_linear_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rn
   const uint64_t ls = limb_stride(c0);
   char* Z[2] = {(char*)ws, (char*)ws + pw};
   char* R[2] = {(char*)ws + 2 * pw, (char*)ws + 3 * pw};
-  rnt_buf rv[2], kv[2];
-  for (int o = 0; o < 2; ++o) {
-    rv[o].ctx = c0->ctx;
-    rv[o].n_polys = B;
-    rv[o].data = R[o];
-    rv[o].owns = false;
-  }
   const rnt_buf* src[2] = {c0, c1};
   for (size_t t = 0; t < n_terms; ++t) {
-    if (steps[t] == 0) {
+    if (steps[t] != 0) {
+      if (int rc = ct_rotate_body(c0->ctx, B, R[0], R[1], c0->data, false, c1->data, false, steps[t],
+                                  GadgetKey(keys_a, keys_b, t)))
+        return rc;
+    } else {
       for (int o = 0; o < 2; ++o)
         if (int rc = copy_rows(k, R[o], ls, src[o]->data, ls, ls, L)) return rc;
-    } else {
-      const rnt_buf* keys[2] = {keys_a, keys_b};
-      for (int o = 0; o < 2; ++o) {
-        kv[o].ctx = c0->ctx;
-        kv[o].n_polys = keys[o]->n_polys;  // (the packed set's limb stride)
-        kv[o].data = (char*)keys[o]->data + t * L * n * wb;
-        kv[o].in_ntt = 1;
-        kv[o].owns = false;
-      }
-      if (int rc = ct_rotate_body(&rv[0], &rv[1], c0, c1, steps[t], &kv[0], &kv[1])) return rc;
     }
     for (int o = 0; o < 2; ++o) {
       if (int rc = fwd_raw(k, R[o], ls)) return rc;
@@ -2788,47 +2854,37 @@ int ct_linear_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rn
 // The four-step key-switch: chunks outside, terms inside.  Per chunk the
 // workspace holds (chunk planes of L bc N words) X0 X1 (the chunk gathered,
 // more than one chunk only) | SIG1 | SEED | NT0 NT1 Z0 Z1 (a step-0 term only)
-// | S U0 U1.  Every nonzero term: sigma(c1) -> decomposition -> rows with the
-// seed NTT(sigma(c0)) 2^-w, the plaintext row and (after the first)
-// accumulation into U0/U1; the step-0 terms' products are summed in the NTT
-// domain, inverted and added by the chunk's two inverse column passes.
+// | S U0 U1.  Every nonzero term is a lin_term with the plaintext row; the
+// step-0 terms' products are summed in the NTT domain, inverted and added by
+// the chunk's two inverse column passes (lin_finish).
 int ct_linear_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
                     const int32_t* steps, size_t n_terms, const char* dm, const rnt_buf* keys_a,
                     const rnt_buf* keys_b, char* ws, size_t bc, bool any_zero, bool any_rot) {
   rnt::Launch k = launch_for(c0);
   const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
-  const size_t pw = L * bc * n * wb;
-  const uint64_t full_ls = limb_stride(c0);
+  const uint64_t full_ls = limb_stride(c0), two_n = 2 * (uint64_t)n;
   const bool multi = bc < B;
-  char* p = ws;
-  auto take = [&](bool on) {
-    char* r = on ? p : nullptr;
-    if (on) p += pw;
-    return r;
-  };
-  char* X[2] = {take(multi), take(multi)};
-  char* SIG1 = take(true);
-  char* SEED = take(true);
-  char* NT[2] = {take(any_zero), take(any_zero)};
-  char* Z[2] = {take(any_zero), take(any_zero)};
-  char* KS = p;
+  Carver cv{ws, L * bc * n * wb};
+  char* X[2] = {cv.take(multi), cv.take(multi)};
+  char* SIG1 = cv.take();
+  char* SEED = cv.take();
+  char* NT[2] = {cv.take(any_zero), cv.take(any_zero)};
+  char* Z[2] = {cv.take(any_zero), cv.take(any_zero)};
+  char* KS = cv.p;
+  char* const tmp[2] = {SEED, SIG1};
   const rnt_buf* src[2] = {c0, c1};
   rnt_buf* out[2] = {out0, out1};
-  const uint64_t two_n = 2 * (uint64_t)n;
   for (size_t p0 = 0; p0 < B; p0 += bc) {
-    const size_t c = std::min(bc, B - p0);
     rnt::Launch kc = k;
-    kc.B = c;
-    const uint64_t cls = (uint64_t)c * n;
-    char* S = KS;
-    char* U[2] = {S + L * L * c * n * wb, S + (L * L + L) * c * n * wb};
+    kc.B = std::min(bc, B - p0);
+    const GadgetWs g(kc, KS);
+    const uint64_t cls = g.ls;
     const char* x[2];
+    char* dst[2];
     for (int o = 0; o < 2; ++o) {
       x[o] = (const char*)src[o]->data + p0 * n * wb;
-      if (multi) {
-        if (int rc = copy_rows(kc, X[o], cls, x[o], full_ls, cls, L)) return rc;
-        x[o] = X[o];
-      }
+      dst[o] = (char*)out[o]->data + p0 * n * wb;
+      if (int rc = chunk_gather(kc, X[o], &x[o], full_ls)) return rc;
     }
     if (any_zero) {
       bool first = true;
@@ -2848,39 +2904,12 @@ int ct_linear_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_b
     bool first = true;
     for (size_t t = 0; t < n_terms; ++t) {
       if (steps[t] == 0) continue;
-      const uint64_t g = rotation_exponent(steps[t], two_n);
-      LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG1, x[1], g), "automorphism");
-      LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SEED, x[0], g), "automorphism");
-      if (int rc = fwd_raw(kc, SEED, cls)) return rc;
-      LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 0, SEED, SEED, nullptr, 0, false), "seed scale");
-      rnt::KsLin lin;
-      lin.mul = dm + t * n * wb;
-      lin.mul_ls = (uint64_t)n_terms * n;
-      lin.accum = first ? 0u : 1u;
-      const size_t koff = t * L * n * wb;
-      LAUNCH(kc.t, rnt::K_KS_DECOMPOSE, rnt::launch_ks_decompose(kc, S, SIG1, cls), "ks decompose");
-      LAUNCH(kc.t, rnt::K_KS_ROWS,
-             rnt::launch_ks_rows_lin(kc, U[0], U[1], cls, S, (const char*)keys_a->data + koff,
-                                     (const char*)keys_b->data + koff, limb_stride(keys_a), SEED, nullptr, cls,
-                                     lin),
-             "ks rows");
+      if (int rc = lin_term(kc, g, SIG1, SEED, x[0], x[1], rotation_exponent(steps[t], two_n),
+                            GadgetKey(keys_a, keys_b, t), dm + t * n * wb, (uint64_t)n_terms * n, !first))
+        return rc;
       first = false;
     }
-    for (int o = 0; o < 2; ++o) {
-      char* dst = (char*)out[o]->data + p0 * n * wb;
-      if (!any_rot) {
-        if (int rc = copy_rows(kc, dst, full_ls, Z[o], cls, cls, L)) return rc;
-      } else if (!multi) {
-        LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, dst, full_ls, U[o], cls, 1, any_zero ? Z[o] : nullptr),
-               "ks inverse");
-      } else {
-        // (the addend shares the output's limb stride: a chunk-local output)
-        char* tmp = o == 0 ? SEED : SIG1;
-        LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, tmp, cls, U[o], cls, 1, any_zero ? Z[o] : nullptr),
-               "ks inverse");
-        if (int rc = copy_rows(kc, dst, full_ls, tmp, cls, cls, L)) return rc;
-      }
-    }
+    if (int rc = lin_finish(kc, g, any_rot, multi, dst, full_ls, Z, tmp)) return rc;
   }
   return RNT_OK;
 }
@@ -2906,16 +2935,7 @@ extern "C" int rnt_ct_linear(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
   for (size_t t = 0; t < n_terms; ++t) (steps[t] == 0 ? any_zero : any_rot) = true;
   const size_t L = c0->ctx->L;
   if (any_rot || keys_a || keys_b) {
-    if (int rc = check_buf(keys_a, "rnt_ct_linear keys")) return rc;
-    if (int rc = check_buf(keys_b, "rnt_ct_linear keys")) return rc;
-    if (keys_a->ctx != c0->ctx || keys_b->ctx != c0->ctx)
-      return fail(RNT_ERR_BASIS_MISMATCH, "rnt_ct_linear: keys and ciphertext belong to different bases");
-    if (keys_a->n_polys != n_terms * L || keys_b->n_polys != n_terms * L)
-      return fail_fields(RNT_ERR_CHANNEL_COUNT, n_terms * L,
-                         keys_a->n_polys != n_terms * L ? keys_a->n_polys : keys_b->n_polys,
-                         "the key set must hold one poly per term and channel (%zu)", n_terms * L);
-    if (!keys_a->in_ntt || !keys_b->in_ntt)
-      return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_ct_linear: keys must be prepared (rnt_key_prepare)");
+    if (int rc = check_key_set("rnt_ct_linear", "", c0->ctx, keys_a, keys_b, n_terms * L)) return rc;
   }
   if (!diag->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_ct_linear: the plaintexts must be in the NTT domain");
   if (c0->in_ntt || c1->in_ntt)
@@ -2933,7 +2953,7 @@ extern "C" int rnt_ct_linear(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
   const size_t bc = composed ? B : ks_chunk(k.t, L, B);
   const size_t planes = composed ? 4 : (bc < B ? 2 : 0) + 2 + (any_zero ? 4 : 0);
   const size_t dm_bytes = L * n_terms * n * wb;
-  const size_t need = dm_bytes + planes * L * bc * n * wb + (composed ? 0 : ks_scratch_words(k.t, L, bc) * wb);
+  const size_t need = dm_bytes + planes * L * bc * n * wb + gadget_ws_words(k.t, L, L, bc) * wb;
   CallWs ws(out0);
   if (int rc = ws.get(std::max<size_t>(need, 16))) return rc;
   // the plaintexts in Montgomery form (m^ 2^w mod q), once per call: a
@@ -2994,17 +3014,7 @@ extern "C" int rnt_ct_rotate_hoisted(rnt_buf* out0, rnt_buf* out1, const rnt_buf
   size_t nz = 0;
   for (size_t t = 0; t < n_steps; ++t) nz += steps[t] != 0;
   if (nz || keys_a || keys_b) {
-    if (int rc = check_buf(keys_a, "rnt_ct_rotate_hoisted keys")) return rc;
-    if (int rc = check_buf(keys_b, "rnt_ct_rotate_hoisted keys")) return rc;
-    if (keys_a->ctx != c0->ctx || keys_b->ctx != c0->ctx)
-      return fail(RNT_ERR_BASIS_MISMATCH, "rnt_ct_rotate_hoisted: keys and ciphertext belong to different bases");
-    if (keys_a->n_polys != n_steps * L || keys_b->n_polys != n_steps * L)
-      return fail_fields(RNT_ERR_CHANNEL_COUNT, n_steps * L,
-                         keys_a->n_polys != n_steps * L ? keys_a->n_polys : keys_b->n_polys,
-                         "the key set must hold one poly per step and channel (%zu)", n_steps * L);
-    if (!keys_a->in_ntt || !keys_b->in_ntt)
-      return fail(RNT_ERR_DOMAIN_MISMATCH,
-                  "rnt_ct_rotate_hoisted: keys must be in hoisting form (rnt_key_prepare_hoisted)");
+    if (int rc = check_key_set("rnt_ct_rotate_hoisted", "", c0->ctx, keys_a, keys_b, n_steps * L)) return rc;
   }
   if (c0->in_ntt || c1->in_ntt)
     return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_ct_rotate_hoisted: the ciphertext must be in coefficient domain");
@@ -3023,8 +3033,7 @@ extern "C" int rnt_ct_rotate_hoisted(rnt_buf* out0, rnt_buf* out1, const rnt_buf
   // block and the gathered c0 (more than one chunk only), within the
   // key-switch workspace cap, one ciphertext being the floor
   const size_t tg = std::min<size_t>(nz, rnt::kHoistT);
-  const size_t per = (L * L + (2 * tg + 2) * L) * n * wb;
-  const size_t bc = nz ? std::min(B, std::max<size_t>(k.t->ks_ws_bytes / per, 1)) : B;
+  const size_t bc = nz ? chunk_polys(k.t, L * L + (2 * tg + 2) * L, B) : B;
   const bool multi = bc < B;
   const size_t pw = L * bc * n * wb;
   CallWs ws(out0);
@@ -3225,9 +3234,7 @@ size_t hybrid_planes(const HybridPlan& pl) { return pl.LE * pl.beta + 2 * pl.LE;
 // Polys per chunk within the key-switch workspace cap (`extra` further planes
 // per poly are the caller's), one poly being the floor.
 size_t hybrid_chunk(const HybridPlan& pl, size_t B, size_t extra) {
-  const rnt::Tables* t = pl.C->t.get();
-  const size_t per = (hybrid_planes(pl) + extra) * t->n * word_bytes(t);
-  return std::min(std::max<size_t>(B, 1), std::max<size_t>(t->ks_ws_bytes / per, 1));
+  return chunk_polys(pl.C->t.get(), hybrid_planes(pl) + extra, B);
 }
 
 // The key-switch workspace of a chunk of c polys, carved from one block: the
@@ -3702,18 +3709,6 @@ int bsgs_inner_sums(const rnt::Launch& k, const BsgsPlan& plan, char* VB, const 
   return RNT_OK;
 }
 
-void key_views(rnt_buf kv[2], const rnt_buf* c0, const rnt_buf* keys_a, const rnt_buf* keys_b, size_t t) {
-  const size_t L = c0->ctx->L, n = c0->ctx->t->n, wb = word_bytes(c0->ctx->t.get());
-  const rnt_buf* keys[2] = {keys_a, keys_b};
-  for (int o = 0; o < 2; ++o) {
-    kv[o].ctx = c0->ctx;
-    kv[o].n_polys = keys[o]->n_polys;  // (the packed set's limb stride)
-    kv[o].data = (char*)keys[o]->data + t * L * n * wb;
-    kv[o].in_ntt = 1;
-    kv[o].owns = false;
-  }
-}
-
 // The whole-plane rings: the composition itself on the whole batch -- every
 // baby rotation through the whole-plane key-switch and a forward transform,
 // the inner sums, one inverse per sum, every giant rotation, adds.
@@ -3731,15 +3726,7 @@ int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_
   char* T = VB + 2 * plan.nv * pw;
   char* HD = T + 2 * pw;      // hoisted: the digits (L blocks) | 2 kHoistT accumulator blocks
   char* HACC = HD + L * pw;
-  auto view = [&](rnt_buf& v, char* p) {
-    v.ctx = c0->ctx;
-    v.n_polys = B;
-    v.data = p;
-    v.in_ntt = 0;
-    v.owns = false;
-  };
   const rnt_buf* src[2] = {c0, c1};
-  rnt_buf kv[2], a[2], b[2];
   for (size_t i = 0; i < n1; ++i) {
     char* R[2] = {RB + 2 * i * pw, RB + (2 * i + 1) * pw};
     if (baby[i] == 0) {
@@ -3748,26 +3735,17 @@ int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_
     } else if (hoisted) {
       continue;  // below: one decomposition for all of them
     } else {
-      key_views(kv, c0, bka, bkb, i);
-      view(a[0], R[0]);
-      view(a[1], R[1]);
-      if (int rc = ct_rotate_body(&a[0], &a[1], c0, c1, baby[i], &kv[0], &kv[1])) return rc;
+      if (int rc = ct_rotate_body(c0->ctx, B, R[0], R[1], c0->data, false, c1->data, false, baby[i],
+                                  GadgetKey(bka, bkb, i)))
+        return rc;
     }
     for (int o = 0; o < 2; ++o)
       if (int rc = fwd_raw(k, R[o], ls)) return rc;
   }
   if (hoisted) {
     auto finish = [&](size_t i, char* A0, char* A1) -> int {
-      const uint64_t g = rotation_exponent(baby[i], 2 * (uint64_t)n);
-      if (int rc = inv_add_raw(k, A0, ls, c0->data)) return rc;
-      if (int rc = inv_raw(k, A1, ls)) return rc;
-      char* A[2] = {A0, A1};
-      for (int o = 0; o < 2; ++o) {
-        char* R = RB + (2 * i + o) * pw;
-        LAUNCH(k.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(k, R, A[o], g), "automorphism");
-        if (int rc = fwd_raw(k, R, ls)) return rc;
-      }
-      return RNT_OK;
+      return hoisted_baby_finish(k, ls, A0, A1, c0->data, rotation_exponent(baby[i], 2 * (uint64_t)n),
+                                 RB + 2 * i * pw, pw);
     };
     if (int rc = hoist_chunk(k, HD, HACC, c1->data, ls, baby, n1, bka, bkb, finish)) return rc;
   }
@@ -3784,15 +3762,13 @@ int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_
   }
   for (size_t j = 0; j < n2; ++j) {
     if (giant[j] == 0) continue;
-    key_views(kv, c0, gka, gkb, j);
-    view(a[0], VB + 2 * plan.slot[j] * pw);
-    view(a[1], VB + (2 * plan.slot[j] + 1) * pw);
-    view(b[0], have ? T : (char*)out0->data);
-    view(b[1], have ? T + pw : (char*)out1->data);
-    if (int rc = ct_rotate_body(&b[0], &b[1], &a[0], &a[1], giant[j], &kv[0], &kv[1])) return rc;
+    char* V0 = VB + 2 * plan.slot[j] * pw;
+    char* r[2] = {have ? T : (char*)out0->data, have ? T + pw : (char*)out1->data};
+    if (int rc = ct_rotate_body(c0->ctx, B, r[0], r[1], V0, false, V0 + pw, false, giant[j], GadgetKey(gka, gkb, j)))
+      return rc;
     if (have) {
       for (int o = 0; o < 2; ++o)
-        LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_elementwise(k, 0, out[o]->data, out[o]->data, b[o].data),
+        LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_elementwise(k, 0, out[o]->data, out[o]->data, r[o]),
                "add_assign");
     }
     have = true;
@@ -3803,14 +3779,12 @@ int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_
 // The four-step key-switch: chunks outside as in ct_linear_fused.  Per chunk
 // the workspace holds (chunk planes of L bc N words) X0 X1 (the chunk gathered,
 // more than one chunk only) | SIG1 | SEED | RB (2 n1) | VB (2 nv) | S U0 U1.
-// Baby stage: every nonzero step runs the whole key-switch (sigma(c1) ->
-// decomposition -> rows -> the two inverse column passes, sigma(c0) as the
-// addend) into its pair of RB blocks, a step-0 baby is a copy; each block is
-// then transformed forward.  Inner sums: k_bsgs_mac, one inverse per block.
-// Giant stage: every nonzero step feeds sigma(V1_j) through the decomposition
-// and the LIN rows with the Montgomery-one plane `one`, the seed
-// NTT(sigma(V0_j)) 2^-w and (after the first) accumulation into U0/U1; the
-// step-0 giants' sum is the addend of the chunk's two inverse column passes.
+// Baby stage: every nonzero step runs the whole key-switch (sigma(c1) -> rows
+// -> lower, sigma(c0) as the addend) into its pair of RB blocks, a step-0 baby
+// is a copy; each block is then transformed forward.  Inner sums: k_bsgs_mac,
+// one inverse per block.  Giant stage: every nonzero step is a lin_term on
+// (V0_j, V1_j) with the Montgomery-one plane `one`; the step-0 giants' sum is
+// the addend of the chunk's two inverse column passes (lin_finish).
 int ct_bsgs_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1, const int32_t* baby,
                   size_t n1, const int32_t* giant, size_t n2, const BsgsPlan& plan, const char* dm,
                   const char* one, const rnt_buf* bka, const rnt_buf* bkb, const rnt_buf* gka,
@@ -3818,42 +3792,33 @@ int ct_bsgs_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf
   rnt::Launch k = launch_for(c0);
   const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
   const size_t pw = L * bc * n * wb;
-  const uint64_t full_ls = limb_stride(c0);
+  const uint64_t full_ls = limb_stride(c0), two_n = 2 * (uint64_t)n;
   const bool multi = bc < B;
-  char* p = ws;
-  auto take = [&](size_t blocks) {
-    char* r = p;
-    p += blocks * pw;
-    return r;
-  };
-  char* X[2] = {nullptr, nullptr};
-  if (multi) {
-    X[0] = take(1);
-    X[1] = take(1);
-  }
-  char* SIG1 = take(1);
-  char* SEED = take(1);
-  char* RB = take(2 * n1);
-  char* VB = take(2 * plan.nv);
-  char* HACC = hoisted ? take(2 * rnt::kHoistT) : nullptr;  // (the digits take S)
-  char* KS = p;
+  Carver cv{ws, pw};
+  char* X[2] = {cv.take(multi), cv.take(multi)};
+  char* SIG1 = cv.take();
+  char* SEED = cv.take();
+  char* RB = cv.take(2 * n1);
+  char* VB = cv.take(2 * plan.nv);
+  char* HACC = cv.take(hoisted ? 2 * rnt::kHoistT : 0);  // (the digits take S)
+  char* KS = cv.p;
+  char* const tmp[2] = {SEED, SIG1};
+  char* Z[2] = {nullptr, nullptr};  // the step-0 giants' sum
+  if (plan.any_zero)
+    for (int o = 0; o < 2; ++o) Z[o] = VB + (2 * plan.zslot + o) * pw;
   const rnt_buf* src[2] = {c0, c1};
   rnt_buf* out[2] = {out0, out1};
-  const uint64_t two_n = 2 * (uint64_t)n;
   for (size_t p0 = 0; p0 < B; p0 += bc) {
-    const size_t c = std::min(bc, B - p0);
     rnt::Launch kc = k;
-    kc.B = c;
-    const uint64_t cls = (uint64_t)c * n;
-    char* S = KS;
-    char* U[2] = {S + L * L * c * n * wb, S + (L * L + L) * c * n * wb};
+    kc.B = std::min(bc, B - p0);
+    const GadgetWs g(kc, KS);
+    const uint64_t cls = g.ls;
     const char* x[2];
+    char* dst[2];
     for (int o = 0; o < 2; ++o) {
       x[o] = (const char*)src[o]->data + p0 * n * wb;
-      if (multi) {
-        if (int rc = copy_rows(kc, X[o], cls, x[o], full_ls, cls, L)) return rc;
-        x[o] = X[o];
-      }
+      dst[o] = (char*)out[o]->data + p0 * n * wb;
+      if (int rc = chunk_gather(kc, X[o], &x[o], full_ls)) return rc;
     }
     // baby stage
     const char* zero_done = nullptr;
@@ -3871,35 +3836,20 @@ int ct_bsgs_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf
       } else if (hoisted) {
         continue;  // below: one decomposition for all of them
       } else {
-        const uint64_t g = rotation_exponent(baby[i], two_n);
-        LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG1, x[1], g), "automorphism");
-        LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SEED, x[0], g), "automorphism");
-        const size_t koff = i * L * n * wb;
-        LAUNCH(kc.t, rnt::K_KS_DECOMPOSE, rnt::launch_ks_decompose(kc, S, SIG1, cls), "ks decompose");
-        LAUNCH(kc.t, rnt::K_KS_ROWS,
-               rnt::launch_ks_rows(kc, U[0], U[1], cls, S, (const char*)bka->data + koff,
-                                   (const char*)bkb->data + koff, limb_stride(bka), nullptr, nullptr, 0),
-               "ks rows");
-        LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, R[0], cls, U[0], cls, 1, SEED), "ks inverse");
-        LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, R[1], cls, U[1], cls, 1, nullptr), "ks inverse");
+        const uint64_t ge = rotation_exponent(baby[i], two_n);
+        LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG1, x[1], ge), "automorphism");
+        LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SEED, x[0], ge), "automorphism");
+        if (int rc = gadget_rows(kc, g, SIG1, cls, GadgetKey(bka, bkb, i), nullptr, nullptr, 0)) return rc;
+        if (int rc = gadget_lower(kc, g, R[0], R[1], cls, SEED)) return rc;
       }
       for (int o = 0; o < 2; ++o)
         if (int rc = fwd_raw(kc, R[o], cls)) return rc;
     }
     if (hoisted) {
       auto finish = [&](size_t i, char* A0, char* A1) -> int {
-        const uint64_t g = rotation_exponent(baby[i], two_n);
-        if (int rc = inv_add_raw(kc, A0, cls, x[0])) return rc;
-        if (int rc = inv_raw(kc, A1, cls)) return rc;
-        char* A[2] = {A0, A1};
-        for (int o = 0; o < 2; ++o) {
-          char* R = RB + (2 * i + o) * pw;
-          LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, R, A[o], g), "automorphism");
-          if (int rc = fwd_raw(kc, R, cls)) return rc;
-        }
-        return RNT_OK;
+        return hoisted_baby_finish(kc, cls, A0, A1, x[0], rotation_exponent(baby[i], two_n), RB + 2 * i * pw, pw);
       };
-      if (int rc = hoist_chunk(kc, S, HACC, x[1], cls, baby, n1, bka, bkb, finish)) return rc;
+      if (int rc = hoist_chunk(kc, g.S, HACC, x[1], cls, baby, n1, bka, bkb, finish)) return rc;
     }
     // inner sums, back to coefficients for the giant decomposition
     if (int rc = bsgs_inner_sums(kc, plan, VB, RB, pw, dm, n1, n2)) return rc;
@@ -3910,37 +3860,12 @@ int ct_bsgs_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf
     for (size_t j = 0; j < n2; ++j) {
       if (giant[j] == 0) continue;
       const char* V0 = VB + 2 * plan.slot[j] * pw;
-      const uint64_t g = rotation_exponent(giant[j], two_n);
-      LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG1, V0 + pw, g), "automorphism");
-      LAUNCH(kc.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SEED, V0, g), "automorphism");
-      if (int rc = fwd_raw(kc, SEED, cls)) return rc;
-      LAUNCH(kc.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kc, 0, SEED, SEED, nullptr, 0, false), "seed scale");
-      rnt::KsLin lin;
-      lin.mul = one;
-      lin.mul_ls = (uint64_t)n;
-      lin.accum = first ? 0u : 1u;
-      const size_t koff = j * L * n * wb;
-      LAUNCH(kc.t, rnt::K_KS_DECOMPOSE, rnt::launch_ks_decompose(kc, S, SIG1, cls), "ks decompose");
-      LAUNCH(kc.t, rnt::K_KS_ROWS,
-             rnt::launch_ks_rows_lin(kc, U[0], U[1], cls, S, (const char*)gka->data + koff,
-                                     (const char*)gkb->data + koff, limb_stride(gka), SEED, nullptr, cls, lin),
-             "ks rows");
+      if (int rc = lin_term(kc, g, SIG1, SEED, V0, V0 + pw, rotation_exponent(giant[j], two_n),
+                            GadgetKey(gka, gkb, j), one, (uint64_t)n, !first))
+        return rc;
       first = false;
     }
-    for (int o = 0; o < 2; ++o) {
-      char* dst = (char*)out[o]->data + p0 * n * wb;
-      char* Z = plan.any_zero ? VB + (2 * plan.zslot + o) * pw : nullptr;
-      if (!plan.any_rot) {
-        if (int rc = copy_rows(kc, dst, full_ls, Z, cls, cls, L)) return rc;
-      } else if (!multi) {
-        LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, dst, full_ls, U[o], cls, 1, Z), "ks inverse");
-      } else {
-        // (the addend shares the output's limb stride: a chunk-local output)
-        char* tmp = o == 0 ? SEED : SIG1;
-        LAUNCH(kc.t, rnt::K_COL_INV, rnt::launch_col_inv(kc, tmp, cls, U[o], cls, 1, Z), "ks inverse");
-        if (int rc = copy_rows(kc, dst, full_ls, tmp, cls, cls, L)) return rc;
-      }
-    }
+    if (int rc = lin_finish(kc, g, plan.any_rot, multi, dst, full_ls, Z, tmp)) return rc;
   }
   return RNT_OK;
 }
@@ -3950,19 +3875,7 @@ int check_stage_keys(const rnt_buf* c0, const int32_t* steps, size_t count, cons
   bool any_rot = false;
   for (size_t t = 0; t < count; ++t) any_rot = any_rot || steps[t] != 0;
   if (!(any_rot || keys_a || keys_b)) return RNT_OK;
-  const size_t L = c0->ctx->L;
-  if (int rc = check_buf(keys_a, "rnt_ct_linear_bsgs keys")) return rc;
-  if (int rc = check_buf(keys_b, "rnt_ct_linear_bsgs keys")) return rc;
-  if (keys_a->ctx != c0->ctx || keys_b->ctx != c0->ctx)
-    return fail(RNT_ERR_BASIS_MISMATCH, "rnt_ct_linear_bsgs: %s keys and ciphertext belong to different bases",
-                stage);
-  if (keys_a->n_polys != count * L || keys_b->n_polys != count * L)
-    return fail_fields(RNT_ERR_CHANNEL_COUNT, count * L,
-                       keys_a->n_polys != count * L ? keys_a->n_polys : keys_b->n_polys,
-                       "the %s key set must hold one poly per step and channel (%zu)", stage, count * L);
-  if (!keys_a->in_ntt || !keys_b->in_ntt)
-    return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_ct_linear_bsgs: %s keys must be prepared (rnt_key_prepare)", stage);
-  return RNT_OK;
+  return check_key_set("rnt_ct_linear_bsgs", stage, c0->ctx, keys_a, keys_b, count * c0->ctx->L);
 }
 
 }  // namespace
@@ -3985,8 +3898,8 @@ static int ct_linear_bsgs_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, 
   if (n_baby > SIZE_MAX / n_giant || diag->n_polys != n_baby * n_giant)
     return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_linear_bsgs: %zu plaintexts for %zu x %zu steps", diag->n_polys,
                 n_giant, n_baby);
-  if (int rc = check_stage_keys(c0, baby_steps, n_baby, baby_keys_a, baby_keys_b, "baby")) return rc;
-  if (int rc = check_stage_keys(c0, giant_steps, n_giant, giant_keys_a, giant_keys_b, "giant")) return rc;
+  if (int rc = check_stage_keys(c0, baby_steps, n_baby, baby_keys_a, baby_keys_b, "baby ")) return rc;
+  if (int rc = check_stage_keys(c0, giant_steps, n_giant, giant_keys_a, giant_keys_b, "giant ")) return rc;
   if (!diag->in_ntt)
     return fail(RNT_ERR_DOMAIN_MISMATCH, "rnt_ct_linear_bsgs: the plaintexts must be in the NTT domain");
   if (c0->in_ntt || c1->in_ntt)
@@ -4017,16 +3930,11 @@ static int ct_linear_bsgs_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, 
   // the key-switch scratch's S, which the whole-plane rings lack)
   const size_t planes =
       2 * n_baby + 2 * plan.nv + (composed ? 2 : 4) + (hoisted ? 2 * rnt::kHoistT + (composed ? L : 0) : 0);
-  size_t bc = B;
-  if (!composed) {
-    const size_t per = (planes * L + L * L + 2 * L) * n * wb;
-    bc = std::min(B, std::max<size_t>(k.t->ks_ws_bytes / per, 1));
-  }
+  const size_t bc = composed ? B : chunk_polys(k.t, planes * L + L * L + 2 * L, B);
   const size_t dm_bytes = L * n_terms * n * wb;
   const size_t one_bytes = composed ? 0 : L * n * wb;
   const size_t used = planes - (!composed && bc == B ? 2 : 0);
-  const size_t need =
-      dm_bytes + one_bytes + used * L * bc * n * wb + (composed ? 0 : ks_scratch_words(k.t, L, bc) * wb);
+  const size_t need = dm_bytes + one_bytes + used * L * bc * n * wb + gadget_ws_words(k.t, L, L, bc) * wb;
   CallWs ws(out0);
   if (int rc = ws.get(std::max<size_t>(need, 16))) return rc;
   // the plaintexts in Montgomery form (m^ 2^w mod q), once per call: the inner
