@@ -92,7 +92,8 @@ int rnt_device_count(int* n);
  * "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd",
  * "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
  * "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown",
- * "moddown_auto", "moddown_rescale", "lincomb", "dot_tensor"), the launch
+ * "moddown_auto", "moddown_rescale", "lincomb", "dot_tensor", "mod_raise",
+ * "mul_monomial", "moddown_rescale_affine"), the launch
  * count and summed device milliseconds since enabling. */
 int rnt_profile_enable(const rnt_ctx* ctx, int enable);
 int rnt_profile_read(const rnt_ctx* ctx, const char* kernel, uint64_t* launches,
@@ -530,7 +531,8 @@ int rnt_ct_mul_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, con
  * (rnt_keyswitch_hybrid, rnt_ct_rotate_hybrid, rnt_ct_mul_relin_hybrid,
  * rnt_ct_rotate_hybrid_hoisted, rnt_ct_linear_bsgs_hybrid,
  * rnt_ct_mul_relin_rescale_hybrid, rnt_ct_linear_bsgs_hybrid_rescale,
- * rnt_ct_dot_relin_hybrid, rnt_ct_dot_relin_rescale_hybrid), and the
+ * rnt_ct_dot_relin_hybrid, rnt_ct_dot_relin_rescale_hybrid) and of
+ * rnt_ct_mul_relin_rescale_affine_hybrid, which shares the multiply's body, and the
  * call is then, word for word, the same call with the restricted key on a
  * root context over the view's moduli.  Both halves (and both sets of a BSGS
  * call) must be views on the SAME level-context handle; a view at level == L
@@ -652,6 +654,34 @@ int rnt_ct_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0,
 int rnt_ct_mul_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
                                     const rnt_buf* c0p, const rnt_buf* c1p,
                                     const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha);
+/* The fused multiply-add on a hybrid key (DESIGN.md "Fused multiply-add and
+ * EvalMod").  With (r0, r1) the result of rnt_ct_mul_relin_rescale_hybrid on
+ * the same inputs,
+ *   out0 = w r0 + u z0 + bias X^0      out1 = w r1 + u z1
+ * exactly mod every q_t, canonical, coefficient domain: DEFINED as that call
+ * followed by rnt_ct_lincomb on [r, z] with weights (w, u) and bias `bias`,
+ * word for word.  The affine step is the epilogue of the two kernels that
+ * close the multiply (profile name "moddown_rescale_affine"): the launch count
+ * is the plain call's, r is never written and w, u, bias travel by value -- no
+ * host array is copied, so unlike rnt_ct_lincomb the call can be recorded.
+ * z0, z1: both NULL (u is ignored) or both given, B polys on the outputs'
+ * context, coefficient domain; z0 == out0 together with z1 == out1 is allowed
+ * (accumulation in place).  w, u, bias are signed integers, reduced mod q_t
+ * by the kernel (a negative one as q_t - |.| mod q_t).
+ * Errors: every rule and status of rnt_ct_mul_relin_rescale_hybrid (key level
+ * views in the key positions included), then |w| >= 2^31, |bias| >= 2^62, an
+ * output that aliases an input, only one of z0 / z1 given, |u| >= 2^31 (with
+ * addends), an addend of another batch size, an addend that overlaps an
+ * output other than z0 == out0 with z1 == out1 -> RNT_ERR_BAD_ARGUMENT; an
+ * addend that is a key level view -> RNT_ERR_UNSUPPORTED; on another context
+ * than the outputs' -> RNT_ERR_BASIS_MISMATCH; in the NTT domain ->
+ * RNT_ERR_DOMAIN_MISMATCH.  A refused call leaves its outputs untouched.
+ * Recordable after one plain run of the (E, Lv, alpha) triple. */
+int rnt_ct_mul_relin_rescale_affine_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                           const rnt_buf* c0p, const rnt_buf* c1p,
+                                           const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha,
+                                           int64_t w, const rnt_buf* z0, const rnt_buf* z1, int64_t u,
+                                           int64_t bias);
 /* rnt_ct_linear_bsgs_hybrid followed by rnt_ct_rescale, word for word: the same
  * arguments, the outputs as above (B polys on one shared drop_last(1) of C, so
  * none aliases an input).  With a nonzero giant step the two closing ModDowns

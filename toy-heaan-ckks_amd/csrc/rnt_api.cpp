@@ -98,7 +98,8 @@ const char* const kKernelNames[rnt::K_COUNT] = {
     "automorphism", "ks_decompose", "ks_rows", "tensor_rows", "import", "export", "crt",
     "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
     "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto",
-    "moddown_rescale", "lincomb", "dot_tensor", "mod_raise", "mul_monomial"};
+    "moddown_rescale", "lincomb", "dot_tensor", "mod_raise", "mul_monomial",
+    "moddown_rescale_affine"};
 
 // A profiling call failed: clear the runtime's slot, keep the first failure
 // in the profiler, and stop profiling (rnt_profile_read reports it).
@@ -3299,9 +3300,18 @@ int hybrid_products(const HybridPlan& pl, size_t c, const char* D, char* A0, cha
 // ModDown(A0) (+ add0), out1 = ModDown(A1) (+ add1) at limb stride out_ls, the
 // optional coefficient-domain addends at add_ls; with `rescale` the results
 // are rescaled by their last limb on the way out (k_moddown_rescale, Lv - 1
-// output limbs).
+// output limbs).  `af` (rescale alone): the affine epilogue of that kernel,
+// out = w r + u z (+ bias on component 0) with r the rescaled result and z0 /
+// z1 the chunk's addends at limb stride z_ls (both or neither; z may be out).
+struct HybridAffine {
+  bool on = false;
+  int64_t w = 1, u = 0, bias = 0;
+  const void *z0 = nullptr, *z1 = nullptr;
+  uint64_t z_ls = 0;
+};
 int hybrid_lower(const HybridPlan& pl, size_t c, char* A0, char* A1, void* out0, void* out1, uint64_t out_ls,
-                 const void* add0, const void* add1, uint64_t add_ls, bool rescale) {
+                 const void* add0, const void* add1, uint64_t add_ls, bool rescale,
+                 const HybridAffine& af = HybridAffine{}) {
   const rnt::Tables* tc = pl.C->t.get();
   const rnt::Launch k = hybrid_launch(pl, c);
   const uint64_t cls = (uint64_t)c * tc->n;
@@ -3311,7 +3321,17 @@ int hybrid_lower(const HybridPlan& pl, size_t c, char* A0, char* A1, void* out0,
   void* out[2] = {out0, out1};
   const void* add[2] = {add0, add1};
   for (int o = 0; o < 2; ++o) {
-    if (rescale) {
+    if (rescale && af.on) {
+      rnt::MdAffine ma;
+      ma.on = true;
+      ma.w = af.w, ma.u = af.u, ma.bias = o == 0 ? af.bias : 0;  // the bias is component 0's
+      ma.z = o == 0 ? af.z0 : af.z1, ma.z_ls = af.z_ls;
+      LAUNCH_ON(tc, k.s, rnt::K_MODDOWN_RESCALE_AFFINE,
+                rnt::launch_moddown_rescale(k, out[o], out_ls, A[o], cls, add[o], add_ls,
+                                            rnt::resc_inv_row(tc, pl.Lv - 1, 0), rnt::resc_inv_row(tc, pl.Lv - 1, 1),
+                                            pl.hc, ma),
+                "ModDown, rescale and affine step");
+    } else if (rescale) {
       LAUNCH_ON(tc, k.s, rnt::K_MODDOWN_RESCALE,
                 rnt::launch_moddown_rescale(k, out[o], out_ls, A[o], cls, add[o], add_ls,
                                             rnt::resc_inv_row(tc, pl.Lv - 1, 0), rnt::resc_inv_row(tc, pl.Lv - 1, 1),
@@ -3331,12 +3351,12 @@ int hybrid_lower(const HybridPlan& pl, size_t c, char* A0, char* A1, void* out0,
 int hybrid_chunk_run(const HybridPlan& pl, size_t c, const HybridWs& ws, const void* x, uint64_t x_ls,
                      const rnt_buf* key_a, const rnt_buf* key_b, void* out0, void* out1, uint64_t out_ls,
                      const void* add0, const void* add1, uint64_t add_ls, bool rescale = false,
-                     bool seeded = false) {
+                     bool seeded = false, const HybridAffine& af = HybridAffine{}) {
   if (int rc = hybrid_raise(pl, c, ws.D, x, x_ls)) return rc;
   if (int rc = hybrid_products(pl, c, ws.D, ws.A0, ws.A1, key_a->data, key_b->data, limb_stride(key_a),
                                seeded ? HybridMac::seeded : HybridMac::set))
     return rc;
-  return hybrid_lower(pl, c, ws.A0, ws.A1, out0, out1, out_ls, add0, add1, add_ls, rescale);
+  return hybrid_lower(pl, c, ws.A0, ws.A1, out0, out1, out_ls, add0, add1, add_ls, rescale, af);
 }
 
 // INV(d^ 2^-w) 2^w = d, canonical: a tensor output (kc.B polys at limb stride
@@ -3353,13 +3373,13 @@ int seeds_to_coeff(const rnt::Launch& kc, char* Dx, uint64_t ls) {
 // else D0, D1 go back to the coefficient domain and are ModDown's addends.
 int hybrid_relin_chunk(const HybridPlan& pl, const rnt::Launch& kc, const HybridWs& ws, bool rescale, bool seeded,
                        char* D0, char* D1, const char* D2, const rnt_buf* key_a, const rnt_buf* key_b, void* out0,
-                       void* out1, uint64_t out_ls) {
+                       void* out1, uint64_t out_ls, const HybridAffine& af = HybridAffine{}) {
   const uint64_t cls = (uint64_t)kc.B * kc.t->n;
   if (!seeded)
     for (char* Dx : {D0, D1})
       if (int rc = seeds_to_coeff(kc, Dx, cls)) return rc;
   return hybrid_chunk_run(pl, kc.B, ws, D2, cls, key_a, key_b, out0, out1, out_ls, seeded ? nullptr : D0,
-                          seeded ? nullptr : D1, cls, rescale, seeded);
+                          seeded ? nullptr : D1, cls, rescale, seeded, af);
 }
 
 // Whether an NTT-domain plane of the ciphertext context's transforms is, on a
@@ -3577,9 +3597,46 @@ extern "C" int rnt_ct_rotate_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf*
 // The two calls validate in their own orders: the plain one compares all six
 // operands with out0 before it looks at the key; the rescaling one compares
 // the inputs with c0, then checks the key and the domain, and its outputs last.
+//
+// CtAffine (the rescaling call alone, rnt_ct_mul_relin_rescale_affine_hybrid):
+// out0 = w r0 + u z0 + bias X^0, out1 = w r1 + u z1 in the epilogue of the two
+// closing k_moddown_rescale launches.  Its rules are checked after the
+// multiply's own, before any device work.
+struct CtAffine {
+  int64_t w, u, bias;
+  const rnt_buf *z0, *z1;
+};
+static int ct_affine_check(const char* name, const CtAffine& a, const rnt_buf* out0, const rnt_buf* out1,
+                           const rnt_buf* const (&in)[4]) {
+  constexpr int64_t kW = (int64_t)1 << 31, kB = (int64_t)1 << 62;
+  if (a.w <= -kW || a.w >= kW) return fail(RNT_ERR_BAD_ARGUMENT, "%s: |w| must be below 2^31", name);
+  if (a.bias <= -kB || a.bias >= kB) return fail(RNT_ERR_BAD_ARGUMENT, "%s: |bias| must be below 2^62", name);
+  for (const rnt_buf* b : in)
+    if (out0 == b || out1 == b || out0->data == b->data || out1->data == b->data)
+      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output aliases an input", name);
+  if ((a.z0 == nullptr) != (a.z1 == nullptr))
+    return fail(RNT_ERR_BAD_ARGUMENT, "%s: z0 and z1 are both given or both null", name);
+  if (a.z0 == nullptr) return RNT_OK;
+  if (a.u <= -kW || a.u >= kW) return fail(RNT_ERR_BAD_ARGUMENT, "%s: |u| must be below 2^31", name);
+  for (const rnt_buf* z : {a.z0, a.z1}) {
+    if (int rc = check_buf(z, name)) return rc;
+    if (z->ctx != out0->ctx) return fail(RNT_ERR_BASIS_MISMATCH, "%s: an addend's basis is not the outputs'", name);
+    if (z->n_polys != out0->n_polys)
+      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an addend of %zu polys for a batch of %zu", name, z->n_polys,
+                  out0->n_polys);
+    if (z->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: addends must be in coefficient domain", name);
+  }
+  // in place: z0 is out0 together with z1 is out1; every other overlap of an addend and an output is refused
+  const bool same0 = a.z0 == out0 || a.z0->data == out0->data, same1 = a.z1 == out1 || a.z1->data == out1->data;
+  if (same0 != same1 || a.z0 == out1 || a.z0->data == out1->data || a.z1 == out0 || a.z1->data == out0->data)
+    return fail(RNT_ERR_BAD_ARGUMENT, "%s: an addend aliases an output (only z0 == out0 with z1 == out1 is allowed)",
+                name);
+  return RNT_OK;
+}
+
 static int ct_mul_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0,
                               const rnt_buf* c1, const rnt_buf* c0p, const rnt_buf* c1p, const rnt_buf* key_a,
-                              const rnt_buf* key_b, size_t alpha) {
+                              const rnt_buf* key_b, size_t alpha, const CtAffine* aff = nullptr) {
   const rnt_buf* all[6] = {out0, out1, c0, c1, c0p, c1p};
   for (const rnt_buf* b : all)
     if (int rc = check_buf(b, name)) return rc;
@@ -3592,6 +3649,10 @@ static int ct_mul_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt
     return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: inputs must be in coefficient domain", name);
   if (rescale)
     if (int rc = rescaled_outputs_check(name, out0, out1, c0, c0->n_polys)) return rc;
+  if (aff) {
+    const rnt_buf* const in[4] = {c0, c1, c0p, c1p};
+    if (int rc = ct_affine_check(name, *aff, out0, out1, in)) return rc;
+  }
   if (int rc = set_device(c0->ctx)) return rc;
   if (int rc = hybrid_prepare(&pl)) return rc;
   rnt::Launch k = launch_for(c0);
@@ -3621,8 +3682,18 @@ static int ct_mul_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt
     char* D0 = seeded ? hw.A0 : D2 + chunk_words * wb;
     char* D1 = seeded ? hw.A1 : D0 + chunk_words * wb;
     if (int rc = tensor(kc, T, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls)) return rc;
+    HybridAffine ha;
+    if (aff) {
+      ha.on = true;
+      ha.w = aff->w, ha.bias = aff->bias;
+      if (aff->z0) {  // the chunk's polys of the addends
+        ha.u = aff->u;
+        ha.z0 = off(aff->z0), ha.z1 = off(aff->z1);
+        ha.z_ls = limb_stride(aff->z0);
+      }
+    }
     if (int rc = hybrid_relin_chunk(pl, kc, hw, rescale, seeded, D0, D1, D2, key_a, key_b, (char*)out0->data + po,
-                                    (char*)out1->data + po, out_ls))
+                                    (char*)out1->data + po, out_ls, ha))
       return rc;
   }
   out0->in_ntt = out1->in_ntt = 0;
@@ -3640,6 +3711,16 @@ extern "C" int rnt_ct_mul_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, con
                                                const rnt_buf* key_b, size_t alpha) {
   return ct_mul_hybrid_body("rnt_ct_mul_relin_rescale_hybrid", true, out0, out1, c0, c1, c0p, c1p, key_a, key_b,
                             alpha);
+}
+
+extern "C" int rnt_ct_mul_relin_rescale_affine_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0,
+                                                      const rnt_buf* c1, const rnt_buf* c0p, const rnt_buf* c1p,
+                                                      const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha,
+                                                      int64_t w, const rnt_buf* z0, const rnt_buf* z1, int64_t u,
+                                                      int64_t bias) {
+  const CtAffine aff{w, u, bias, z0, z1};
+  return ct_mul_hybrid_body("rnt_ct_mul_relin_rescale_affine_hybrid", true, out0, out1, c0, c1, c0p, c1p, key_a,
+                            key_b, alpha, &aff);
 }
 
 // ---------------------------------------------------------------------------

@@ -183,7 +183,8 @@ enum KernelId {
   K_AUTOMORPHISM, K_KS_DECOMPOSE, K_KS_ROWS, K_TENSOR_ROWS, K_IMPORT, K_EXPORT, K_CRT,
   K_SFFT, K_SAMPLE, K_COPY, K_PLANE_FUSED, K_MF_NTT_FWD, K_MF_NTT_INV, K_WHOLE_FWD, K_WHOLE_INV, K_WHOLE_MUL,
   K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_MODUP, K_MODDOWN,
-  K_MODDOWN_AUTO, K_MODDOWN_RESCALE, K_LINCOMB, K_DOT_TENSOR, K_MOD_RAISE, K_MUL_MONOMIAL, K_COUNT
+  K_MODDOWN_AUTO, K_MODDOWN_RESCALE, K_LINCOMB, K_DOT_TENSOR, K_MOD_RAISE, K_MUL_MONOMIAL,
+  K_MODDOWN_RESCALE_AFFINE, K_COUNT
 };
 
 struct Prof {
@@ -463,9 +464,19 @@ hipError_t launch_moddown_auto(const Launch& k, void* out, uint64_t out_ls, cons
 // rinv[j] for j < Lv - 1, r = ModDown(A) (+ add); rinv / rinvp are the row
 // resc_inv_row(ciphertext tables, Lv - 1, 0 / 1) launch_rescale reads.  The
 // words are those of launch_moddown followed by launch_rescale.  Lv >= 2.
+// MdAffine (on): the kernel's affine epilogue, out_j = w o_j + u z_j (+ bias on
+// coefficient 0 of every poly) mod q_j with o the rescaled result; z (optional,
+// coefficient domain, Lv - 1 limbs at limb stride z_ls) may be `out`.  The
+// three integers go to the kernel by value: no table, no host copy.
+struct MdAffine {
+  bool on = false;
+  int64_t w = 1, u = 0, bias = 0;
+  const void* z = nullptr;
+  uint64_t z_ls = 0;
+};
 hipError_t launch_moddown_rescale(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
                                   const void* add, uint64_t add_ls, const void* rinv, const void* rinvp,
-                                  const HybridConsts& hc);
+                                  const HybridConsts& hc, const MdAffine& af = MdAffine{});
 // launch_lincomb (k_lincomb): n_out scalar linear combinations of n_in
 // ciphertexts, both components in one launch.  k.L = Lv limbs of the inputs,
 // k.B ciphertexts; x0 / x1 hold n_in k.B polys a limb at limb stride in_ls

@@ -2305,13 +2305,51 @@ __device__ __forceinline__ void moddown_limb(W (&r)[V], uint32_t j, const W (&z)
 // rescale table k_rescale reads: the words of the two kernels in sequence.
 // blockIdx.y takes a run of jper of the Lv - 1 output limbs; every run
 // recomputes z_k and r_last (K + 1 planes read again, hits of the cache).
-template <class W, bool VEC, int KMAX>
+//
+// AFFINE (rnt_ct_mul_relin_rescale_affine_hybrid): the output word o_j of a
+// lane is held back and
+//   out_j = w o_j + u z_j (+ b on coefficient 0 of a poly)  mod q_j,
+// canonical, is stored in its place -- z the addend at limb stride z_ls (null:
+// no second term), w, u, b signed integers by value.  Their residues mod q_j
+// are formed per limb from LimbConst alone (affine_residue: Shoup products by
+// 1, no division; uniform, so once a wave) and w, u go to Montgomery form
+// (times 2^w mod q_j, LimbConst::rmod), so a word costs two Montgomery
+// products and an addition and no table is read: nothing is copied from the
+// host.  The bias belongs to element 0 of the lane whose position is a
+// multiple of N (k_lincomb's rule; V divides N where VEC); the caller passes
+// b = 0 for component 1.  A lane loads z_j at its position before it stores
+// out_j there and no other lane touches that position, so z may be out (the
+// AFFINE instantiations have no __restrict__ on out).
+template <class W>
+struct MdAffineArg {
+  const W* z;
+  uint64_t z_ls;
+  int64_t w, u, b;
+  uint32_t nmask;  // N - 1
+};
+
+// |c| < 2^63 mod q, canonical and without a division: Shoup products by 1.
+template <class W>
+__device__ __forceinline__ W affine_residue(int64_t c, const LimbConst<W>& lc) {
+  const uint64_t m = c < 0 ? (uint64_t)(-(c + 1)) + 1u : (uint64_t)c;
+  W r;
+  if constexpr (sizeof(W) == 4) r = mag_mod<W>(m, lc);
+  else r = shoup_mul<W>((W)m, (W)1, lc.one_p, lc.q);
+  return c < 0 && r != 0 ? (W)(lc.q - r) : r;
+}
+
+template <class W, bool AFFINE>
+struct MdOut { using type = W* __restrict__; };
+template <class W>
+struct MdOut<W, true> { using type = W*; };
+
+template <class W, bool VEC, int KMAX, bool AFFINE = false>
 __global__ void __launch_bounds__(256)
-k_moddown_rescale(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A, uint64_t a_ls, const W* add,
-                  uint64_t add_ls, TabPtrs<W> tp, const W* __restrict__ pinv, const W* __restrict__ pinvp,
+k_moddown_rescale(typename MdOut<W, AFFINE>::type out, uint64_t out_ls, const W* __restrict__ A, uint64_t a_ls,
+                  const W* add, uint64_t add_ls, TabPtrs<W> tp, const W* __restrict__ pinv, const W* __restrict__ pinvp,
                   const W* __restrict__ pq, const W* __restrict__ pqp, const W* __restrict__ Pinv,
                   const W* __restrict__ Pinvp, const W* __restrict__ rinv, const W* __restrict__ rinvp,
-                  uint64_t limb_words, uint32_t Lv, uint32_t K, uint32_t jper, LimbMap lm) {
+                  uint64_t limb_words, uint32_t Lv, uint32_t K, uint32_t jper, LimbMap lm, MdAffineArg<W> af) {
   constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
   const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
   if (i >= limb_words) return;
@@ -2343,6 +2381,19 @@ k_moddown_rescale(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ A,
     for (int v = 0; v < V; ++v) {
       const W cl = shoup_mul<W>(rl[v], (W)1, lc.one_p, lc.q);  // canonical r_last mod q_j, as k_rescale's
       o[v] = shoup_mul<W>(sub_mod<W>(r[v], cl, lc.q), inv, invp, lc.q);
+    }
+    if constexpr (AFFINE) {
+      const W wm = shoup_mul<W>(affine_residue<W>(af.w, lc), lc.rmod, lc.rmod_p, lc.q);  // w 2^w mod q_j (uniform)
+#pragma unroll
+      for (int v = 0; v < V; ++v) o[v] = mont_mul<W>(o[v], wm, lc.q, lc.qinv);
+      if (af.z != nullptr) {  // (uniform)
+        const W um = shoup_mul<W>(affine_residue<W>(af.u, lc), lc.rmod, lc.rmod_p, lc.q);
+        W zv[V];
+        ld_vec<W, VEC, V>(zv, af.z + (uint64_t)j * af.z_ls + i);
+#pragma unroll
+        for (int v = 0; v < V; ++v) o[v] = add_mod<W>(o[v], mont_mul<W>(zv[v], um, lc.q, lc.qinv), lc.q);
+      }
+      if (((uint32_t)i & af.nmask) == 0) o[0] = add_mod<W>(o[0], affine_residue<W>(af.b, lc), lc.q);
     }
     st_vec<W, VEC, V>(out + (uint64_t)j * out_ls + i, o);
   }
@@ -3323,16 +3374,18 @@ static hipError_t moddown_t(const Launch& k, void* out, uint64_t out_ls, const v
 template <class W>
 static hipError_t moddown_rescale_t(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
                                     const void* add, uint64_t add_ls, const void* rinv, const void* rinvp,
-                                    const HybridConsts& hc) {
+                                    const HybridConsts& hc, const MdAffine& af) {
   const uint64_t N = 1ull << k.t->log_n;
   const uint64_t limb_words = (uint64_t)k.B * N;
   if (hc.Lv < 2 || hc.K == 0 || k.L != (size_t)hc.Lv + hc.K || !limb_map_ok(k) || out_ls < limb_words ||
-      a_ls < limb_words || (add && add_ls < limb_words) || !rinv || !rinvp)
+      a_ls < limb_words || (add && add_ls < limb_words) || !rinv || !rinvp || (af.z && af.z_ls < limb_words))
     return hipErrorInvalidValue;
   if (limb_words == 0) return hipSuccess;
   constexpr int V = 16 / (int)sizeof(W);
   const bool vec = N % V == 0 && out_ls % V == 0 && a_ls % V == 0 && (!add || add_ls % V == 0) &&
-                   ((uintptr_t)out | (uintptr_t)A | (uintptr_t)add) % 16 == 0;
+                   (!af.z || af.z_ls % V == 0) &&
+                   ((uintptr_t)out | (uintptr_t)A | (uintptr_t)add | (uintptr_t)af.z) % 16 == 0;
+  const MdAffineArg<W> aa{(const W*)af.z, af.z_ls, af.w, af.u, af.bias, (uint32_t)(N - 1)};
   const uint64_t per = vec ? limb_words / V : limb_words;
   const uint64_t bx = (per + 255) / 256;
   if (bx > 0x7fffffffull) return hipErrorInvalidConfiguration;
@@ -3340,18 +3393,20 @@ static hipError_t moddown_rescale_t(const Launch& k, void* out, uint64_t out_ls,
   const uint64_t runs = std::min<uint64_t>(lo, std::max<uint64_t>(kSplitBlocks / bx, 1));
   const uint32_t jper = (uint32_t)((lo + runs - 1) / runs);
   const dim3 grid((unsigned)bx, (unsigned)((lo + jper - 1) / jper));
-#define RNT_MR(VEC, KMAX)                                                                              \
-  hipLaunchKernelGGL((k_moddown_rescale<W, VEC, KMAX>), grid, dim3(256), 0, k.s, (W*)out, out_ls,       \
+#define RNT_MR(VEC, KMAX, AFF)                                                                         \
+  hipLaunchKernelGGL((k_moddown_rescale<W, VEC, KMAX, AFF>), grid, dim3(256), 0, k.s, (W*)out, out_ls,  \
                      (const W*)A, a_ls, (const W*)add, add_ls, tab_ptrs<W>(k.t), (const W*)hc.pinv,     \
                      (const W*)hc.pinvp, (const W*)hc.pq, (const W*)hc.pqp, (const W*)hc.Pinv,          \
                      (const W*)hc.Pinvp, (const W*)rinv, (const W*)rinvp, limb_words, hc.Lv, hc.K, jper,    \
-                     limb_map(k))
-#define RNT_MR_K(KMAX) do { if (vec) RNT_MR(true, KMAX); else RNT_MR(false, KMAX); } while (0)
+                     limb_map(k), aa)
+#define RNT_MR_V(VEC, KMAX) do { if (af.on) RNT_MR(VEC, KMAX, true); else RNT_MR(VEC, KMAX, false); } while (0)
+#define RNT_MR_K(KMAX) do { if (vec) RNT_MR_V(true, KMAX); else RNT_MR_V(false, KMAX); } while (0)
   if (hc.K <= 4) RNT_MR_K(4);
   else if (hc.K <= 8) RNT_MR_K(8);
   else if (hc.K <= 16) RNT_MR_K(16);
   else RNT_MR_K(0);
 #undef RNT_MR_K
+#undef RNT_MR_V
 #undef RNT_MR
   return hipGetLastError();
 }
@@ -4153,9 +4208,9 @@ hipError_t launch_moddown_auto(const Launch& k, void* out, uint64_t out_ls, cons
 }
 hipError_t launch_moddown_rescale(const Launch& k, void* out, uint64_t out_ls, const void* A, uint64_t a_ls,
                                   const void* add, uint64_t add_ls, const void* rinv, const void* rinvp,
-                                  const HybridConsts& hc) {
-  RNT_WIDE(moddown_rescale_t<uint32_t>(k, out, out_ls, A, a_ls, add, add_ls, rinv, rinvp, hc),
-           moddown_rescale_t<uint64_t>(k, out, out_ls, A, a_ls, add, add_ls, rinv, rinvp, hc));
+                                  const HybridConsts& hc, const MdAffine& af) {
+  RNT_WIDE(moddown_rescale_t<uint32_t>(k, out, out_ls, A, a_ls, add, add_ls, rinv, rinvp, hc, af),
+           moddown_rescale_t<uint64_t>(k, out, out_ls, A, a_ls, add, add_ls, rinv, rinvp, hc, af));
 }
 hipError_t launch_lincomb(const Launch& k, void* out0, void* out1, uint64_t out_ls, const void* x0, const void* x1,
                           uint64_t in_ls, size_t n_in, size_t n_out, const void* w, const void* wp, const void* bias,

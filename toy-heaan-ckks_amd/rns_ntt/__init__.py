@@ -27,7 +27,8 @@ import numpy as np
 from . import _lib
 from ._lib import RnsNttError, check, load
 from .homdft import HomDftPlan, homdft_plan
-from .poly_eval import PolyEvalPlan, poly_eval_plan
+from .poly_eval import PolyEvalPlan, poly_eval_plan, poly_eval_plan_fused
+from .evalmod import EvalModPlan, evalmod_plan
 
 __all__ = [
     "device_count",
@@ -44,6 +45,9 @@ __all__ = [
     "linear_transform_hybrid",
     "linear_transform_bsgs_hybrid",
     "mul_ciphertexts_hybrid_rescale",
+    "mul_ciphertexts_hybrid_rescale_affine",
+    "evalmod_plan",
+    "EvalModPlan",
     "linear_transform_bsgs_hybrid_rescale",
     "dot_ciphertexts_hybrid",
     "conjugate_hybrid",
@@ -69,6 +73,7 @@ __all__ = [
     "rescale_ciphertext",
     "ct_lincomb",
     "poly_eval_plan",
+    "poly_eval_plan_fused",
     "PolyEvalPlan",
     "Plaintext",
     "CkksEncoder",
@@ -1272,6 +1277,43 @@ def mul_ciphertexts_hybrid_rescale(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsHyb
                                                  ct2.c0.handle, ct2.c1.handle, rlk.a.handle, rlk.b.handle,
                                                  rlk.alpha))
     return Ciphertext(out0, out1, ct1.logp + ct2.logp - bits_dropped, ct1.logq - bits_dropped)
+
+
+def mul_ciphertexts_hybrid_rescale_affine(ct1: Ciphertext, ct2: Ciphertext, rlk: RnsHybridKey, weight: int = 1,
+                                         addend: Optional[Ciphertext] = None, addend_weight: int = 1, bias: int = 0,
+                                         out_basis: Optional[RnsBasis] = None) -> Ciphertext:
+    """``weight * (ct1 * ct2) + addend_weight * addend + bias`` with the
+    product relinearised and rescaled, as one op
+    (rnt_ct_mul_relin_rescale_affine_hybrid): word for word
+    :func:`mul_ciphertexts_hybrid_rescale` followed by an un-rescaled
+    :func:`ct_lincomb` on the product and the addend, the affine step in the
+    epilogue of the kernels that close the multiply -- no launch and no pass
+    over the ciphertext of its own, and nothing copied from the host, so the
+    call can be recorded.  ``weight``, ``addend_weight`` (below 2^31 in
+    magnitude) and ``bias`` (below 2^62) are signed Python ints; the bias is
+    the constant in every slot at the result's scale (it is added after the
+    rescale), and the weights do not change logp.  ``addend`` lives at the result's level, on the result's basis
+    object (``out_basis``, by default the addend's own), with the result's logp
+    and logq: anything else raises ValueError.  logp / logq are the
+    multiply's."""
+    _require_class(rlk, RnsHybridKey, "mul_ciphertexts_hybrid_rescale_affine")
+    assert ct1.logq == ct2.logq, "logq mismatch in hybrid multiplication"
+    rlk = _at_ct_level(rlk, ct1.c0.basis)
+    bits_dropped = ct1.c0.basis.moduli()[-1].bit_length()
+    logp, logq = ct1.logp + ct2.logp - bits_dropped, ct1.logq - bits_dropped
+    if addend is not None:
+        if addend.logp != logp or addend.logq != logq:
+            raise ValueError(f"mul_ciphertexts_hybrid_rescale_affine: the addend's (logp, logq) = ({addend.logp}, "
+                             f"{addend.logq}) is not the result's ({logp}, {logq})")
+        if out_basis is None:
+            out_basis = addend.c0.basis
+    new_basis = out_basis if out_basis is not None else ct1.c0.basis.drop_last(1)
+    out0, out1 = ct1.c0._like(new_basis), ct1.c0._like(new_basis)
+    check(load().rnt_ct_mul_relin_rescale_affine_hybrid(
+        out0.handle, out1.handle, ct1.c0.handle, ct1.c1.handle, ct2.c0.handle, ct2.c1.handle, rlk.a.handle,
+        rlk.b.handle, rlk.alpha, int(weight), None if addend is None else addend.c0.handle,
+        None if addend is None else addend.c1.handle, int(addend_weight), int(bias)))
+    return Ciphertext(out0, out1, logp, logq)
 
 
 def linear_transform_bsgs_hybrid_rescale(ct: Ciphertext, diag: RnsPoly, baby_keyset: RnsHybridKeySet,

@@ -162,6 +162,8 @@ SIGNATURES = {
     "rnt_ct_linear_bsgs_hybrid": (c_int, [_P, _P, _P, _P, POINTER(c_int32), c_size_t, POINTER(c_int32), c_size_t,
                                           _P, _P, _P, _P, _P, c_size_t]),
     "rnt_ct_mul_relin_rescale_hybrid": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_size_t]),
+    "rnt_ct_mul_relin_rescale_affine_hybrid": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_size_t, c_int64, _P, _P,
+                                                       c_int64, c_int64]),
     "rnt_ct_linear_bsgs_hybrid_rescale": (c_int, [_P, _P, _P, _P, POINTER(c_int32), c_size_t, POINTER(c_int32),
                                                   c_size_t, _P, _P, _P, _P, _P, c_size_t]),
     "rnt_copy_polys": (c_int, [_P, c_size_t, _P, c_size_t, c_size_t]),
@@ -183,7 +185,7 @@ PROFILE_NAMES = (
     "ks_rows", "tensor_rows", "import", "export", "crt", "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd",
     "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul", "bsgs_mac",
     "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto", "moddown_rescale", "lincomb", "dot_tensor",
-    "mod_raise", "mul_monomial",
+    "mod_raise", "mul_monomial", "moddown_rescale_affine",
 )
 
 _lib = None

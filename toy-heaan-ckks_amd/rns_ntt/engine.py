@@ -29,7 +29,8 @@ from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadge
                split_real_imag_hybrid,
                linear_transform_bsgs_hoisted, linear_transform_bsgs_hybrid, linear_transform_bsgs_hybrid_rescale,
                linear_transform_hybrid, load, mul_ciphertexts_gadget, mul_ciphertexts_hybrid,
-               mul_ciphertexts_hybrid_rescale, poly_eval_plan, rescale_ciphertext, rotate_ciphertext,
+               mul_ciphertexts_hybrid_rescale, mul_ciphertexts_hybrid_rescale_affine, poly_eval_plan,
+               poly_eval_plan_fused, rescale_ciphertext, rotate_ciphertext,
                rotate_ciphertext_hoisted, rotate_ciphertext_hybrid, rotate_ciphertext_hybrid_hoisted)
 
 
@@ -51,6 +52,19 @@ class PublicKey:
 
     b: RnsPoly
     a: RnsPoly
+
+
+def _check_levels(name: str, ct: Ciphertext, depth: int, what: str) -> None:
+    """A circuit of ``depth`` levels at the scale 2^logp: enough limbs, and
+    every consumed prime of logp bits."""
+    p = int(ct.logp)
+    mods = ct.c0.basis.moduli()
+    if len(mods) - depth < 1:
+        raise ValueError(f"{name}: {what} consumes {depth} levels, the ciphertext has {len(mods)} limbs")
+    for q in mods[len(mods) - depth:]:
+        if q.bit_length() != p:
+            raise ValueError(f"{name}: the consumed prime {q} has {q.bit_length()} bits, the ciphertext's logp "
+                             f"is {p}")
 
 
 class CkksEngine:
@@ -395,17 +409,31 @@ class CkksEngine:
         the scale stays 2^logp (up to the drift of q != 2^logp, which the
         integer logp does not track); the result is ``plan.depth`` levels
         down."""
+        plan = poly_eval_plan(coeffs, basis, int(ct.logp))
+        _check_levels("evaluate_polynomial_hybrid", ct, plan.depth, f"degree {plan.degree}")
+        return CkksEngine._run_poly_plan(ct, plan, rlk)[0]
+
+    @staticmethod
+    def evaluate_polynomial_hybrid_fused(ct: Ciphertext, coeffs, rlk: RnsHybridKey,
+                                         basis: str = "monomial") -> Ciphertext:
+        """:meth:`evaluate_polynomial_hybrid` on ``poly_eval_plan_fused``: the
+        same arguments, rules, depth and leaves, with every affine step after
+        a product riding in the product's own call
+        (``mul_ciphertexts_hybrid_rescale_affine``) -- the same values from
+        fewer launches and less traffic; in the Chebyshev basis the very words
+        of the unfused evaluation."""
+        plan = poly_eval_plan_fused(coeffs, basis, int(ct.logp))
+        _check_levels("evaluate_polynomial_hybrid_fused", ct, plan.depth, f"degree {plan.degree}")
+        return CkksEngine._run_poly_plan(ct, plan, rlk)[0]
+
+    @staticmethod
+    def _run_poly_plan(ct: Ciphertext, plan, rlk: RnsHybridKey):
+        """The ops of a ``PolyEvalPlan`` on the device: the result and the one
+        basis object per level it was computed on (a later call that joins the
+        result with another operand needs the same object)."""
         p = int(ct.logp)
-        plan = poly_eval_plan(coeffs, basis, p)
         top = ct.c0.basis
         mods = top.moduli()
-        if len(mods) - plan.depth < 1:
-            raise ValueError(f"evaluate_polynomial_hybrid: degree {plan.degree} consumes {plan.depth} levels, the "
-                             f"ciphertext has {len(mods)} limbs")
-        for q in mods[len(mods) - plan.depth:]:
-            if q.bit_length() != p:
-                raise ValueError(f"evaluate_polynomial_hybrid: the consumed prime {q} has {q.bit_length()} bits, "
-                                 f"the ciphertext's logp is {p}")
         B = ct.c0.n_polys
         level_basis = {0: top}  # one basis object per level: operands of a call share it
 
@@ -432,6 +460,10 @@ class CkksEngine:
             elif op[0] == "add":
                 _, dst, a, b = op
                 v[dst] = CkksEngine.add_ciphertexts(v[a], v[b])
+            elif op[0] == "fma":
+                _, dst, a, b, w, z, u, bias, _ = op
+                v[dst] = mul_ciphertexts_hybrid_rescale_affine(v[a], v[b], rlk, w, None if z is None else v[z], u,
+                                                               bias, out_basis=lb(plan.levels[dst]))
             else:
                 _, dsts, srcs, weights, bias, rescale, _, _ = op
                 if len(srcs) == 1:
@@ -454,7 +486,28 @@ class CkksEngine:
                     c0.copy_polys(out.c0, 0, j * B, B)
                     c1.copy_polys(out.c1, 0, j * B, B)
                     v[d] = Ciphertext(c0, c1, out.logp, out.logq)
-        return v[plan.result]
+        return v[plan.result], lb
+
+    @staticmethod
+    def eval_mod_hybrid(ct: Ciphertext, plan, rlk: RnsHybridKey) -> Ciphertext:
+        """The homomorphic modular reduction of bootstrapping (EvalMod) on
+        every ciphertext of the batch -- the real and imaginary halves of a
+        split ciphertext go through as one batch of 2 B.  ``plan`` is an
+        ``evalmod_plan(K, degree, r, ct.logp)``: real slots u = (I + eps) / K
+        with an integer |I| < K come back as sin(2 pi eps) / (2 pi), close to
+        eps.  The fused Chebyshev evaluation of the scaled cosine, then r
+        double angles y <- 2 y^2 - a^(2^(j+1)), each ONE
+        ``mul_ciphertexts_hybrid_rescale_affine``.  The result is
+        ``plan.depth`` levels down with logp unchanged; every consumed prime
+        must have ``ct.logp`` bits, as ``evaluate_polynomial_hybrid`` demands."""
+        if int(ct.logp) != plan.logp:
+            raise ValueError(f"eval_mod_hybrid: the plan was made for logp {plan.logp}, the ciphertext's is {ct.logp}")
+        _check_levels("eval_mod_hybrid", ct, plan.depth, f"EvalMod (K = {plan.K}, degree {plan.degree}, "
+                                                         f"{plan.double_angles} double angles)")
+        y, lb = CkksEngine._run_poly_plan(ct, plan.poly, rlk)
+        for j, c in enumerate(plan.constants):
+            y = mul_ciphertexts_hybrid_rescale_affine(y, y, rlk, 2, None, 0, -c, out_basis=lb(plan.poly.depth + j + 1))
+        return y
 
     # -- encryption (engine.rs:84-127) -----------------------------------------
     def encrypt(self, plaintext, pk: PublicKey, rng, logp: int = 0,

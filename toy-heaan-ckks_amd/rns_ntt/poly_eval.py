@@ -16,6 +16,11 @@ an operand is never used above the level the plan states.
                                     sum_i weights[j][i] srcs[i] + bias[j]; with
                                     ``rescale`` level + 1.  fweights / fbias:
                                     the real numbers the integers stand for.
+    ("fma", dst, a, b, w, z, u, bias, fbias)   (poly_eval_plan_fused alone)
+                                    mul_ciphertexts_hybrid_rescale_affine:
+                                    dst = w a b + u z + bias at level + 1, z
+                                    (or None) at that level already; fbias the
+                                    real number the integer bias stands for.
 
 The schedule.  m = max(2, 2^ceil(log2(d + 1) / 2)) babies Phi_1..Phi_{m-1}, the
 giants g_k = m 2^k <= d.  Phi_n = Phi_a Phi_b with a the largest power of two
@@ -26,6 +31,16 @@ giant <= e, eval(P) = eval(Q) Phi_g + eval(R); every P of degree < m is a leaf,
 and all leaves come from ONE rescaling ct_lincomb of the babies (chunks of 16
 outputs): weight k >= 1 is rint(c_k 2^logp), the bias rint(c_0 2^(2 logp)).
 The depth is at most ceil(log2(d + 1)) + 1 levels.
+
+``poly_eval_plan_fused(coeffs, basis, logp)`` (the same arguments; a function of
+its own, so that ``poly_eval_plan`` is what it was, signature included)
+keeps the schedule, its levels and its leaves and folds every
+affine step that follows a product into the product's own call: a Chebyshev
+power is ONE fma (w = 2, z = T_{a-b} at the output level, u = -1; for T_{2a}
+w = 2 and the bias -2^logp), so no un-rescaled ct_lincomb is left, and a node
+eval(Q) Phi_g + eval(R) is one fma with z = eval(R) dropped to the product's
+level.  Where eval(R) sits deeper than the product the node keeps mul, drop,
+add.  The default plan is today's, op for op.
 """
 from __future__ import annotations
 
@@ -67,6 +82,9 @@ class PolyEvalPlan:
                 v[op[1]] = v[op[2]] * v[op[3]]
             elif op[0] == "add":
                 v[op[1]] = v[op[2]] + v[op[3]]
+            elif op[0] == "fma":
+                _, dst, a, b, w, z, u, _, fbias = op
+                v[dst] = w * (v[a] * v[b]) + (u * v[z] if z is not None else 0.0) + fbias
             else:
                 _, dsts, srcs, _, _, _, fw, fb = op
                 for j, d in enumerate(dsts):
@@ -85,6 +103,16 @@ def _trim(c):
 
 
 def poly_eval_plan(coeffs, basis: str, logp: int) -> PolyEvalPlan:
+    return _build_plan(coeffs, basis, logp, fused=False)
+
+
+def poly_eval_plan_fused(coeffs, basis: str, logp: int) -> PolyEvalPlan:
+    """The same schedule with every affine step that follows a product folded
+    into the product's call (the module docstring's ``fma`` op)."""
+    return _build_plan(coeffs, basis, logp, fused=True)
+
+
+def _build_plan(coeffs, basis: str, logp: int, fused: bool) -> PolyEvalPlan:
     if basis not in ("monomial", "chebyshev"):
         raise ValueError(f"poly_eval_plan: unknown basis {basis!r} (monomial or chebyshev)")
     cheb = basis == "chebyshev"
@@ -133,6 +161,11 @@ def poly_eval_plan(coeffs, basis: str, logp: int) -> PolyEvalPlan:
         name = f"phi{n}"
         if not cheb:
             ops.append(("mul", name, A, Bn))
+        elif fused:
+            if a != b:  # T_n = 2 T_a T_b - T_{a-b}
+                ops.append(("fma", name, A, Bn, 2, at(power[a - b], lv + 1), -1, 0, 0.0))
+            else:  # T_2a = 2 T_a^2 - 1, the constant at the scale 2^logp
+                ops.append(("fma", name, A, Bn, 2, None, 0, -(1 << logp), -1.0))
         else:
             t = fresh("t")
             ops.append(("mul", t, A, Bn))
@@ -194,6 +227,20 @@ def poly_eval_plan(coeffs, basis: str, logp: int) -> PolyEvalPlan:
         _, g, qn, rn = node
         q = emit(qn)
         lv = max(lev[q], lev[power[g]])
+        if fused and rn is not None:
+            r = emit(rn)
+            if lev[r] <= lv + 1:  # eval(R) reaches the product's level: one call
+                t = fresh("t")
+                ops.append(("fma", t, at(q, lv), at(power[g], lv), 1, at(r, lv + 1), 1, 0, 0.0))
+                lev[t] = lv + 1
+                return t
+            t = fresh("t")
+            ops.append(("mul", t, at(q, lv), at(power[g], lv)))
+            lev[t] = lv + 1
+            s = fresh("t")
+            ops.append(("add", s, at(t, lev[r]), r))
+            lev[s] = lev[r]
+            return s
         t = fresh("t")
         ops.append(("mul", t, at(q, lv), at(power[g], lv)))
         lev[t] = lv + 1
