@@ -93,7 +93,7 @@ int rnt_device_count(int* n);
  * "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
  * "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown",
  * "moddown_auto", "moddown_rescale", "lincomb", "dot_tensor", "mod_raise",
- * "mul_monomial", "moddown_rescale_affine"), the launch
+ * "mul_monomial", "moddown_rescale_affine", "plain_mac"), the launch
  * count and summed device milliseconds since enabling. */
 int rnt_profile_enable(const rnt_ctx* ctx, int enable);
 int rnt_profile_read(const rnt_ctx* ctx, const char* kernel, uint64_t* launches,
@@ -779,6 +779,53 @@ int rnt_ct_dot_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, con
 int rnt_ct_dot_relin_rescale_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1,
                                     const rnt_buf* y0, const rnt_buf* y1, size_t n_terms,
                                     const rnt_buf* key_a, const rnt_buf* key_b, size_t alpha);
+
+/* ---- ciphertext x plaintext multiply-accumulate (DESIGN.md "Plaintext
+ * multiply-accumulate") ------------------------------------------------------
+ * sum_i w_i (.) ct_i + b with encoded plaintext vectors w_i and b: a dense layer
+ * over pre-rotated ciphertexts, a slot mask, per-slot coefficients.  No key is
+ * involved.  Two calls: rnt_ct_plain_mac, and rnt_ct_plain_mac_rescale, which
+ * closes the level as well.  x0, x1: n_terms B polys over a context C with Lv limbs,
+ * coefficient domain, term i of ciphertext b at poly i B + b (the layout
+ * rnt_ct_lincomb and rnt_ct_dot_relin_hybrid read and
+ * rnt_ct_rotate_hybrid_hoisted writes).  m: the plaintexts in the NTT domain on
+ * C (as the diag of rnt_ct_linear), either n_terms polys -- plaintext i shared
+ * by every ciphertext of the batch -- or n_terms B polys, term i of ciphertext
+ * b at poly i B + b.  bias: NULL, or 1 poly (shared) or B polys, NTT domain on
+ * C.  With negacyclic products, exact mod every q_t and canonical:
+ *   r0_b = sum_i x0_{i,b} m_{i(,b)} + bias_{(b)}      r1_b = sum_i x1_{i,b} m_{i(,b)}
+ * rnt_ct_plain_mac writes (r0, r1): B polys over C, coefficient domain.  These
+ * ARE the words of the coefficient-domain composition: rnt_mul of each term
+ * with the plaintext taken back to coefficients (rnt_ntt_inv), rnt_add over the
+ * terms and the bias.  Any n_terms >= 1 is valid: the terms are transformed and
+ * summed in groups, a batch in chunks within RNT_KS_WS_MB of workspace; two
+ * inverse transforms a chunk whatever n_terms is.  The plaintexts are read
+ * where they lie; the inputs are never written.  No host array is read: both
+ * calls can be recorded after one plain run.
+ * Errors (a refused call leaves its outputs untouched):
+ *   n_terms == 0                                           RNT_ERR_BAD_ARGUMENT
+ *   x0 / x1 poly counts that differ or are no multiple
+ *     of n_terms                                           RNT_ERR_BAD_ARGUMENT
+ *   m of neither n_terms nor n_terms B polys               RNT_ERR_BAD_ARGUMENT
+ *   bias of neither 1 nor B polys                          RNT_ERR_BAD_ARGUMENT
+ *   outputs of other than B polys                          RNT_ERR_BAD_ARGUMENT
+ *   an output that aliases an input or the other output    RNT_ERR_BAD_ARGUMENT
+ *   inputs, plaintexts or bias on different contexts       RNT_ERR_BASIS_MISMATCH
+ *   an un-rescaled output on another context than the
+ *     inputs'                                              RNT_ERR_BASIS_MISMATCH
+ *   an NTT-domain x0 / x1                                  RNT_ERR_DOMAIN_MISMATCH
+ *   a coefficient-domain m or bias                         RNT_ERR_DOMAIN_MISMATCH
+ *   a key level view in any position                       RNT_ERR_UNSUPPORTED (fields 0, 0)
+ *   the rescaling call with Lv == 1                        RNT_ERR_INVALID_MOD_DROP (fields: 1, Lv)
+ *   the rescaling call with outputs on the wrong or on
+ *     two contexts                                         RNT_ERR_BASIS_MISMATCH */
+int rnt_ct_plain_mac(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1,
+                     const rnt_buf* m, const rnt_buf* bias, size_t n_terms);
+/* rnt_ct_plain_mac followed by rnt_ct_rescale, word for word: out0, out1 hold B
+ * polys on ONE shared context that is drop_last(1) of C (the output rules of
+ * rnt_ct_mul_relin_rescale_hybrid).  Errors as in the table above. */
+int rnt_ct_plain_mac_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1,
+                             const rnt_buf* m, const rnt_buf* bias, size_t n_terms);
 
 /* ---- limb-sharded building blocks ------------------------ */
 /* A rank owning a contiguous run of the global basis' limbs holds every

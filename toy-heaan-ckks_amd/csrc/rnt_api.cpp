@@ -99,7 +99,7 @@ const char* const kKernelNames[rnt::K_COUNT] = {
     "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
     "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto",
     "moddown_rescale", "lincomb", "dot_tensor", "mod_raise", "mul_monomial",
-    "moddown_rescale_affine"};
+    "moddown_rescale_affine", "plain_mac"};
 
 // A profiling call failed: clear the runtime's slot, keep the first failure
 // in the profiler, and stop profiling (rnt_profile_read reports it).
@@ -4529,6 +4529,154 @@ extern "C" int rnt_ct_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, c
     return fail(RNT_ERR_BASIS_MISMATCH, "rescale_ciphertext: outputs must share one basis");
   if (int rc = rnt_rescale(out0, c0)) return rc;
   return rnt_rescale(out1, c1);
+}
+
+// ---------------------------------------------------------------------------
+// ciphertext x plaintext multiply-accumulate (k_plain_mac)
+// ---------------------------------------------------------------------------
+namespace {
+
+// The shared body of rnt_ct_plain_mac and its rescaling form.  Per chunk of
+// ciphertexts and group of up to kPlainT terms: the group's planes of x0 and x1
+// go, forward-transformed, into one call-scoped block X ([L][2 g c][N]: x0's g
+// terms, then x1's, on every limb) -- by the four-step column pass straight
+// from the inputs (launch_col_fwd reads one place and writes another) and one
+// row pass over the block, or, where the transform is one in-place launch (the
+// whole-plane and matrix-core paths), by a gather and that launch over the
+// block; k_plain_mac then sums the group against the plaintexts where they lie
+// (groups after the first accumulate, the last adds the bias).  Un-rescaled the
+// sums are written to the outputs and inverse-transformed there; rescaling they
+// go to one block S ([L][2 c][N]: s0 | s1 on every limb), one inverse runs over
+// both and launch_rescale_strided writes each output.
+int ct_plain_mac_body(const char* name, bool rescale, rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0,
+                      const rnt_buf* x1, const rnt_buf* m, const rnt_buf* bias, size_t n_terms) {
+  const rnt_buf* in[4] = {x0, x1, m, bias};
+  for (const rnt_buf* b : {(const rnt_buf*)out0, (const rnt_buf*)out1, x0, x1, m})
+    if (int rc = check_buf(b, name)) return rc;
+  if (bias)
+    if (int rc = check_buf(bias, name)) return rc;
+  if (n_terms == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: n_terms must be at least 1", name);
+  if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
+  for (const rnt_buf* b : in)
+    if (b && (out0 == b || out1 == b || out0->data == b->data || out1->data == b->data))
+      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output aliases an input", name);
+  if (int rc = check_same(x0, x1, name)) return rc;
+  if (m->ctx != x0->ctx || (bias && bias->ctx != x0->ctx))
+    return fail(RNT_ERR_BASIS_MISMATCH, "%s: operands belong to different bases", name);
+  if (x0->n_polys % n_terms != 0)
+    return fail(RNT_ERR_BAD_ARGUMENT, "%s: inputs of %zu polys are no %zu terms of a batch", name, x0->n_polys,
+                n_terms);
+  const size_t B = x0->n_polys / n_terms;
+  const bool m_shared = m->n_polys == n_terms;  // (one ciphertext: the two forms are one)
+  if (!m_shared && m->n_polys != n_terms * B)
+    return fail(RNT_ERR_BAD_ARGUMENT, "%s: %zu plaintexts for %zu terms of a batch of %zu", name, m->n_polys, n_terms,
+                B);
+  const bool b_shared = bias && bias->n_polys == 1;
+  if (bias && !b_shared && bias->n_polys != B)
+    return fail(RNT_ERR_BAD_ARGUMENT, "%s: a bias of %zu polys for a batch of %zu", name, bias->n_polys, B);
+  if (x0->in_ntt || x1->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the ciphertexts must be in coefficient domain", name);
+  if (!m->in_ntt || (bias && !bias->in_ntt))
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the plaintexts and the bias must be in NTT domain", name);
+  const size_t L = x0->ctx->L;
+  if (rescale) {
+    if (int rc = rescaled_outputs_check(name, out0, out1, x0, B)) return rc;
+  } else {
+    for (const rnt_buf* o : {out0, out1}) {
+      if (o->ctx != x0->ctx) return fail(RNT_ERR_BASIS_MISMATCH, "%s: an output's basis is not the inputs'", name);
+      if (o->n_polys != B)
+        return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output of %zu polys for a batch of %zu", name, o->n_polys, B);
+    }
+  }
+  if (int rc = set_device(x0->ctx)) return rc;
+  rnt::Launch k = launch_for(x0);
+  const size_t n = k.t->n, wb = word_bytes(k.t);
+  const size_t gmax = std::min<size_t>(n_terms, rnt::kPlainT);
+  const size_t ns = rescale ? 2 : 0;  // s0, s1 in workspace
+  const size_t bc = chunk_polys(k.t, (2 * gmax + ns) * L, B);
+  const size_t chunk_words = L * bc * n;
+  // ws: X (x0's and x1's gmax terms) | S (s0 | s1, the rescaling call alone)
+  CallWs cws(out0);
+  if (int rc = cws.get(std::max<size_t>((2 * gmax + ns) * chunk_words * wb, 16))) return rc;
+  char* X = (char*)cws.p;
+  char* S = X + 2 * gmax * chunk_words * wb;
+  const bool four_step = !use_mf(k) && !rnt::whole_ok(k.t, 0);
+  const uint64_t full_ls = limb_stride(x0), out_ls = limb_stride(out0), m_ls = limb_stride(m);
+  const uint64_t b_ls = bias ? limb_stride(bias) : 0;
+  for (size_t p0 = 0; p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    rnt::Launch kc = k;
+    kc.B = c;
+    const uint64_t cls = (uint64_t)c * n;
+    const size_t po = p0 * n * wb;
+    char* D0 = rescale ? S : (char*)out0->data + po;
+    char* D1 = rescale ? S + cls * wb : (char*)out1->data + po;
+    const uint64_t d_ls = rescale ? 2 * cls : out_ls;
+    for (size_t t0 = 0; t0 < n_terms; t0 += gmax) {
+      const size_t g = std::min(gmax, n_terms - t0);
+      const uint64_t gls = (uint64_t)g * cls, xls = 2 * gls;
+      rnt::Launch kx = k;
+      kx.B = 2 * g * c;
+      // term t of the chunk: polys [t B + p0, t B + p0 + c) of every limb; one run a limb where the chunk is the batch
+      const size_t runs = c == B ? 1 : g;
+      rnt::Launch kr = k;
+      kr.B = c == B ? g * c : c;
+      for (size_t i = 0; i < runs; ++i) {
+        const size_t src = ((t0 + i) * B + p0) * n * wb;
+        char* dst = X + i * cls * wb;
+        if (four_step) {
+          LAUNCH(k.t, rnt::K_COL_FWD,
+                 rnt::launch_col_fwd(kr, dst, (const char*)x0->data + src, dst + gls * wb,
+                                     (const char*)x1->data + src, full_ls, xls),
+                 "column forward");
+        } else {
+          for (size_t j = 0; j < 2; ++j)
+            LAUNCH(k.t, rnt::K_COPY,
+                   rnt::launch_copy_rows(k.s, dst + j * gls * wb, xls * wb, (const char*)in[j]->data + src,
+                                         full_ls * wb, (c == B ? gls : cls) * wb, L),
+                   "term gather");
+        }
+      }
+      if (four_step) {
+        LAUNCH(k.t, rnt::K_ROW_FWD, rnt::launch_row(kx, 0, X, nullptr, xls), "row forward");
+      } else {
+        if (int rc = fwd_raw(kx, X, xls)) return rc;
+      }
+      const bool last = t0 + g >= n_terms;
+      const char* mp = (const char*)m->data + (m_shared ? t0 : t0 * B + p0) * n * wb;
+      const char* bp = bias && last ? (const char*)bias->data + (b_shared ? 0 : po) : nullptr;
+      LAUNCH(k.t, rnt::K_PLAIN_MAC,
+             rnt::launch_plain_mac(kc, D0, D1, d_ls, X, X + gls * wb, xls, cls, mp, m_ls, m_shared ? n : B * n,
+                                   m_shared, bp, b_ls, b_shared, g, t0 != 0),
+             "plaintext multiply-accumulate");
+    }
+    if (rescale) {
+      rnt::Launch ks = k;
+      ks.B = 2 * c;
+      if (int rc = inv_raw(ks, S, d_ls)) return rc;
+      LAUNCH(k.t, rnt::K_RESCALE, rnt::launch_rescale_strided(kc, (char*)out0->data + po, out_ls, D0, d_ls),
+             "rescale");
+      LAUNCH(k.t, rnt::K_RESCALE, rnt::launch_rescale_strided(kc, (char*)out1->data + po, out_ls, D1, d_ls),
+             "rescale");
+    } else {
+      if (int rc = inv_raw(kc, D0, d_ls)) return rc;
+      if (int rc = inv_raw(kc, D1, d_ls)) return rc;
+    }
+  }
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
+}  // namespace
+
+extern "C" int rnt_ct_plain_mac(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1, const rnt_buf* m,
+                                const rnt_buf* bias, size_t n_terms) {
+  return ct_plain_mac_body("rnt_ct_plain_mac", false, out0, out1, x0, x1, m, bias, n_terms);
+}
+
+extern "C" int rnt_ct_plain_mac_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* x0, const rnt_buf* x1,
+                                        const rnt_buf* m, const rnt_buf* bias, size_t n_terms) {
+  return ct_plain_mac_body("rnt_ct_plain_mac_rescale", true, out0, out1, x0, x1, m, bias, n_terms);
 }
 
 // ---------------------------------------------------------------------------

@@ -184,7 +184,7 @@ enum KernelId {
   K_SFFT, K_SAMPLE, K_COPY, K_PLANE_FUSED, K_MF_NTT_FWD, K_MF_NTT_INV, K_WHOLE_FWD, K_WHOLE_INV, K_WHOLE_MUL,
   K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_MODUP, K_MODDOWN,
   K_MODDOWN_AUTO, K_MODDOWN_RESCALE, K_LINCOMB, K_DOT_TENSOR, K_MOD_RAISE, K_MUL_MONOMIAL,
-  K_MODDOWN_RESCALE_AFFINE, K_COUNT
+  K_MODDOWN_RESCALE_AFFINE, K_PLAIN_MAC, K_COUNT
 };
 
 struct Prof {
@@ -500,6 +500,21 @@ constexpr size_t kDotT = 4;
 hipError_t launch_dot_tensor(const Launch& k, void* d0, void* d1, void* d2, uint64_t out_ls, const void* x0,
                              const void* x1, const void* y0, const void* y1, uint64_t in_ls, uint64_t term_words,
                              size_t nt, bool accum);
+// launch_plain_mac (k_plain_mac): the plaintext sums of nt <= kPlainT terms of
+// rnt_ct_plain_mac.  k.L = Lv limbs, k.B = the chunk's ciphertexts; x0 / x1:
+// NTT-domain planes at limb stride in_ls, term i at + i term_words of a limb;
+// m: the NTT-domain plaintexts at limb stride m_ls, term i at + i m_term_words,
+// one plane for every ciphertext (m_shared) or k.B planes; bias: nullptr, or
+// NTT-domain words at limb stride b_ls, one plane (b_shared) or k.B.  d0 / d1:
+// sum_i x0_i m_i (+ bias) and sum_i x1_i m_i, canonical, at limb stride out_ls
+// -- added to the words already there with `accum`.  The outputs alias no input.
+// kPlainT: the largest of 4, 8, 16 at which every form of the kernel keeps 0
+// bytes of scratch and the occupancy of k_dot_tensor's same form (DESIGN.md §4
+// "rnt_ct_plain_mac").
+constexpr size_t kPlainT = 16;
+hipError_t launch_plain_mac(const Launch& k, void* d0, void* d1, uint64_t out_ls, const void* x0, const void* x1,
+                            uint64_t in_ls, uint64_t term_words, const void* m, uint64_t m_ls, uint64_t m_term_words,
+                            bool m_shared, const void* bias, uint64_t b_ls, bool b_shared, size_t nt, bool accum);
 // launch_mod_raise (rnt_raise.hip k_mod_raise): k.t the OUTPUT basis' tables,
 // k.L its limbs, k.B polys; `in` holds l0 < k.L coefficient-domain limbs of k.B
 // polys (limb stride k.B N, as `out`) whose moduli are the tables' first l0.

@@ -2784,6 +2784,87 @@ k_dot_tensor(W* __restrict__ d0, W* __restrict__ d1, W* __restrict__ d2, const W
   st_vec<W, VEC, V>(d2 + o, s2);
 }
 
+// The plaintext sums of rnt_ct_plain_mac[_rescale]: with x0^, x1^ the
+// forward-transformed planes of a group of nt <= PLAIN_T terms (term i of the
+// chunk's c ciphertexts at + i term_words of a limb plane, limb stride in_ls)
+// and m^ the NTT-domain plaintexts where the caller keeps them (term i at
+// + i m_term_words of a limb plane, limb stride m_ls),
+//   s0^ = sum_i x0^_i m^_i (+ bias^)   s1^ = sum_i x1^_i m^_i
+// as canonical NTT-domain words at limb stride out_ls.  A lane owns one vector
+// of the c N positions of the chunk on limb blockIdx.y; its plaintext words
+// are at position & m_mask of the term's plane (N - 1: one plaintext for every
+// ciphertext; all ones: one per ciphertext), the bias' at position & b_mask.
+// The products are Montgomery products of plain words (x m 2^-w, reduced) and
+// the sums add_mod of canonical words, so no bound depends on the modulus or on
+// the number of terms; each sum is then multiplied once by 2^w mod q
+// (LimbConst::rmod), so neither the plaintexts nor the sums take a pass of
+// their own.  With `accum` (uniform) the canonical sums of the groups before
+// are added after that factor; the bias (nullptr: none) goes to s0^ of the
+// last group.  The loop over the PLAIN_T terms is unrolled behind a uniform
+// guard: no counter or address arithmetic between the terms, and the three
+// loads of a term are in flight together.  (The compiler keeps each guarded
+// term a block of its own, so the registers do not grow with PLAIN_T:
+// DESIGN.md §4 has the table.)
+constexpr int PLAIN_T = (int)kPlainT;
+struct PlainMacGeom {
+  uint64_t limb_words, term_words, in_ls, out_ls, m_term_words, m_ls, m_mask, b_ls, b_mask;
+  uint32_t nt, accum;
+};
+template <class W, bool VEC>
+__global__ void __launch_bounds__(256)
+k_plain_mac(W* __restrict__ d0, W* __restrict__ d1, const W* __restrict__ x0, const W* __restrict__ x1,
+            const W* __restrict__ m, const W* __restrict__ bias, PlainMacGeom a, TabPtrs<W> tp, LimbMap lm) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint32_t l = blockIdx.y;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= a.limb_words) return;
+  const LimbConst<W> lc = tp.lc[root_limb(l, lm)];
+  const uint64_t in = (uint64_t)l * a.in_ls + i;
+  const uint64_t mi = (uint64_t)l * a.m_ls + (i & a.m_mask);
+  W s0[V], s1[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) s0[v] = s1[v] = (W)0;
+#pragma unroll
+  for (int tt = 0; tt < PLAIN_T; ++tt) {
+    if ((uint32_t)tt < a.nt) {  // (uniform)
+      const uint64_t g = in + (uint64_t)tt * a.term_words;
+      W a0[V], a1[V], p[V];
+      ld_vec<W, VEC, V>(a0, x0 + g);
+      ld_vec<W, VEC, V>(a1, x1 + g);
+      ld_vec<W, VEC, V>(p, m + mi + (uint64_t)tt * a.m_term_words);
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        s0[v] = add_mod<W>(s0[v], mont_mul<W>(a0[v], p[v], lc.q, lc.qinv), lc.q);
+        s1[v] = add_mod<W>(s1[v], mont_mul<W>(a1[v], p[v], lc.q, lc.qinv), lc.q);
+      }
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    s0[v] = shoup_mul<W>(s0[v], lc.rmod, lc.rmod_p, lc.q);
+    s1[v] = shoup_mul<W>(s1[v], lc.rmod, lc.rmod_p, lc.q);
+  }
+  const uint64_t o = (uint64_t)l * a.out_ls + i;
+  if (a.accum) {  // (uniform)
+    W p0[V], p1[V];
+    ld_vec<W, VEC, V>(p0, d0 + o);
+    ld_vec<W, VEC, V>(p1, d1 + o);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      s0[v] = add_mod<W>(p0[v], s0[v], lc.q);
+      s1[v] = add_mod<W>(p1[v], s1[v], lc.q);
+    }
+  }
+  if (bias != nullptr) {  // (uniform)
+    W b[V];
+    ld_vec<W, VEC, V>(b, bias + (uint64_t)l * a.b_ls + (i & a.b_mask));
+#pragma unroll
+    for (int v = 0; v < V; ++v) s0[v] = add_mod<W>(s0[v], b[v], lc.q);
+  }
+  st_vec<W, VEC, V>(d0 + o, s0);
+  st_vec<W, VEC, V>(d1 + o, s1);
+}
+
 // Gather kernels: grid y = limb, x = the limb's B*N words (no per-thread
 // division).  XCD-aware deal along x: hardware block b of a row runs on XCD
 // b % 8 (gridDim.x is a multiple of 8), so logical block (b % 8) *
@@ -3668,6 +3749,52 @@ static hipError_t dot_tensor_t(const Launch& k, void* d0, void* d1, void* d2, ui
   return hipGetLastError();
 }
 
+// k.L = Lv limbs, k.B = the chunk's ciphertexts (rnt_internal.hpp).
+template <class W>
+static hipError_t plain_mac_t(const Launch& k, void* d0, void* d1, uint64_t out_ls, const void* x0, const void* x1,
+                              uint64_t in_ls, uint64_t term_words, const void* m, uint64_t m_ls,
+                              uint64_t m_term_words, bool m_shared, const void* bias, uint64_t b_ls, bool b_shared,
+                              size_t nt, bool accum) {
+  const uint64_t N = 1ull << k.t->log_n;
+  const uint64_t limb_words = (uint64_t)k.B * N;
+  const uint64_t m_words = m_shared ? N : limb_words, b_words = b_shared ? N : limb_words;
+  if (nt == 0 || nt > kPlainT || !limb_map_ok(k) || out_ls < limb_words || term_words < limb_words ||
+      in_ls < (nt - 1) * term_words + limb_words || m_term_words < m_words ||
+      m_ls < (nt - 1) * m_term_words + m_words || (bias && b_ls < b_words) || !d0 || !d1 || !x0 || !x1 || !m)
+    return hipErrorInvalidValue;
+  if (limb_words == 0 || k.L == 0) return hipSuccess;
+  constexpr int V = 16 / (int)sizeof(W);
+  // 16-byte accesses: whole vectors within a plane, every plane and term 16-byte aligned -- the
+  // plaintexts' and the bias' too
+  const bool vec = N % V == 0 && in_ls % V == 0 && out_ls % V == 0 && term_words % V == 0 && m_ls % V == 0 &&
+                   m_term_words % V == 0 && (!bias || b_ls % V == 0) &&
+                   ((uintptr_t)d0 | (uintptr_t)d1 | (uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)m | (uintptr_t)bias) %
+                           16 == 0;
+  const uint64_t per = vec ? limb_words / V : limb_words;
+  const uint64_t bx = (per + 255) / 256;
+  if (bx > 0x7fffffffull || k.L > 65535) return hipErrorInvalidConfiguration;
+  const dim3 grid((unsigned)bx, (unsigned)k.L);
+  PlainMacGeom a;
+  a.limb_words = limb_words;
+  a.term_words = term_words;
+  a.in_ls = in_ls;
+  a.out_ls = out_ls;
+  a.m_term_words = m_term_words;
+  a.m_ls = m_ls;
+  a.m_mask = m_shared ? N - 1 : ~0ull;
+  a.b_ls = b_ls;
+  a.b_mask = b_shared ? N - 1 : ~0ull;
+  a.nt = (uint32_t)nt;
+  a.accum = accum ? 1u : 0u;
+#define RNT_PM(VEC)                                                                                         \
+  hipLaunchKernelGGL((k_plain_mac<W, VEC>), grid, dim3(256), 0, k.s, (W*)d0, (W*)d1, (const W*)x0, (const W*)x1, \
+                     (const W*)m, (const W*)bias, a, tab_ptrs<W>(k.t), limb_map(k))
+  if (vec) RNT_PM(true);
+  else RNT_PM(false);
+#undef RNT_PM
+  return hipGetLastError();
+}
+
 static uint64_t inv_mod_pow2(uint64_t h, uint64_t M) {
   // h odd, M power of two: Newton iteration for h^-1 mod 2^64, then mask.
   uint64_t x = h;  // correct to 3 bits
@@ -4223,6 +4350,14 @@ hipError_t launch_dot_tensor(const Launch& k, void* d0, void* d1, void* d2, uint
                              size_t nt, bool accum) {
   RNT_WIDE(dot_tensor_t<uint32_t>(k, d0, d1, d2, out_ls, x0, x1, y0, y1, in_ls, term_words, nt, accum),
            dot_tensor_t<uint64_t>(k, d0, d1, d2, out_ls, x0, x1, y0, y1, in_ls, term_words, nt, accum));
+}
+hipError_t launch_plain_mac(const Launch& k, void* d0, void* d1, uint64_t out_ls, const void* x0, const void* x1,
+                            uint64_t in_ls, uint64_t term_words, const void* m, uint64_t m_ls, uint64_t m_term_words,
+                            bool m_shared, const void* bias, uint64_t b_ls, bool b_shared, size_t nt, bool accum) {
+  RNT_WIDE(plain_mac_t<uint32_t>(k, d0, d1, out_ls, x0, x1, in_ls, term_words, m, m_ls, m_term_words, m_shared, bias,
+                                 b_ls, b_shared, nt, accum),
+           plain_mac_t<uint64_t>(k, d0, d1, out_ls, x0, x1, in_ls, term_words, m, m_ls, m_term_words, m_shared, bias,
+                                 b_ls, b_shared, nt, accum));
 }
 hipError_t launch_hoist_mac_seed(const Launch& k, void* acc0, void* acc1, const void* d, const void* key_a,
                                  const void* key_b, uint64_t key_ls, const void* seed_a, const void* seed_b,

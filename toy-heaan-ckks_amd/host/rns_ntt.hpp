@@ -289,6 +289,26 @@ class RnsPoly {
     return out;
   }
 
+  // (c0, c1) (.) pt (+ bias) for one ciphertext and one NTT-domain plaintext
+  // (rnt_ct_plain_mac with one term; bias: NTT domain or nullptr), and the
+  // same followed by the ciphertext rescale (rnt_ct_plain_mac_rescale)
+  static std::pair<RnsPoly, RnsPoly> mul_plain(const RnsPoly& c0, const RnsPoly& c1, const RnsPoly& pt,
+                                               const RnsPoly* bias = nullptr) {
+    RnsPoly r0(c0.basis_), r1(c0.basis_);
+    check(rnt_ct_plain_mac(r0.buf_, r1.buf_, c0.buf_, c1.buf_, pt.buf_, bias ? bias->buf_ : nullptr, 1));
+    return {std::move(r0), std::move(r1)};
+  }
+  static std::pair<RnsPoly, RnsPoly> mul_plain_rescale(const RnsPoly& c0, const RnsPoly& c1, const RnsPoly& pt,
+                                                       const RnsPoly* bias = nullptr) {
+    if (c0.basis_->channel_count() < 2)
+      throw RnsNttError(RNT_ERR_INVALID_MOD_DROP, "rescale needs at least two channels", 1,
+                        c0.basis_->channel_count());
+    BasisRef<N> nb = c0.basis_->drop_last(1);
+    RnsPoly r0(nb), r1(nb);
+    check(rnt_ct_plain_mac_rescale(r0.buf_, r1.buf_, c0.buf_, c1.buf_, pt.buf_, bias ? bias->buf_ : nullptr, 1));
+    return {std::move(r0), std::move(r1)};
+  }
+
   // PolyRing::to_coeffs (poly.rs:404-427): centred CRT on the device
   std::array<int64_t, N> to_coeffs() const {
     std::array<int64_t, N> out{};

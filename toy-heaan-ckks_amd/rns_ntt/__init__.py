@@ -72,6 +72,8 @@ __all__ = [
     "bsgs_diagonal_rows",
     "rescale_ciphertext",
     "ct_lincomb",
+    "ct_plain_mac",
+    "mul_plain",
     "poly_eval_plan",
     "poly_eval_plan_fused",
     "PolyEvalPlan",
@@ -1425,6 +1427,59 @@ def dot_ciphertexts_hybrid(ctx: Ciphertext, cty: Ciphertext, n_terms: int, rlk: 
     check(call(out0.handle, out1.handle, ctx.c0.handle, ctx.c1.handle, cty.c0.handle, cty.c1.handle, n_terms,
                rlk.a.handle, rlk.b.handle, rlk.alpha))
     return Ciphertext(out0, out1, ctx.logp + cty.logp - bits_dropped, ctx.logq - bits_dropped)
+
+
+def ct_plain_mac(ct: Ciphertext, n_terms: int, pt: RnsPoly, bias: Optional[RnsPoly] = None, rescale: bool = True,
+                 out_basis: Optional[RnsBasis] = None) -> Ciphertext:
+    """``sum_i ct_i * pt_i + bias`` over the ``n_terms`` ciphertexts packed in
+    ``ct`` (a batch of ``n_terms * B``, term i of ciphertext b at ``i * B + b``,
+    the layout ``ct_lincomb`` reads and ``rotate_ciphertext_hybrid_hoisted``
+    writes) with encoded plaintexts (rnt_ct_plain_mac /
+    rnt_ct_plain_mac_rescale).  ``pt`` is an NTT-domain ``RnsPoly`` on the
+    ciphertexts' basis: ``n_terms`` polys, plaintext i for every ciphertext, or
+    ``n_terms * B``, term i of ciphertext b at ``i * B + b``.  ``bias`` is None
+    or an NTT-domain ``RnsPoly`` of 1 or ``B`` polys, added to ``c0``, at the
+    scale the caller means (the products' scale).  A batch of ``B`` comes back;
+    its words are those of the coefficient-domain composition.  With
+    ``rescale`` the result is ``rescale_ciphertext`` of the un-rescaled call,
+    word for word, and logp / logq drop by the bit length of the limb rescaled
+    away.  logp does not grow by the plaintexts' scale: the caller adds it.
+    ``out_basis`` as in :func:`mul_ciphertexts_hybrid_rescale`."""
+    n_terms = int(n_terms)
+    if n_terms < 1 or ct.c0.n_polys % n_terms != 0 or ct.c1.n_polys != ct.c0.n_polys:
+        raise ValueError(f"ct_plain_mac: a batch of {ct.c0.n_polys} polys is no {n_terms} terms of ciphertexts")
+    B = ct.c0.n_polys // n_terms
+    if not isinstance(pt, RnsPoly) or (bias is not None and not isinstance(bias, RnsPoly)):
+        raise ValueError("ct_plain_mac: the plaintexts and the bias are RnsPoly batches in the NTT domain")
+    if pt.n_polys not in (n_terms, n_terms * B):
+        raise ValueError(f"ct_plain_mac: {pt.n_polys} plaintexts for {n_terms} terms of a batch of {B}")
+    if bias is not None and bias.n_polys not in (1, B):
+        raise ValueError(f"ct_plain_mac: a bias of {bias.n_polys} polys for a batch of {B}")
+    if not pt.is_ntt_domain() or (bias is not None and not bias.is_ntt_domain()):
+        raise ValueError("ct_plain_mac: the plaintexts and the bias must be in the NTT domain")
+    basis = ct.c0.basis
+    bits_dropped = 0
+    if rescale:
+        mods = basis.moduli()
+        if len(mods) < 2:
+            raise RnsNttError(_lib.INVALID_MOD_DROP, f"invalid mod-drop count 1 for {len(mods)} channels",
+                              {"drop_count": 1, "channel_count": len(mods)})
+        bits_dropped = mods[-1].bit_length()
+        new_basis = out_basis if out_basis is not None else basis.drop_last(1)
+    else:
+        new_basis = out_basis if out_basis is not None else basis
+    out0 = RnsPoly(new_basis, B, _uninit=True)
+    out1 = RnsPoly(new_basis, B, _uninit=True)
+    call = load().rnt_ct_plain_mac_rescale if rescale else load().rnt_ct_plain_mac
+    check(call(out0.handle, out1.handle, ct.c0.handle, ct.c1.handle, pt.handle,
+               None if bias is None else bias.handle, n_terms))
+    return Ciphertext(out0, out1, ct.logp - bits_dropped, ct.logq - bits_dropped)
+
+
+def mul_plain(ct: Ciphertext, pt: RnsPoly, rescale: bool = True) -> Ciphertext:
+    """``ct * pt`` for an NTT-domain plaintext (one poly for the whole batch,
+    or one per ciphertext): :func:`ct_plain_mac` with one term."""
+    return ct_plain_mac(ct, 1, pt, None, rescale)
 
 
 def rescale_ciphertext(ct: Ciphertext) -> Ciphertext:

@@ -172,6 +172,8 @@ SIGNATURES = {
     "rnt_ct_dot_relin_rescale_hybrid": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, _P, _P, c_size_t]),
     "rnt_ct_lincomb": (c_int, [_P, _P, _P, _P, c_size_t, c_size_t, _U64P, _U64P]),
     "rnt_ct_lincomb_rescale": (c_int, [_P, _P, _P, _P, c_size_t, c_size_t, _U64P, _U64P]),
+    "rnt_ct_plain_mac": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t]),
+    "rnt_ct_plain_mac_rescale": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t]),
     "rnt_encode": (c_int, [_P, c_void_p, c_size_t, c_uint32]),
     "rnt_decode": (c_int, [_P, c_void_p, c_size_t, c_uint32]),
     "rnt_sample_uniform": (c_int, [_P, c_uint64, c_uint64]),
@@ -185,7 +187,7 @@ PROFILE_NAMES = (
     "ks_rows", "tensor_rows", "import", "export", "crt", "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd",
     "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul", "bsgs_mac",
     "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto", "moddown_rescale", "lincomb", "dot_tensor",
-    "mod_raise", "mul_monomial", "moddown_rescale_affine",
+    "mod_raise", "mul_monomial", "moddown_rescale_affine", "plain_mac",
 )
 
 _lib = None

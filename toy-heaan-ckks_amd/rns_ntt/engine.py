@@ -24,7 +24,7 @@ from typing import Optional
 import numpy as np
 
 from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsGadgetKeySet, RnsHybridKey,
-               RnsHybridKeySet, RnsPoly, bsgs_diagonal_rows, check, conjugate_hybrid, ct_lincomb,
+               RnsHybridKeySet, RnsPoly, bsgs_diagonal_rows, check, conjugate_hybrid, ct_lincomb, ct_plain_mac,
                dot_ciphertexts_hybrid, linear_transform, linear_transform_bsgs, merge_real_imag, mul_i,
                split_real_imag_hybrid,
                linear_transform_bsgs_hoisted, linear_transform_bsgs_hybrid, linear_transform_bsgs_hybrid_rescale,
@@ -539,6 +539,54 @@ class CkksEngine:
         assert ct1.logp == ct2.logp, "logp mismatch in addition"
         assert ct1.logq == ct2.logq, "logq mismatch in addition"
         return Ciphertext(ct1.c0 + ct2.c0, ct1.c1 + ct2.c1, ct1.logp, ct1.logq)
+
+    # -- ciphertext x plaintext (rnt_ct_plain_mac) -----------------------------
+    @staticmethod
+    def prepare_plaintext(pt: Plaintext) -> Plaintext:
+        """A copy of ``pt`` in the NTT domain, the form ``mul_plaintext`` and
+        ``plain_mac`` read: made once per weight, used by every call."""
+        poly = pt.poly.clone()
+        if not poly.is_ntt_domain():
+            poly.to_ntt_domain()
+        return Plaintext(poly, pt.scale_bits, pt.slots)
+
+    @staticmethod
+    def plain_mac(ct: Ciphertext, n_terms: int, pt: Plaintext, bias: Optional[Plaintext] = None,
+                  rescale: bool = True) -> Ciphertext:
+        """``sum_i ct_i (.) pt_i + bias`` slot by slot over the ``n_terms``
+        ciphertexts packed in ``ct`` (term i of ciphertext b at ``i * B + b``,
+        as ``rotate_hoisted_hybrid`` writes them): ``pt`` holds ``n_terms``
+        plaintexts for the whole batch or ``n_terms * B``, ``bias`` one or
+        ``B``.  A coefficient-domain plaintext is converted on the fly
+        (``prepare_plaintext`` does it once).  logp grows by the plaintexts'
+        scale, which a bias must carry too, and with ``rescale`` drops, with
+        logq, by the bits of the limb rescaled away."""
+        if bias is not None and bias.scale_bits != ct.logp + pt.scale_bits:
+            raise ValueError(f"plain_mac: a bias at scale 2^{bias.scale_bits} for products at scale "
+                             f"2^{ct.logp + pt.scale_bits}")
+        if not pt.poly.is_ntt_domain():
+            pt = CkksEngine.prepare_plaintext(pt)
+        if bias is not None and not bias.poly.is_ntt_domain():
+            bias = CkksEngine.prepare_plaintext(bias)
+        out = ct_plain_mac(ct, n_terms, pt.poly, None if bias is None else bias.poly, rescale)
+        out.logp += pt.scale_bits
+        return out
+
+    @staticmethod
+    def mul_plaintext(ct: Ciphertext, pt: Plaintext, rescale: bool = True) -> Ciphertext:
+        """``ct (.) pt`` slot by slot: ``plain_mac`` with one term."""
+        return CkksEngine.plain_mac(ct, 1, pt, None, rescale)
+
+    @staticmethod
+    def add_plaintext(ct: Ciphertext, pt: Plaintext) -> Ciphertext:
+        """``ct + pt`` slot by slot: the plaintext, in the coefficient domain
+        and at the ciphertext's scale, is added to c0."""
+        assert ct.logp == pt.scale_bits, "logp mismatch in plaintext addition"
+        poly = pt.poly
+        if poly.is_ntt_domain():
+            poly = poly.clone()
+            poly.to_coeff_domain()
+        return Ciphertext(ct.c0 + poly, ct.c1.clone(), ct.logp, ct.logq)
 
     # the gadget multiply / rotate / rescale are the library calls
     mul_ciphertexts_gadget = staticmethod(mul_ciphertexts_gadget)
