@@ -14,17 +14,22 @@ all: $(LIBDIR)/librnsntt.so $(LIBDIR)/isa_check.ok oracle/liboracle.so
 # Every header each translation unit includes, transitively (a CPU test,
 # tests/test_abi_cpu.py::test_makefile_dependencies_match_includes, diffs
 # these lists against the sources' #include lines).
-DEP_rnt_kernels := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp $(CSRC)/rnt_device.hpp
+DEP_rnt_col     := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp $(CSRC)/rnt_device.hpp $(CSRC)/rnt_fourstep.hpp $(CSRC)/rnt_launch.hpp
+DEP_rnt_rows    := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp $(CSRC)/rnt_device.hpp $(CSRC)/rnt_fourstep.hpp $(CSRC)/rnt_launch.hpp
+DEP_rnt_kernels := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp $(CSRC)/rnt_device.hpp $(CSRC)/rnt_launch.hpp
 DEP_rnt_plane   := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp $(CSRC)/rnt_device.hpp $(CSRC)/rnt_bfly4.hpp
 DEP_rnt_mfma    := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_hostmath.hpp $(CSRC)/rnt_modarith.hpp $(CSRC)/rnt_device.hpp
 DEP_rnt_encode  := $(CSRC)/rnt_internal.hpp
 DEP_rnt_sample  := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp
-DEP_rnt_raise   := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp $(CSRC)/rnt_device.hpp
+DEP_rnt_raise   := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp $(CSRC)/rnt_device.hpp $(CSRC)/rnt_launch.hpp
 DEP_rnt_api     := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_hostmath.hpp include/rnsntt.h
 
-OBJS := $(LIBDIR)/rnt_kernels.o $(LIBDIR)/rnt_plane.o $(LIBDIR)/rnt_mfma.o $(LIBDIR)/rnt_encode.o \
-        $(LIBDIR)/rnt_sample.o $(LIBDIR)/rnt_raise.o $(LIBDIR)/rnt_api.o
+OBJS := $(LIBDIR)/rnt_col.o $(LIBDIR)/rnt_rows.o $(LIBDIR)/rnt_kernels.o \
+        $(LIBDIR)/rnt_plane.o $(LIBDIR)/rnt_mfma.o $(LIBDIR)/rnt_encode.o $(LIBDIR)/rnt_sample.o $(LIBDIR)/rnt_raise.o \
+        $(LIBDIR)/rnt_api.o
 
+$(LIBDIR)/rnt_col.o: $(CSRC)/rnt_col.hip $(DEP_rnt_col)
+$(LIBDIR)/rnt_rows.o: $(CSRC)/rnt_rows.hip $(DEP_rnt_rows)
 $(LIBDIR)/rnt_kernels.o: $(CSRC)/rnt_kernels.hip $(DEP_rnt_kernels)
 $(LIBDIR)/rnt_plane.o: $(CSRC)/rnt_plane.hip $(DEP_rnt_plane)
 $(LIBDIR)/rnt_mfma.o: $(CSRC)/rnt_mfma.hip $(DEP_rnt_mfma)

@@ -17,7 +17,7 @@ LIB=toy-heaan-ckks_amd/lib
 CS=toy-heaan-ckks_amd/csrc
 mkdir -p "$OUT"
 SAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined -fno-omit-frame-pointer"
-for o in rnt_kernels rnt_plane rnt_mfma rnt_encode rnt_sample rnt_raise; do
+for o in rnt_col rnt_rows rnt_kernels rnt_plane rnt_mfma rnt_encode rnt_sample rnt_raise; do
   test -f $LIB/$o.o || { echo "$LIB/$o.o is missing: run make first" >&2; exit 2; }
 done
 {
@@ -28,7 +28,7 @@ $HIPCC --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC $SAN -c $CS/rnt_api.cpp -o 
 $HIPCC --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC $SAN -I include -I $CS -c tests/cpp/affine_args_check.cpp \
   -o $OUT/affine_args_check.o
 $HIPCC --offload-arch=gfx950 -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
-  $OUT/affine_args_check.o $OUT/rnt_api_host.o $LIB/rnt_kernels.o $LIB/rnt_plane.o $LIB/rnt_mfma.o $LIB/rnt_encode.o \
+  $OUT/affine_args_check.o $OUT/rnt_api_host.o $LIB/rnt_col.o $LIB/rnt_rows.o $LIB/rnt_kernels.o $LIB/rnt_plane.o $LIB/rnt_mfma.o $LIB/rnt_encode.o \
   $LIB/rnt_sample.o $LIB/rnt_raise.o -o $OUT/affine_args_check
 set +e
 ASAN_OPTIONS=detect_leaks=0:abort_on_error=1:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \

@@ -1,7 +1,9 @@
 // rnt_device.hpp -- device helpers shared by the kernel translation units
-// (rnt_kernels.hip: four-step transforms, key-switch, elementwise; rnt_plane.hip:
-// the whole-plane poly-mul): table pointers, buffer-resource views, twiddle
-// sources, the truncated product's degree-3 block product, LDS opt-in.
+// (the four-step units over rnt_fourstep.hpp; rnt_kernels.hip and rnt_raise.hip:
+// the streaming kernels; rnt_plane.hip: the whole-plane poly-mul): table
+// pointers, buffer-resource views, twiddle sources, the truncated product's
+// degree-3 block product, 16-byte / one-word accesses, the XCD deal, the limb
+// map, LDS opt-in.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -220,6 +222,59 @@ __device__ __forceinline__ void mul_mod_x4(uint32_t (&c)[4], const uint32_t* a, 
   c[1] = redc_sum4(t1, q, qinv);
   c[2] = redc_sum4(t2, q, qinv);
   c[3] = redc_sum4(t3, q, qinv);
+}
+
+// 16-byte (VEC) or one-word access of V words at p.
+template <class W, bool VEC, int V>
+__device__ __forceinline__ void ld_vec(W (&o)[V], const W* p) {
+  if constexpr (VEC) {
+    const uint4 a = *reinterpret_cast<const uint4*>(p);
+    __builtin_memcpy(o, &a, 16);
+  } else {
+    o[0] = p[0];
+  }
+}
+template <class W, bool VEC, int V>
+__device__ __forceinline__ void st_vec(W* p, const W (&r)[V]) {
+  if constexpr (VEC) {
+    uint4 o;
+    __builtin_memcpy(&o, r, 16);
+    *reinterpret_cast<uint4*>(p) = o;
+  } else {
+    p[0] = r[0];
+  }
+}
+
+// Gather kernels: grid y = limb, x = the limb's B*N words (no per-thread
+// division).  XCD-aware deal along x: hardware block b of a row runs on XCD
+// b % 8 (gridDim.x is a multiple of 8), so logical block (b % 8) *
+// (gridDim.x / 8) + b / 8 gives every XCD a contiguous run of the limb --
+// whole polys, whose scattered gathers then stay in that XCD's L2 instead
+// of every XCD fetching every poly.
+__device__ __forceinline__ uint64_t xcd_gid() {
+  const uint32_t per_xcd = gridDim.x >> 3;
+  const uint32_t wg = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+  return (uint64_t)wg * blockDim.x + threadIdx.x;
+}
+
+// The limb map of a hybrid key's level view (rnt_key_level_view): working limb
+// t of the basis q_0..q_{level-1}, p_0..p_{K-1} is root limb t below `level`
+// and t + gap from there on -- the row of tp.lc and the key plane to read.
+// Every caller derives t from blockIdx or a loop counter, so the mapped index
+// is wave-uniform; gap 0 (every other caller) is the identity.
+struct LimbMap {
+  uint32_t level, gap;
+};
+__device__ __forceinline__ uint32_t root_limb(uint32_t t, LimbMap m) { return t < m.level ? t : t + m.gap; }
+// The limb map of a launch over a level view (Launch::map_level / map_gap) and
+// its bound: the last working limb's root limb is one of the tables'.
+static inline LimbMap limb_map(const Launch& k) { return LimbMap{k.map_level, k.map_gap}; }
+static inline bool limb_map_ok(const Launch& k) {
+  return k.L <= k.t->L && (k.L <= k.map_level || k.L + k.map_gap <= k.t->L);
+}
+
+static inline unsigned grid_for(uint64_t total, unsigned block) {
+  return (unsigned)((total + block - 1) / block);
 }
 
 template <class K>

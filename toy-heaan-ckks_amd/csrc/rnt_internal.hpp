@@ -1,5 +1,6 @@
 // rnt_internal.hpp -- private types shared by the C-ABI layer (rnt_api.cpp)
-// and the kernels (rnt_kernels.hip).
+// and the kernel units (rnt_col / rnt_rows / rnt_kernels /
+// rnt_raise / rnt_plane / rnt_mfma .hip).
 //
 // Device layout (private):
 //   A buffer of B polynomials over L limbs is one allocation of W words laid
@@ -284,7 +285,7 @@ struct Launch {
   size_t src_limbs() const { return Ls ? Ls : L; }
 };
 
-// ---- launchers (rnt_kernels.hip), W-dispatched by t->wide ---------------
+// ---- launchers (one per kernel family, beside its kernels), W-dispatched by t->wide
 // All arrays are [limb][poly][N] with an explicit limb stride `*_ls` (words);
 // k.B polys (a batch or a chunk of one) and k.L limbs are processed.
 // Forward column pass on up to two operands (in0->out0, in1->out1).
@@ -331,7 +332,7 @@ hipError_t launch_mf_mul(const Launch& k, void* c, const void* a, const void* b,
 // multiplies degree-3 residues (u32 canonical bases, row length 2^(4k));
 // its inverse column pass then takes rfold = 2.
 bool mul_truncated(const Tables* t);
-// The whole-plane row path at 2^10 <= N <= 2^14 (u32 and u64; rnt_kernels.hip
+// The whole-plane row path at 2^10 <= N <= 2^14 (u32 and u64; rnt_rows.hip
 // k_row<..., WHOLE>): one launch per transform or product, every plane one
 // row.  mode 0: forward in place (x); 1: inverse in place (x); 2: out = x * y
 // in the coefficient domain (out may alias x or y).  whole_ok: the path serves

@@ -4,7 +4,7 @@
 // (src/rings/backends/rns_ntt/poly.rs:307-329: to_ntt_domain of both
 // operands, the pointwise mul_mod, to_coeff_domain), computed for a batch of
 // (poly, limb) planes with the same merged negacyclic CT / GS network as the
-// four-step kernels in rnt_kernels.hip, so the result is word-for-word the
+// four-step kernels in rnt_col.hip / rnt_rows.hip, so the result is word-for-word the
 // same (and the reference's).
 #include <hip/hip_runtime.h>
 

@@ -13,35 +13,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "rnt_device.hpp"
 #include "rnt_internal.hpp"
+#include "rnt_launch.hpp"
 #include "rnt_modarith.hpp"
 
 namespace rnt {
 
 namespace {
-
-template <class W, bool VEC, int V>
-__device__ __forceinline__ void ld_words(W (&o)[V], const W* p) {
-  if constexpr (VEC) {
-    const uint4 a = *reinterpret_cast<const uint4*>(p);
-    __builtin_memcpy(o, &a, 16);
-  } else {
-    o[0] = p[0];
-  }
-}
-template <class W, bool VEC, int V>
-__device__ __forceinline__ void st_words(W* p, const W (&r)[V]) {
-  if constexpr (VEC) {
-    uint4 o;
-    __builtin_memcpy(&o, r, 16);
-    *reinterpret_cast<uint4*>(p) = o;
-  } else {
-    p[0] = r[0];
-  }
-}
 
 // ModRaise.  A lane reads its vector of the L0 input planes once and forms
 // the mixed-radix digits d_0 .. d_{L0-1} of x in [0, Q0) -- x = d_0 + q_0 d_1 +
@@ -66,7 +45,7 @@ k_mod_raise(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ in, uint
   W x[L0][V], d[L0][V];
   bool neg[V];
 #pragma unroll
-  for (int a = 0; a < L0; ++a) ld_words<W, VEC, V>(x[a], in + (uint64_t)a * in_ls + i);
+  for (int a = 0; a < L0; ++a) ld_vec<W, VEC, V>(x[a], in + (uint64_t)a * in_ls + i);
 #pragma unroll
   for (int v = 0; v < V; ++v) d[0][v] = x[0][v];
 #pragma unroll
@@ -113,7 +92,7 @@ k_mod_raise(W* __restrict__ out, uint64_t out_ls, const W* __restrict__ in, uint
 #pragma unroll
       for (int v = 0; v < V; ++v) r[v] = sub_mod<W>(r[v], neg[v] ? c : (W)0, q);
     }
-    st_words<W, VEC, V>(out + (uint64_t)j * out_ls + i, r);
+    st_vec<W, VEC, V>(out + (uint64_t)j * out_ls + i, r);
   }
 }
 
@@ -137,7 +116,7 @@ k_mul_monomial(W* __restrict__ out, const W* __restrict__ in, TabPtrs<W> tp, uin
   W r[V];
   if constexpr (VEC && ALN) {
     const uint32_t s = (t - k) & m2;  // a multiple of V: the V sources do not wrap
-    ld_words<W, true, V>(r, in + base + (s & (N - 1)));
+    ld_vec<W, true, V>(r, in + base + (s & (N - 1)));
     if (s >= N) {
 #pragma unroll
       for (int v = 0; v < V; ++v) r[v] = r[v] == 0 ? (W)0 : (W)(q - r[v]);
@@ -150,80 +129,59 @@ k_mul_monomial(W* __restrict__ out, const W* __restrict__ in, TabPtrs<W> tp, uin
       r[v] = s < N ? c : (c == 0 ? (W)0 : (W)(q - c));
     }
   }
-  st_words<W, VEC, V>(out + (uint64_t)l * limb_words + i, r);
-}
-
-// Blocks below which the output limbs of k_mod_raise are split over blockIdx.y
-// (as the hybrid kernels' kSplitBlocks).
-constexpr uint64_t kRaiseSplitBlocks = 1024;
-
-template <class W>
-hipError_t mod_raise_t(const Launch& k, void* out, const void* in, size_t l0, const RaiseConsts& rc) {
-  const uint64_t N = 1ull << k.t->log_n;
-  const uint64_t limb_words = (uint64_t)k.B * N;
-  if (l0 == 0 || l0 > kRaiseMax || l0 >= k.L || k.L > k.t->L || !out || !in || !rc.rad || !rc.radp || !rc.q0m)
-    return hipErrorInvalidValue;
-  if (limb_words == 0) return hipSuccess;
-  constexpr int V = 16 / (int)sizeof(W);
-  // 16-byte accesses: whole vectors within a plane, every plane 16-byte aligned
-  const bool vec = N % V == 0 && ((uintptr_t)out | (uintptr_t)in) % 16 == 0;
-  const uint64_t per = vec ? limb_words / V : limb_words;
-  const uint64_t bx = (per + 255) / 256;
-  if (bx > 0x7fffffffull) return hipErrorInvalidConfiguration;
-  const uint64_t runs = std::min<uint64_t>(k.L, std::max<uint64_t>(kRaiseSplitBlocks / bx, 1));
-  const uint32_t jper = (uint32_t)((k.L + runs - 1) / runs);
-  const dim3 grid((unsigned)bx, (unsigned)((k.L + jper - 1) / jper));
-#define RNT_MR(VEC, L0)                                                                                         \
-  hipLaunchKernelGGL((k_mod_raise<W, VEC, L0>), grid, dim3(256), 0, k.s, (W*)out, limb_words, (const W*)in,      \
-                     limb_words, tab_ptrs<W>(k.t), (const W*)rc.rad, (const W*)rc.radp, (const W*)rc.q0m, rc.g,  \
-                     limb_words, (uint32_t)k.L, jper)
-#define RNT_MR_V(L0)          \
-  do {                        \
-    if (vec) RNT_MR(true, L0); \
-    else RNT_MR(false, L0);   \
-  } while (0)
-  switch (l0) {
-    case 1: RNT_MR_V(1); break;
-    case 2: RNT_MR_V(2); break;
-    case 3: RNT_MR_V(3); break;
-    default: RNT_MR_V(4); break;
-  }
-#undef RNT_MR_V
-#undef RNT_MR
-  return hipGetLastError();
-}
-
-template <class W>
-hipError_t mul_monomial_t(const Launch& k, void* out, const void* in, uint64_t shift) {
-  const uint64_t N = 1ull << k.t->log_n;
-  const uint64_t limb_words = (uint64_t)k.B * N;
-  if (shift >= 2 * N || !out || !in || out == in) return hipErrorInvalidValue;
-  if (limb_words == 0 || k.L == 0) return hipSuccess;
-  constexpr int V = 16 / (int)sizeof(W);
-  const bool vec = N % V == 0 && ((uintptr_t)out | (uintptr_t)in) % 16 == 0;
-  const bool aln = vec && shift % V == 0;
-  const uint64_t per = vec ? limb_words / V : limb_words;
-  const uint64_t bx = (per + 255) / 256;
-  if (bx > 0x7fffffffull || k.L > 65535) return hipErrorInvalidConfiguration;
-  const dim3 grid((unsigned)bx, (unsigned)k.L);
-#define RNT_MM(VEC, ALN)                                                                                  \
-  hipLaunchKernelGGL((k_mul_monomial<W, VEC, ALN>), grid, dim3(256), 0, k.s, (W*)out, (const W*)in,        \
-                     tab_ptrs<W>(k.t), k.t->log_n, (uint32_t)shift, limb_words)
-  if (aln) RNT_MM(true, true);
-  else if (vec) RNT_MM(true, false);
-  else RNT_MM(false, false);
-#undef RNT_MM
-  return hipGetLastError();
+  st_vec<W, VEC, V>(out + (uint64_t)l * limb_words + i, r);
 }
 
 }  // namespace
 
+// The output limbs are split over blockIdx.y below kSplitBlocks workgroups (as
+// the hybrid kernels'); one instantiation per input limb count l0 <= kRaiseMax.
 hipError_t launch_mod_raise(const Launch& k, void* out, const void* in, size_t l0, const RaiseConsts& rc) {
-  return k.t->wide ? mod_raise_t<uint64_t>(k, out, in, l0, rc) : mod_raise_t<uint32_t>(k, out, in, l0, rc);
+  return by_word(k, [&](auto w) -> hipError_t {
+    using W = decltype(w);
+    const uint64_t N = 1ull << k.t->log_n;
+    const uint64_t limb_words = (uint64_t)k.B * N;
+    if (l0 == 0 || l0 > kRaiseMax || l0 >= k.L || k.L > k.t->L || !out || !in || !rc.rad || !rc.radp || !rc.q0m)
+      return hipErrorInvalidValue;
+    if (limb_words == 0) return hipSuccess;
+    // 16-byte accesses: whole vectors within a plane, every plane 16-byte aligned
+    const bool vec = vec_ok<W>(N, {}, ptr_bits(out, in));
+    const uint64_t bx = blocks_x<W>(limb_words, vec);
+    if (!grid_ok(bx)) return hipErrorInvalidConfiguration;
+    const LimbSplit sp = limb_split(k.L, bx);
+    const dim3 grid((unsigned)bx, sp.extent);
+    with_tier<1, 2, 3, 4>(l0, [&](auto L0) {
+      with_bool(vec, [&](auto VEC) {
+        hipLaunchKernelGGL((k_mod_raise<W, decltype(VEC)::value, decltype(L0)::value>), grid, dim3(256), 0, k.s,
+                           (W*)out, limb_words, (const W*)in, limb_words, tab_ptrs<W>(k.t), (const W*)rc.rad,
+                           (const W*)rc.radp, (const W*)rc.q0m, rc.g, limb_words, (uint32_t)k.L, sp.per);
+      });
+    });
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_mul_monomial(const Launch& k, void* out, const void* in, uint64_t shift) {
-  return k.t->wide ? mul_monomial_t<uint64_t>(k, out, in, shift) : mul_monomial_t<uint32_t>(k, out, in, shift);
+  return by_word(k, [&](auto w) -> hipError_t {
+    using W = decltype(w);
+    const uint64_t N = 1ull << k.t->log_n;
+    const uint64_t limb_words = (uint64_t)k.B * N;
+    if (shift >= 2 * N || !out || !in || out == in) return hipErrorInvalidValue;
+    if (limb_words == 0 || k.L == 0) return hipSuccess;
+    const bool vec = vec_ok<W>(N, {}, ptr_bits(out, in));
+    const uint64_t bx = blocks_x<W>(limb_words, vec);
+    if (!grid_ok(bx, k.L)) return hipErrorInvalidConfiguration;
+    const dim3 grid((unsigned)bx, (unsigned)k.L);
+    // ALN: the shift a whole number of vectors too (VEC alone else; never ALN without VEC)
+    with_bool(vec, [&](auto VEC) {
+      with_bool(vec && shift % (16 / sizeof(W)) == 0, [&](auto ALN) {
+        if constexpr (decltype(VEC)::value || !decltype(ALN)::value)
+          hipLaunchKernelGGL((k_mul_monomial<W, decltype(VEC)::value, decltype(ALN)::value>), grid, dim3(256), 0, k.s,
+                             (W*)out, (const W*)in, tab_ptrs<W>(k.t), k.t->log_n, (uint32_t)shift, limb_words);
+      });
+    });
+    return hipGetLastError();
+  });
 }
 
 }  // namespace rnt
