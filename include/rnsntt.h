@@ -93,7 +93,8 @@ int rnt_device_count(int* n);
  * "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
  * "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown",
  * "moddown_auto", "moddown_rescale", "lincomb", "dot_tensor", "mod_raise",
- * "mul_monomial", "moddown_rescale_affine", "plain_mac"), the launch
+ * "mul_monomial", "moddown_rescale_affine", "rotsum_mac", "rotsum_c0",
+ * "automorph_ntt", "plain_mac"), the launch
  * count and summed device milliseconds since enabling. */
 int rnt_profile_enable(const rnt_ctx* ctx, int enable);
 int rnt_profile_read(const rnt_ctx* ctx, const char* kernel, uint64_t* launches,
@@ -286,6 +287,20 @@ int rnt_automorphism(rnt_buf* out, const rnt_buf* in, uint64_t g);
 /* rotate_slots (poly.rs:546-569): g = 5^k mod 2N (k >= 0); for k < 0 the
  * reference's automorphism(5^|k|) then automorphism(2N-1). */
 int rnt_rotate_slots(rnt_buf* out, const rnt_buf* in, int32_t k);
+/* The automorphism X -> X^g in the NTT domain (rnt_automorphism_ntt; no
+ * reference counterpart): `in` is in the NTT domain, g is odd, and `out` receives the NTT-domain words of
+ * sigma_g(in) -- DEFINED as rnt_ntt_fwd(rnt_automorphism(., g)), word for word,
+ * but no inverse or forward transform runs: in the NTT domain sigma_g is a pure
+ * permutation of the evaluation points, with no sign changes (one gather
+ * launch; DESIGN.md "Rotate-and-sum").  g is taken mod 2N.  Both buffers on one
+ * context with one batch size; `out` must not alias `in`; recordable.
+ * Errors: a coefficient-domain `in` -> RNT_ERR_DOMAIN_MISMATCH; an even g,
+ * out == in, batch sizes that differ, a null argument -> RNT_ERR_BAD_ARGUMENT;
+ * different contexts -> RNT_ERR_BASIS_MISMATCH; a key level view in any
+ * position -> RNT_ERR_UNSUPPORTED (fields 0, 0).  A refused call leaves `out`
+ * untouched.  rnt_automorphism itself is unchanged (coefficient-domain
+ * output).  Profile name: "automorph_ntt". */
+int rnt_automorphism_ntt(rnt_buf* out, const rnt_buf* in, uint64_t g);
 /* ModRaise (no reference counterpart): `in` holds B coefficient-domain polys
  * on a context C0 over q_0..q_{l0-1}, 1 <= l0 <= 4; `out` holds B polys on a
  * context C over q_0..q_{L-1}, L > l0, whose first l0 moduli equal C0's BY
@@ -531,7 +546,8 @@ int rnt_ct_mul_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, con
  * (rnt_keyswitch_hybrid, rnt_ct_rotate_hybrid, rnt_ct_mul_relin_hybrid,
  * rnt_ct_rotate_hybrid_hoisted, rnt_ct_linear_bsgs_hybrid,
  * rnt_ct_mul_relin_rescale_hybrid, rnt_ct_linear_bsgs_hybrid_rescale,
- * rnt_ct_dot_relin_hybrid, rnt_ct_dot_relin_rescale_hybrid) and of
+ * rnt_ct_dot_relin_hybrid, rnt_ct_dot_relin_rescale_hybrid), of
+ * rnt_ct_rotsum_hybrid (the key set of a rotate-and-sum) and of
  * rnt_ct_mul_relin_rescale_affine_hybrid, which shares the multiply's body, and the
  * call is then, word for word, the same call with the restricted key on a
  * root context over the view's moduli.  Both halves (and both sets of a BSGS
@@ -618,6 +634,48 @@ int rnt_ct_linear_bsgs_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, c
                               const int32_t* giant_steps, size_t n_giant, const rnt_buf* diag,
                               const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
                               const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b, size_t alpha);
+/* ---- rotate-and-sum on hybrid keys: one ModDown for many rotations
+ * (DESIGN.md "Rotate-and-sum") ------------------------------------------------
+ * The inner sum sum_t sigma_{k_t}(ct) of one stage of a slot sum.  Notation as
+ * above: C, E, beta, ModUp_d, ModDown, sigma_k.  With NZ = {t : steps[t] != 0},
+ * z = n_steps - |NZ| and D_d = ModUp_d(c1) over E:
+ *   A0   = sum_{t in NZ} sum_d sigma_{k_t}(D_d) * key_b[t][d]   (negacyclic, over
+ *          E);  A1 with key_a
+ *   out0 = z c0 + sum_{t in NZ} sigma_{k_t}(c0) + ModDown(A0)
+ *   out1 = z c1 +                                ModDown(A1)
+ * Canonical outputs, coefficient domain, over C; z x is x added z times mod
+ * q_j.  The keys are in the ORDINARY prepared form (rnt_key_prepare): the keys
+ * rnt_ct_rotate_hybrid takes for step k_t, packed as the giant keys of
+ * rnt_ct_linear_bsgs_hybrid are (n_steps * beta polys over E, step t's key at
+ * [t beta, (t + 1) beta); a step-0 slot is ignored).  With NZ empty the result
+ * is z ct, no key is read and the key buffers may be NULL.
+ * The ORDER is part of the definition: sigma stands OUTSIDE ModUp and INSIDE
+ * ModDown.  These are therefore NOT the words of a loop of rnt_ct_rotate_hybrid
+ * and rnt_add -- ModUp does not commute with negation, and a ModDown of a sum
+ * is not the sum of ModDowns -- but it decrypts the same way: sigma_k(D_d) ==
+ * sigma_k(c1) mod Q_d with coefficients below alpha Q_d in magnitude (sigma
+ * permutes coefficients up to sign), which is all the key-switch error bound
+ * of rnt_ct_rotate_hybrid asks of ModUp_d(sigma_k(c1)); so every term has that
+ * call's bound, and the ModDown error enters once instead of |NZ| times.
+ * It is also what runs: one ModUp and one forward transform of the digits for
+ * every step (in the NTT domain sigma_k is a gather, rnt_automorphism_ntt's),
+ * |NZ| key streams into ONE accumulator pair, two inverse transforms over E and
+ * two ModDowns, whatever n_steps is.  It spends no level and needs no plaintext.
+ * c0, c1, out0, out1: B polys each on C, coefficient domain.  out0 == c0 and
+ * out1 == c1 are allowed (a chain of stages runs in place); out0 == out1, an
+ * output that is the other component or aliases a key -> RNT_ERR_BAD_ARGUMENT.
+ * Every other rule and status is rnt_ct_rotate_hybrid_hoisted's: alpha, degree,
+ * device, moduli prefix, word width, key domain, RNT_ERR_CHANNEL_COUNT (fields:
+ * n_steps * beta, got), n_steps == 0 -> RNT_ERR_BAD_ARGUMENT, an NTT-domain
+ * ciphertext -> RNT_ERR_DOMAIN_MISMATCH.  A refused call leaves its outputs
+ * untouched.  Key level views are accepted in the key positions.  The library
+ * cannot tell a hoisting-form key from an ordinary one.  The first call of an
+ * (E, Lv, alpha) triple builds the constants and cannot be recorded; later
+ * calls are recordable.  Profile names: "rotsum_mac" (the key products, 8 steps
+ * a launch), "rotsum_c0" (the coefficient-domain sums). */
+int rnt_ct_rotsum_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                         const int32_t* steps, size_t n_steps,
+                         const rnt_buf* keys_a, const rnt_buf* keys_b, size_t alpha);
 /* polys [src_first, src_first + count) of src -> [dst_first, ...) of dst (same
  * context; dst takes src's domain, which must equal dst's unless the copy
  * covers all of dst).  A range outside either batch -> RNT_ERR_BAD_ARGUMENT. */

@@ -99,7 +99,7 @@ const char* const kKernelNames[rnt::K_COUNT] = {
     "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
     "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto",
     "moddown_rescale", "lincomb", "dot_tensor", "mod_raise", "mul_monomial",
-    "moddown_rescale_affine", "plain_mac"};
+    "moddown_rescale_affine", "rotsum_mac", "rotsum_c0", "automorph_ntt", "plain_mac"};
 
 // A profiling call failed: clear the runtime's slot, keep the first failure
 // in the profiler, and stop profiling (rnt_profile_read reports it).
@@ -1946,6 +1946,22 @@ static uint64_t rotation_exponent(int32_t k, uint64_t two_n) {
 extern "C" int rnt_rotate_slots(rnt_buf* out, const rnt_buf* in, int32_t k) {
   if (int rc = check_buf(in, "rnt_rotate_slots")) return rc;
   return rnt_automorphism(out, in, rotation_exponent(k, 2 * (uint64_t)in->ctx->t->n));
+}
+
+extern "C" int rnt_automorphism_ntt(rnt_buf* out, const rnt_buf* in, uint64_t g) {
+  const char* name = "rnt_automorphism_ntt";
+  if (int rc = check_buf(out, name)) return rc;
+  if (int rc = check_buf(in, name)) return rc;
+  if (int rc = check_same(out, in, name)) return rc;
+  if (!in->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the input must be in the NTT domain", name);
+  if ((g & 1) == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: the exponent must be odd, got %" PRIu64, name, g);
+  if (out == in || out->data == in->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out aliases in", name);
+  if (int rc = set_device(in->ctx)) return rc;
+  rnt::Launch k = launch_for(in);
+  LAUNCH(k.t, rnt::K_AUTOMORPH_NTT, rnt::launch_automorphism_ntt(k, out->data, in->data, g),
+         "automorphism in the NTT domain");
+  out->in_ntt = 1;
+  return RNT_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -4297,6 +4313,116 @@ extern "C" int rnt_ct_rotate_hybrid_hoisted(rnt_buf* out0, rnt_buf* out1, const 
     if (int rc = hybrid_hoist_chunk(pl, c, hw, (const char*)c1->data + p0 * n * wb, full_ls, steps, n_steps,
                                     keys_a, keys_b, finish))
       return rc;
+  }
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
+// Rotate-and-sum on hybrid keys: with NZ the steps that rotate, z the others,
+//   A0   = sum_{t in NZ} sum_d sigma_t(D_d) key_b[t][d] over E,  A1 with key_a
+//   out0 = z c0 + sum_{t in NZ} sigma_t(c0) + ModDown(A0),  out1 = z c1 + ModDown(A1)
+// with D_d = ModUp_d(c1) raised and transformed ONCE: sigma_t acts on the
+// transformed digits as a gather (k_rotsum_mac).  Per chunk: hybrid_raise, one
+// k_rotsum_mac launch per group of kRotsumT rotating steps into one A0 / A1,
+// one k_rotsum_c0 launch per group of kRotsumT steps into S (and, where z != 0,
+// one for z c1 into S1), hybrid_lower with S / S1 as ModDown's addends.
+extern "C" int rnt_ct_rotsum_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                    const int32_t* steps, size_t n_steps, const rnt_buf* keys_a,
+                                    const rnt_buf* keys_b, size_t alpha) {
+  const char* name = "rnt_ct_rotsum_hybrid";
+  const rnt_buf* all[4] = {out0, out1, c0, c1};
+  for (const rnt_buf* b : all)
+    if (int rc = check_buf(b, name)) return rc;
+  if (n_steps == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: no steps", name);
+  if (!steps) return fail(RNT_ERR_BAD_ARGUMENT, "%s: null steps", name);
+  if (alpha == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: alpha must be at least 1", name);
+  for (int i = 1; i < 4; ++i)
+    if (int rc = check_same(all[0], all[i], name)) return rc;
+  HybridPlan pl;
+  size_t nz = 0;
+  bool have = false;
+  if (int rc = hybrid_set_check(name, c0->ctx, steps, n_steps, keys_a, keys_b, alpha, &pl, &nz, &have)) return rc;
+  if (c0->in_ntt || c1->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the ciphertext must be in coefficient domain", name);
+  if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
+  const rnt_buf* ins[4] = {c0, c1, keys_a, keys_b};
+  for (int i = 0; i < 4; ++i) {
+    if (!ins[i]) continue;
+    if ((i != 0 && (out0 == ins[i] || out0->data == ins[i]->data)) ||
+        (i != 1 && (out1 == ins[i] || out1->data == ins[i]->data)))
+      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output aliases an input other than its own component", name);
+  }
+  if (int rc = set_device(c0->ctx)) return rc;
+  if (nz)
+    if (int rc = hybrid_prepare(&pl)) return rc;
+  const rnt::Launch k = launch_for(c0);
+  const rnt::Tables* tc = k.t;
+  const size_t n = tc->n, wb = word_bytes(tc), Lv = k.L, B = c0->n_polys;
+  const size_t z = n_steps - nz;
+  const uint64_t full_ls = limb_stride(c0), two_n = 2 * (uint64_t)n;
+  // ws per ciphertext: D | A0 | A1 over E (hybrid_planes(), where a step
+  // rotates) | S over C (the c0 sum) | S1 over C (z c1, where a step is 0)
+  const size_t c_planes = (z ? 2 : 1) * Lv;
+  const size_t bc = nz ? hybrid_chunk(pl, B, c_planes) : chunk_polys(tc, c_planes, B);
+  const size_t pw = Lv * bc * n * wb;
+  const size_t pe = nz ? pl.LE * bc * n * wb : 0;
+  CallWs ws(out0);
+  if (int rc = ws.get((nz ? pl.beta + 2 : 0) * pe + c_planes * bc * n * wb)) return rc;
+  char* S = (char*)ws.p + (nz ? pl.beta + 2 : 0) * pe;
+  char* S1 = z ? S + pw : nullptr;
+  for (size_t p0 = 0; p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    const uint64_t cls = (uint64_t)c * n;
+    const char* x0 = (const char*)c0->data + p0 * n * wb;
+    const char* x1 = (const char*)c1->data + p0 * n * wb;
+    char* dst0 = (char*)out0->data + p0 * n * wb;
+    char* dst1 = (char*)out1->data + p0 * n * wb;
+    rnt::Launch kc = k;
+    kc.B = c;
+    // S = z c0 + sum sigma_t(c0), kRotsumT steps a launch; S1 = z c1
+    for (size_t t = 0; t < n_steps;) {
+      uint64_t g[rnt::kRotsumT];
+      uint32_t nt = 0, zg = 0;
+      const bool first = t == 0;
+      for (size_t e = std::min(n_steps, t + rnt::kRotsumT); t < e; ++t) {
+        if (steps[t] == 0) ++zg;
+        else g[nt++] = rotation_exponent(steps[t], two_n);
+      }
+      LAUNCH(tc, rnt::K_ROTSUM_C0, rnt::launch_rotsum_c0(kc, S, x0, full_ls, nt, g, zg, !first),
+             "rotate-and-sum of c0");
+    }
+    if (z)
+      LAUNCH(tc, rnt::K_ROTSUM_C0, rnt::launch_rotsum_c0(kc, S1, x1, full_ls, 0, nullptr, (uint32_t)z, false),
+             "z c1");
+    if (!nz) {
+      LAUNCH(tc, rnt::K_COPY, rnt::launch_copy_rows(k.s, dst0, full_ls * wb, S, cls * wb, cls * wb, Lv), "z c0");
+      LAUNCH(tc, rnt::K_COPY, rnt::launch_copy_rows(k.s, dst1, full_ls * wb, S1, cls * wb, cls * wb, Lv), "z c1");
+      continue;
+    }
+    const HybridWs hw(pl, bc, ws.p);
+    if (int rc = hybrid_raise(pl, c, hw.D, x1, full_ls)) return rc;
+    rnt::Launch km = hybrid_launch(pl, c);
+    km.Ls = pl.beta;
+    bool first = true;
+    for (size_t t = 0; t < n_steps;) {
+      uint64_t g[rnt::kRotsumT];
+      const void* ka[rnt::kRotsumT] = {};
+      const void* kb[rnt::kRotsumT] = {};
+      uint32_t nt = 0;
+      for (; t < n_steps && nt < rnt::kRotsumT; ++t) {
+        if (steps[t] == 0) continue;
+        g[nt] = rotation_exponent(steps[t], two_n);
+        ka[nt] = (const char*)keys_a->data + t * key_step_polys(keys_a, pl) * n * wb;
+        kb[nt] = (const char*)keys_b->data + t * key_step_polys(keys_b, pl) * n * wb;
+        ++nt;
+      }
+      if (nt == 0) break;
+      LAUNCH_ON(tc, km.s, rnt::K_ROTSUM_MAC,
+                rnt::launch_rotsum_mac(km, hw.A0, hw.A1, nt, g, hw.D, ka, kb, limb_stride(keys_a), !first),
+                "rotate-and-sum key products");
+      first = false;
+    }
+    if (int rc = hybrid_lower(pl, c, hw.A0, hw.A1, dst0, dst1, full_ls, S, S1, cls, false)) return rc;
   }
   out0->in_ntt = out1->in_ntt = 0;
   return RNT_OK;

@@ -185,7 +185,7 @@ enum KernelId {
   K_SFFT, K_SAMPLE, K_COPY, K_PLANE_FUSED, K_MF_NTT_FWD, K_MF_NTT_INV, K_WHOLE_FWD, K_WHOLE_INV, K_WHOLE_MUL,
   K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_MODUP, K_MODDOWN,
   K_MODDOWN_AUTO, K_MODDOWN_RESCALE, K_LINCOMB, K_DOT_TENSOR, K_MOD_RAISE, K_MUL_MONOMIAL,
-  K_MODDOWN_RESCALE_AFFINE, K_PLAIN_MAC, K_COUNT
+  K_MODDOWN_RESCALE_AFFINE, K_ROTSUM_MAC, K_ROTSUM_C0, K_AUTOMORPH_NTT, K_PLAIN_MAC, K_COUNT
 };
 
 struct Prof {
@@ -441,6 +441,23 @@ hipError_t launch_hoist_mac(const Launch& k, void* const* acc0, void* const* acc
 // giant stage of rnt_ct_linear_bsgs_hybrid, one A0 / A1 over several launches.
 hipError_t launch_hoist_mac_acc(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt, const void* d,
                                 const void* const* key_a, const void* const* key_b, uint64_t key_ls);
+// The automorphism in the NTT domain and the rotate-and-sum built on it
+// (rnt_automorphism_ntt, rnt_ct_rotsum_hybrid).  launch_automorphism_ntt
+// (k_automorph_ntt): out = the NTT-domain words of sigma_g(in), g odd, out not
+// in.  launch_rotsum_mac (k_rotsum_mac), nt <= kRotsumT steps in one launch:
+// acc0 (+)= sum_t sum_d sigma_{g[t]}(D^[j][d]) (.) key_b[t][d][j], acc1 with
+// key_a; D the block launch_modup wrote, transformed (k.src_limbs() = beta);
+// key_*[t] points at step t's ORDINARY key (digit d at + d N words, limb j at
+// + j key_ls), read through the limb map; accum: added to what acc0 / acc1
+// hold.  launch_rotsum_c0 (k_rotsum_c0): out = z x + sum_{t < nt} sigma_{g[t]}(x)
+// in the coefficient domain over k.L limbs, x at limb stride x_ls, out at the
+// chunk's own; accum: added to out.
+constexpr uint32_t kRotsumT = 8;
+hipError_t launch_automorphism_ntt(const Launch& k, void* out, const void* in, uint64_t g);
+hipError_t launch_rotsum_mac(const Launch& k, void* acc0, void* acc1, uint32_t nt, const uint64_t* g, const void* d,
+                             const void* const* key_a, const void* const* key_b, uint64_t key_ls, bool accum);
+hipError_t launch_rotsum_c0(const Launch& k, void* out, const void* x, uint64_t x_ls, uint32_t nt, const uint64_t* g,
+                            uint32_t z, bool accum);
 // Hybrid key-switching (rnt_keyswitch_hybrid).  k.t is the KEY basis' tables,
 // k.L = Lv + K its limbs, k.B the chunk's polys.  These launchers and the three
 // launch_hoist_mac* read the limb constants and the key planes through the limb

@@ -427,6 +427,142 @@ k_hoist_mac_acc(HoistArgs<W> a, const W* __restrict__ d, TabPtrs<W> tp, uint32_t
   }
 }
 
+// The automorphism sigma_g (g odd) in the NTT domain is a pure permutation of
+// evaluation points, with no sign: sigma_g(a)(psi^(2k+1)) = a(psi^(g (2k+1))),
+// and the device holds device[brv(k)] = a(psi^(2k+1)) (rnt_internal.hpp).  So
+// position p of the output reads position
+//   brv(((g (2 brv(p) + 1) mod 2N) - 1) / 2)
+// of the input.  The map is a bijection and BLOCK-STRUCTURED: for every m an
+// aligned block of 2^m positions reads from one aligned block of 2^m positions
+// (the top log_n - m bits of p are the low bits of k, and g (2k + 1) mod
+// 2^(log_n - m + 1) depends on those alone), permuted inside.  A wave of 64
+// lanes x 16 bytes therefore gathers from exactly one aligned span of its own
+// size: word-granular loads, but every cache line fetched is used whole.
+// tests/test_rotsum_ref.py pins both properties.  g < 2N <= 2^18; the product
+// wraps mod 2^32, a multiple of 2N.
+__device__ __forceinline__ uint32_t ntt_automorph_src(uint32_t p, uint32_t g, uint32_t log_n) {
+  const uint32_t sh = 32u - log_n;
+  const uint32_t k = __brev(p) >> sh;
+  const uint32_t e = (g * (2u * k + 1u)) & ((2u << log_n) - 1u);
+  return __brev(e >> 1) >> sh;
+}
+
+// out = the NTT-domain words of sigma_g(in), in in the NTT domain (g odd): the
+// gather above within every plane.  Grid as k_elementwise (x = the words of a
+// limb's chunk, y = limb), one word per thread.
+template <class W>
+__global__ void __launch_bounds__(256)
+k_automorph_ntt(W* __restrict__ out, const W* __restrict__ in, uint32_t log_n, uint32_t g, uint64_t limb_words) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= limb_words) return;
+  const uint64_t N = 1ull << log_n;
+  const uint64_t base = (uint64_t)blockIdx.y * limb_words + (i & ~(N - 1));
+  out[base + (i & (N - 1))] = in[base + ntt_automorph_src((uint32_t)(i & (N - 1)), g, log_n)];
+}
+
+// The key products of a rotate-and-sum (rnt_ct_rotsum_hybrid) for up to
+// ROTSUM_T steps of one chunk in the NTT domain:
+//   acc0 (+)= sum_{t < nt} sum_s sigma_{g_t}(D^[j][s]) (.) key_b[t][s],  acc1 with key_a.
+// d is the transformed Montgomery-form digits ([L][Ls][B][N], hybrid_raise);
+// the keys are ORDINARY prepared keys, key_*[t] pointing at (digit 0, limb 0)
+// of step t's key: digit s at + s N, limb j at + j key_ls, the same plane for
+// every poly of the batch.  Grid as k_hoist_mac; a thread owns one vector
+// position and the two accumulators.  Per step it computes its V source
+// positions once (ntt_automorph_src), then per digit gathers the V digit words
+// at them inside the poly's own plane, streams the two key vectors and adds the
+// Montgomery products -- canonical, as in k_hoist_mac.  The steps run in a loop
+// over the table in the kernel arguments, so the registers do not grow with
+// ROTSUM_T.  ACC: the sums start from what acc0 / acc1 hold (the groups after
+// the first).
+constexpr int ROTSUM_T = (int)kRotsumT;
+
+template <class W>
+struct RotsumArgs {
+  const W* key_b[ROTSUM_T];
+  const W* key_a[ROTSUM_T];
+  uint32_t g[ROTSUM_T];
+};
+template <class W, bool VEC, bool ACC>
+__global__ void __launch_bounds__(256)
+k_rotsum_mac(W* acc0, W* acc1, RotsumArgs<W> a, const W* __restrict__ d, TabPtrs<W> tp, uint32_t log_n,
+             uint64_t limb_words, uint64_t key_ls, uint32_t Ls, uint32_t nt, LimbMap lm) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint32_t j = blockIdx.y;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= limb_words) return;
+  const uint32_t rj = root_limb(j, lm);
+  const LimbConst<W> lc = tp.lc[rj];
+  const uint64_t N = 1ull << log_n;
+  const uint32_t p0 = (uint32_t)(i & (N - 1));  // V divides N: one plane
+  const W* dp = d + (uint64_t)j * Ls * limb_words + (i - p0);
+  const uint64_t ko = (uint64_t)rj * key_ls + p0;
+  const uint64_t o = (uint64_t)j * limb_words + i;
+  W s0[V], s1[V];
+  if constexpr (ACC) {
+    ld_vec<W, VEC, V>(s0, acc0 + o);
+    ld_vec<W, VEC, V>(s1, acc1 + o);
+  } else {
+#pragma unroll
+    for (int v = 0; v < V; ++v) s0[v] = s1[v] = (W)0;
+  }
+  for (uint32_t t = 0; t < nt; ++t) {  // (uniform)
+    const uint32_t g = a.g[t];
+    uint32_t src[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) src[v] = ntt_automorph_src(p0 + (uint32_t)v, g, log_n);
+    const W* bq = a.key_b[t] + ko;
+    const W* aq = a.key_a[t] + ko;
+    for (uint32_t s = 0; s < Ls; ++s) {
+      const W* ds = dp + (uint64_t)s * limb_words;
+      W xv[V], bv[V], av[V];
+#pragma unroll
+      for (int v = 0; v < V; ++v) xv[v] = ds[src[v]];
+      ld_vec<W, VEC, V>(bv, bq + (uint64_t)s * N);
+      ld_vec<W, VEC, V>(av, aq + (uint64_t)s * N);
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        s0[v] = add_mod<W>(s0[v], mont_mul<W>(xv[v], bv[v], lc.q, lc.qinv), lc.q);
+        s1[v] = add_mod<W>(s1[v], mont_mul<W>(xv[v], av[v], lc.q, lc.qinv), lc.q);
+      }
+    }
+  }
+  st_vec<W, VEC, V>(acc0 + o, s0);
+  st_vec<W, VEC, V>(acc1 + o, s1);
+}
+
+// The coefficient-domain addend of a rotate-and-sum over the ciphertext's
+// limbs: out[i] = z x[i] + sum_{t < nt} +-x[i g_t^-1 mod 2N] (k_automorph_odd's
+// gather summed over the steps of a launch), canonical; z x is x added z times.
+// x at limb stride x_ls, out at the chunk's own (limb_words).  ACC: added to
+// what out holds.  Grid as k_elementwise, one word per thread.
+struct RotsumC0Args {
+  uint32_t ginv[ROTSUM_T];
+};
+template <class W, bool ACC>
+__global__ void __launch_bounds__(256)
+k_rotsum_c0(W* out, const W* __restrict__ x, RotsumC0Args a, TabPtrs<W> tp, uint32_t log_n, uint64_t limb_words,
+            uint64_t x_ls, uint32_t nt, uint32_t z) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= limb_words) return;
+  const uint32_t l = blockIdx.y;
+  const W q = tp.lc[l].q;
+  const uint64_t N = 1ull << log_n;
+  const uint32_t jo = (uint32_t)(i & (N - 1));
+  const W* xp = x + (uint64_t)l * x_ls + (i - jo);
+  W s = ACC ? out[(uint64_t)l * limb_words + i] : (W)0;
+  if (z != 0) {  // (uniform)
+    const W c = xp[jo];
+    for (uint32_t r = 0; r < z; ++r) s = add_mod<W>(s, c, q);
+  }
+  for (uint32_t t = 0; t < nt; ++t) {  // (uniform)
+    const uint32_t e = (jo * a.ginv[t]) & (uint32_t)(2 * N - 1);
+    W c = xp[e & (uint32_t)(N - 1)];
+    if (e >= N) c = c == 0 ? (W)0 : (W)(q - c);
+    s = add_mod<W>(s, c, q);
+  }
+  out[(uint64_t)l * limb_words + i] = s;
+}
+
 
 // ModUp of the hybrid key-switch: digit d = blockIdx.y owns the cnt <= alpha
 // source limbs from d alpha on.  A thread reads its vector of each of them
@@ -1461,6 +1597,81 @@ hipError_t launch_hoist_mac(const Launch& k, void* const* acc0, void* const* acc
 hipError_t launch_hoist_mac_acc(const Launch& k, void* const* acc0, void* const* acc1, uint32_t nt, const void* d,
                                 const void* const* key_a, const void* const* key_b, uint64_t key_ls) {
   return hoist_mac(k, acc0, acc1, nt, d, key_a, key_b, key_ls, true);
+}
+
+static uint64_t inv_mod_pow2(uint64_t h, uint64_t M);
+
+hipError_t launch_automorphism_ntt(const Launch& k, void* out, const void* in, uint64_t g) {
+  return by_word(k, [&](auto w) -> hipError_t {
+    using W = decltype(w);
+    const uint64_t N = 1ull << k.t->log_n;
+    const uint64_t limb_words = (uint64_t)k.B * N;
+    if ((g & 1) == 0 || out == in) return hipErrorInvalidValue;
+    if (limb_words == 0 || k.L == 0) return hipSuccess;
+    const uint64_t bx = blocks_x<W>(limb_words, false);
+    if (!grid_ok(bx, k.L)) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL((k_automorph_ntt<W>), dim3((unsigned)bx, (unsigned)k.L), dim3(256), 0, k.s, (W*)out,
+                       (const W*)in, k.t->log_n, (uint32_t)(g & (2 * N - 1)), limb_words);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_rotsum_mac(const Launch& k, void* acc0, void* acc1, uint32_t nt, const uint64_t* g, const void* d,
+                             const void* const* key_a, const void* const* key_b, uint64_t key_ls, bool accum) {
+  return by_word(k, [&](auto w) -> hipError_t {
+    using W = decltype(w);
+    const uint64_t N = 1ull << k.t->log_n;
+    const uint64_t limb_words = (uint64_t)k.B * N;
+    const size_t Ls = k.src_limbs();
+    if (nt == 0 || nt > (uint32_t)ROTSUM_T || Ls == 0 || key_ls < Ls * N || !limb_map_ok(k))
+      return hipErrorInvalidValue;
+    if (limb_words == 0 || k.L == 0) return hipSuccess;
+    RotsumArgs<W> a{};
+    uintptr_t align = ptr_bits(d, acc0, acc1);
+    for (uint32_t t = 0; t < nt; ++t) {
+      if ((g[t] & 1) == 0) return hipErrorInvalidValue;
+      a.key_a[t] = (const W*)key_a[t];
+      a.key_b[t] = (const W*)key_b[t];
+      a.g[t] = (uint32_t)(g[t] & (2 * N - 1));
+      align |= ptr_bits(key_a[t], key_b[t]);
+    }
+    // 16-byte accesses: whole vectors within a plane, every plane and block 16-byte aligned
+    const bool vec = vec_ok<W>(N, {key_ls}, align);
+    const uint64_t bx = blocks_x<W>(limb_words, vec);
+    if (!grid_ok(bx, k.L)) return hipErrorInvalidConfiguration;
+    const dim3 grid((unsigned)bx, (unsigned)k.L);
+    with_bool(accum, [&](auto ACC) {
+      with_bool(vec, [&](auto VEC) {
+        hipLaunchKernelGGL((k_rotsum_mac<W, decltype(VEC)::value, decltype(ACC)::value>), grid, dim3(256), 0, k.s,
+                           (W*)acc0, (W*)acc1, a, (const W*)d, tab_ptrs<W>(k.t), k.t->log_n, limb_words, key_ls,
+                           (uint32_t)Ls, nt, limb_map(k));
+      });
+    });
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_rotsum_c0(const Launch& k, void* out, const void* x, uint64_t x_ls, uint32_t nt, const uint64_t* g,
+                            uint32_t z, bool accum) {
+  return by_word(k, [&](auto w) -> hipError_t {
+    using W = decltype(w);
+    const uint64_t N = 1ull << k.t->log_n;
+    const uint64_t limb_words = (uint64_t)k.B * N;
+    if (nt > (uint32_t)ROTSUM_T || x_ls < limb_words || out == x) return hipErrorInvalidValue;
+    if (limb_words == 0 || k.L == 0) return hipSuccess;
+    RotsumC0Args a{};
+    for (uint32_t t = 0; t < nt; ++t) {
+      if ((g[t] & 1) == 0) return hipErrorInvalidValue;
+      a.ginv[t] = (uint32_t)inv_mod_pow2(g[t] & (2 * N - 1), 2 * N);
+    }
+    const uint64_t bx = blocks_x<W>(limb_words, false);
+    if (!grid_ok(bx, k.L)) return hipErrorInvalidConfiguration;
+    with_bool(accum, [&](auto ACC) {
+      hipLaunchKernelGGL((k_rotsum_c0<W, decltype(ACC)::value>), dim3((unsigned)bx, (unsigned)k.L), dim3(256), 0, k.s,
+                         (W*)out, (const W*)x, a, tab_ptrs<W>(k.t), k.t->log_n, limb_words, x_ls, nt, z);
+    });
+    return hipGetLastError();
+  });
 }
 
 // The hybrid launchers: k.t the key basis' tables, k.L = Lv + K, k.B the

@@ -29,6 +29,7 @@ from ._lib import RnsNttError, check, load
 from .homdft import HomDftPlan, homdft_plan
 from .poly_eval import PolyEvalPlan, poly_eval_plan, poly_eval_plan_fused
 from .evalmod import EvalModPlan, evalmod_plan
+from .rotsum import RotsumPlan, rotsum_plan
 
 __all__ = [
     "device_count",
@@ -42,6 +43,10 @@ __all__ = [
     "mul_ciphertexts_hybrid",
     "RnsHybridKeySet",
     "rotate_ciphertext_hybrid_hoisted",
+    "rotsum_ciphertext_hybrid",
+    "automorphism_ntt",
+    "rotsum_plan",
+    "RotsumPlan",
     "linear_transform_hybrid",
     "linear_transform_bsgs_hybrid",
     "mul_ciphertexts_hybrid_rescale",
@@ -604,6 +609,10 @@ class RnsPoly:
         check(load().rnt_rotate_slots(out._h, self._h, k))
         return out
 
+    def automorphism_ntt(self, exponent: int, out: Optional["RnsPoly"] = None) -> "RnsPoly":
+        """:func:`automorphism_ntt` of this NTT-domain polynomial."""
+        return automorphism_ntt(self, exponent, out)
+
     # -- PolyRing::to_coeffs (poly.rs:404-427) ------------------------------
     def to_coeffs(self) -> np.ndarray:
         """PolyRing::to_coeffs (poly.rs:404-427): the centred CRT value of each
@@ -1047,6 +1056,37 @@ def rotate_ciphertext_hybrid_hoisted(ct: Ciphertext, keyset: RnsHybridKeySet,
     check(load().rnt_ct_rotate_hybrid_hoisted(out.c0.handle, out.c1.handle, ct.c0.handle, ct.c1.handle, steps,
                                               len(keyset.steps), keyset.a.handle if keyset.a is not None else None,
                                               keyset.b.handle if keyset.b is not None else None, keyset.alpha))
+    return out
+
+
+def automorphism_ntt(poly: RnsPoly, g: int, out: Optional[RnsPoly] = None) -> RnsPoly:
+    """``X -> X^g`` (g odd) on an NTT-domain polynomial without leaving the
+    domain (rnt_automorphism_ntt): the words of
+    ``to_ntt(automorphism(to_coeff(poly), g))``, word for word, by one gather.
+    ``out`` must not be ``poly``."""
+    if out is None:
+        out = poly._like()
+    check(load().rnt_automorphism_ntt(out.handle, poly.handle, int(g)))
+    return out
+
+
+def rotsum_ciphertext_hybrid(ct: Ciphertext, keyset: RnsHybridKeySet, out: Optional[Ciphertext] = None) -> Ciphertext:
+    """``sum_t rotate(ct, keyset.steps[t])`` for every ciphertext of the batch
+    (rnt_ct_rotsum_hybrid): one ModUp and one forward transform for every step,
+    the key products of all steps summed over the extended basis and divided
+    by P once.  A step of 0 adds the ciphertext itself.  ``keyset`` holds
+    ORDINARY prepared keys.  It spends no level and no scale; ``out`` may be
+    ``ct`` (a chain of stages runs in place).  The same decryption as a chain
+    of ``rotate_ciphertext_hybrid`` and additions with less ModDown error, not
+    its words."""
+    _require_hybrid_set(keyset, False, "rotsum_ciphertext_hybrid")
+    keyset = _at_ct_level(keyset, ct.c0.basis)
+    if out is None:
+        out = Ciphertext(ct.c0._like(), ct.c0._like(), ct.logp, ct.logq)
+    steps = (ctypes.c_int32 * len(keyset.steps))(*keyset.steps)
+    check(load().rnt_ct_rotsum_hybrid(out.c0.handle, out.c1.handle, ct.c0.handle, ct.c1.handle, steps,
+                                      len(keyset.steps), keyset.a.handle if keyset.a is not None else None,
+                                      keyset.b.handle if keyset.b is not None else None, keyset.alpha))
     return out
 
 

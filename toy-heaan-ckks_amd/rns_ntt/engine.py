@@ -31,7 +31,8 @@ from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadge
                linear_transform_hybrid, load, mul_ciphertexts_gadget, mul_ciphertexts_hybrid,
                mul_ciphertexts_hybrid_rescale, mul_ciphertexts_hybrid_rescale_affine, poly_eval_plan,
                poly_eval_plan_fused, rescale_ciphertext, rotate_ciphertext,
-               rotate_ciphertext_hoisted, rotate_ciphertext_hybrid, rotate_ciphertext_hybrid_hoisted)
+               rotate_ciphertext_hoisted, rotate_ciphertext_hybrid, rotate_ciphertext_hybrid_hoisted,
+               rotsum_ciphertext_hybrid)
 
 
 @dataclass
@@ -262,6 +263,35 @@ class CkksEngine:
         steps with one ModUp: a batch of ``n_steps * B``, rotation t of
         ciphertext b at ``t * B + b``."""
         return rotate_ciphertext_hybrid_hoisted(ct, keyset)
+
+    def generate_rotsum_key_sets(self, sk: RnsPoly, plan, rng, alpha: int) -> list:
+        """One ORDINARY hybrid key set per stage of a ``rotsum_plan`` (its
+        steps, the leading 0 without a key), for ``inner_sum_hybrid``.  The
+        caller's trade-off is the plan's radix: radix 2 needs ``log2 n`` keys
+        and ``log2 n`` ModUps, radix r ``(r - 1) log_r n`` keys and ``log_r n``
+        ModUps; a key is ``2 beta (Lv + K)`` planes (72 MiB at 2^16 x (16 + 2)
+        limbs, alpha = 2, 32-bit words)."""
+        if plan.stages[-1][-1] >= self.degree // 2:
+            raise ValueError("generate_rotsum_key_sets: a step of the plan reaches the ring's N/2 slots")
+        return [self.generate_hybrid_rotation_key_set(sk, st, rng, alpha) for st in plan.stages]
+
+    @staticmethod
+    def inner_sum_hybrid(ct: Ciphertext, plan, keysets) -> Ciphertext:
+        """``sum_{t < plan.n} rotate(ct, t plan.stride)``: slot j of the result
+        holds the sum of slots ``j, j + stride, ..., j + (n - 1) stride`` of
+        ``ct`` (indices mod N/2).  One ``rotsum_ciphertext_hybrid`` per stage of
+        the plan, the stages after the first in place on one output
+        ciphertext.  Scale and level are unchanged: no plaintext, no
+        rescale."""
+        if len(keysets) != len(plan.stages):
+            raise ValueError(f"inner_sum_hybrid: {len(keysets)} key sets for {len(plan.stages)} stages")
+        for u, (ks, st) in enumerate(zip(keysets, plan.stages)):
+            if list(ks.steps) != list(st):
+                raise ValueError(f"inner_sum_hybrid: the key set of stage {u} is not for the plan's steps")
+        out = None
+        for ks in keysets:
+            out = rotsum_ciphertext_hybrid(ct if out is None else out, ks, out=out)
+        return out
 
     @staticmethod
     def linear_transform_hybrid(ct: Ciphertext, diag_plaintexts: Plaintext, keyset: RnsHybridKeySet) -> Ciphertext:
