@@ -22,7 +22,7 @@ DEP_rnt_mfma    := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_hostmath.hpp $(CSRC)/rnt
 DEP_rnt_encode  := $(CSRC)/rnt_internal.hpp
 DEP_rnt_sample  := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp
 DEP_rnt_raise   := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_modarith.hpp $(CSRC)/rnt_device.hpp $(CSRC)/rnt_launch.hpp
-DEP_rnt_api     := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_hostmath.hpp include/rnsntt.h
+DEP_rnt_api     := $(CSRC)/rnt_internal.hpp $(CSRC)/rnt_hostmath.hpp $(CSRC)/rnt_ws.hpp include/rnsntt.h
 
 OBJS := $(LIBDIR)/rnt_col.o $(LIBDIR)/rnt_rows.o $(LIBDIR)/rnt_kernels.o \
         $(LIBDIR)/rnt_plane.o $(LIBDIR)/rnt_mfma.o $(LIBDIR)/rnt_encode.o $(LIBDIR)/rnt_sample.o $(LIBDIR)/rnt_raise.o \

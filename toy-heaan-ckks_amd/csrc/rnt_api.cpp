@@ -19,6 +19,7 @@
 #include "../../include/rnsntt.h"
 #include "rnt_hostmath.hpp"
 #include "rnt_internal.hpp"
+#include "rnt_ws.hpp"
 
 namespace {
 
@@ -502,11 +503,13 @@ struct CallWs {
   explicit CallWs(const rnt_buf* b) : CallWs(b->ctx) {}
   CallWs(const CallWs&) = delete;
   CallWs& operator=(const CallWs&) = delete;
-  int get(size_t need) {
+  // A block of the layout's total (`floor` bytes at the least), the layout placed in it.
+  int get(rnt::WsLayout& w, size_t floor = 0) {
     size_t got = 0;
-    if (hipError_t e = pool_malloc(dev, need, s, &p, &got, true); e != hipSuccess)
+    if (hipError_t e = pool_malloc(dev, w.total(floor), s, &p, &got, true); e != hipSuccess)
       return hip_fail(e, "hipMalloc(workspace)");
     bytes = got;
+    w.place(p);
     return RNT_OK;
   }
   ~CallWs() {
@@ -2155,6 +2158,8 @@ struct GadgetKey {
 size_t chunk_polys(const rnt::Tables* t, size_t planes, size_t B) {
   return std::min(B, std::max<size_t>(t->ks_ws_bytes / (planes * t->n * word_bytes(t)), 1));
 }
+// The chunk of the calls whose whole layout is to fit the cap (the hybrid family, the plain MAC), set on the layout.
+size_t fit_chunk(const rnt::Tables* t, rnt::WsLayout& w, size_t B) { return w.chunk(chunk_polys(t, w.planes, B)).bc; }
 
 // The chunk of the calls that bound S ([L][L][Bc][N]) alone.  (The whole-plane
 // key-switch has no S: its chunk is bounded by the ct-mul's seven chunk-local
@@ -2163,21 +2168,18 @@ size_t ks_chunk(const rnt::Tables* t, size_t L, size_t B) {
   return chunk_polys(t, rnt::ks_whole_ok(t) ? 7 * L : L * L, B);
 }
 
-// The key-switch scratch of a chunk of kc.B polys, kc.L target limbs over
-// kc.src_limbs() source limbs, carved from one block: the decomposition S
-// ([Lt][Ls][Bc][N]) | the NTT-row accumulators U0 | U1 ([Lt][Bc][N], limb
-// stride ls).  gadget_ws_words() is its size for a chunk of bc polys; the
-// whole-plane key-switch has none.
-size_t gadget_ws_words(const rnt::Tables* t, size_t Lt, size_t Ls, size_t bc) {
-  return rnt::ks_whole_ok(t) ? 0 : (Lt * Ls + 2 * Lt) * bc * t->n;
+// A layout over the words of t's basis; its gadget scratch (rnt::gadget_ws), Lt target limbs over Ls.
+rnt::WsLayout ws_layout(const rnt::Tables* t) { return rnt::WsLayout(t->n, word_bytes(t)); }
+rnt::WsLayout gadget_ws(const rnt::Tables* t, size_t Lt, size_t Ls) {
+  return rnt::gadget_ws(t->n, word_bytes(t), Lt, Ls, rnt::ks_whole_ok(t));
 }
+// The gadget scratch of a chunk of kc.B polys, carved at ws (limb stride ls).
 struct GadgetWs {
   char *S, *U0, *U1;
   uint64_t ls;
-  GadgetWs(const rnt::Launch& kc, void* ws) : S((char*)ws), ls((uint64_t)kc.B * kc.t->n) {
-    const size_t acc = kc.L * ls * word_bytes(kc.t);
-    U0 = S + kc.src_limbs() * acc;
-    U1 = U0 + acc;
+  GadgetWs(const rnt::Launch& kc, void* ws) : ls((uint64_t)kc.B * kc.t->n) {
+    const rnt::WsLayout w = gadget_ws(kc.t, kc.L, kc.src_limbs()).chunk(kc.B).place(ws);
+    S = w.at(rnt::WS_S), U0 = w.at(rnt::WS_U0), U1 = w.at(rnt::WS_U1);
   }
 };
 
@@ -2279,13 +2281,14 @@ extern "C" int rnt_keyswitch(rnt_buf* acc0, rnt_buf* acc1, const rnt_buf* d, con
   const size_t L = k.L, wb = word_bytes(k.t);
   const size_t bc = ks_chunk(k.t, L, d->n_polys);
   const uint64_t ls = limb_stride(d);
+  rnt::WsLayout w = ws_layout(k.t).sub(gadget_ws(k.t, L, L)).chunk(bc);
   CallWs ws(acc0);
-  if (int rc = ws.get(std::max<size_t>(gadget_ws_words(k.t, L, L, bc) * wb, 16))) return rc;
+  if (int rc = ws.get(w, 16)) return rc;
   for (size_t p0 = 0; p0 < d->n_polys; p0 += bc) {
     rnt::Launch kc = k;
     kc.B = std::min(bc, d->n_polys - p0);
     const size_t off = p0 * k.t->n * wb;
-    if (int rc = gadget_chunk_run(kc, ws.p, (const char*)d->data + off, ls, GadgetKey(key_a, key_b),
+    if (int rc = gadget_chunk_run(kc, w.at(0), (const char*)d->data + off, ls, GadgetKey(key_a, key_b),
                                   (char*)acc0->data + off, (char*)acc1->data + off, ls, nullptr, nullptr, 0, nullptr))
       return rc;
   }
@@ -2317,17 +2320,18 @@ extern "C" int rnt_keyswitch_ext(rnt_buf* acc0, rnt_buf* acc1, const void* src, 
   // polys per chunk: S is [Lt][Ls][Bc][N]; the whole-plane key-switch (2^10 <=
   // N <= 2^14) has no S and takes the whole batch in one launch
   const bool whole = rnt::ks_whole_ok(k.t);
-  const size_t bc = whole ? B : chunk_polys(k.t, Lt * Ls, B);
+  const size_t bc = whole ? B : chunk_polys(k.t, Lt * Ls, B);  // (S alone, not the layout's total)
+  rnt::WsLayout w = ws_layout(k.t).sub(gadget_ws(k.t, Lt, Ls)).chunk(bc);
   CallWs ws(acc0);
   if (!whole)
-    if (int rc = ws.get(gadget_ws_words(k.t, Lt, Ls, bc) * wb)) return rc;
+    if (int rc = ws.get(w)) return rc;
   for (size_t p0 = 0; p0 < B; p0 += bc) {
     rnt::Launch kc = k;
     kc.B = std::min(bc, B - p0);
     const size_t off = p0 * n * wb;
     const char* i0 = init0 ? (const char*)init0->data + off : nullptr;
     const char* i1 = init1 ? (const char*)init1->data + off : nullptr;
-    if (int rc = gadget_chunk_run(kc, ws.p, (const char*)src + off, src_ls, GadgetKey(key_a, key_b),
+    if (int rc = gadget_chunk_run(kc, w.at(0), (const char*)src + off, src_ls, GadgetKey(key_a, key_b),
                                   (char*)acc0->data + off, (char*)acc1->data + off, full_ls, i0, i1, full_ls, nullptr))
       return rc;
   }
@@ -2405,15 +2409,17 @@ extern "C" int rnt_ct_tensor(rnt_buf* d0, rnt_buf* d1, rnt_buf* d2, const rnt_bu
         return fail(RNT_ERR_BAD_ARGUMENT, "rnt_ct_tensor: outputs must not alias other operands");
   if (int rc = set_device(c0->ctx)) return rc;
   rnt::Launch k = launch_for(c0);
-  const size_t plane = k.t->n * word_bytes(k.t), block = k.L * c0->n_polys * plane;
   const uint64_t ls = limb_stride(c0);
   const size_t nt = tensor_blocks(k);
-  CallWs ws(d0);
   // (the matrix-core tensor's scratch at its own size, not a whole block)
+  rnt::WsLayout w = ws_layout(k.t).chunk(c0->n_polys);
+  if (nt == 1) w.bytes(rnt::plane_scratch_planes((uint64_t)k.L * c0->n_polys) * k.t->n * word_bytes(k.t));
+  else w.blocks(k.L, nt);
+  CallWs ws(d0);
   if (nt)
-    if (int rc = ws.get(nt == 1 ? rnt::plane_scratch_planes((uint64_t)k.L * c0->n_polys) * plane : 4 * block)) return rc;
+    if (int rc = ws.get(w)) return rc;
   char* T[4] = {};
-  for (size_t i = 0; i < nt; ++i) T[i] = (char*)ws.p + i * block;
+  for (size_t i = 0; i < nt; ++i) T[i] = w.at(0, i);
   if (int rc = tensor(k, T, d0->data, d1->data, d2->data, ls, c0->data, c1->data, c0p->data, c1p->data, ls)) return rc;
   d0->in_ntt = d1->in_ntt = 1;
   d2->in_ntt = 0;
@@ -2431,29 +2437,18 @@ static int ct_mul_relin_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
   if (int rc = set_device(c0->ctx)) return rc;
   rnt::Launch k = launch_for(c0);
   const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
-  const size_t bc = ks_chunk(k.t, L, B);
-  // ws: [T0..T3 (column outputs, chunk-local)] | D0 | D1 | D2 | key-switch (S|U0|U1)
-  // [| LAST0 | LAST1 with resc]
-  // (the whole-plane tensor reads the ciphertexts directly: no T)
-  const size_t chunk_words = L * bc * n;
+  const size_t bc = ks_chunk(k.t, L, B);  // (S alone, not the layout's total)
   const size_t nt = tensor_blocks(k);
   // the key-switch's diagonal from the tensor's d2^ (one more chunk plane
   // set, D2H): the four-step key-switch on tiled grids, whose tensor writes it
   const bool diag = k.t->ks_diag && nt != 0 && !rnt::ks_whole_ok(k.t) && rnt::col_resc_ok(k.t);
-  const size_t ks_words = gadget_ws_words(k.t, L, L, bc);
-  const size_t need = ((nt + 3 + (diag ? 1 : 0)) * chunk_words + ks_words + (resc ? 2 * bc * n : 0)) * wb;
+  rnt::WsLayout w = rnt::mul_relin_ws(n, wb, L, nt, rnt::ks_whole_ok(k.t), resc, diag).chunk(bc);
   CallWs cws(out0);
-  if (int rc = cws.get(need)) return rc;
-  char* ws = (char*)cws.p;
-  char* T[4];
-  for (int i = 0; i < 4; ++i) T[i] = ws + i * chunk_words * wb;
-  char* D0 = ws + nt * chunk_words * wb;
-  char* D1 = D0 + chunk_words * wb;
-  char* D2 = D1 + chunk_words * wb;
-  char* KS = D2 + chunk_words * wb;
-  char* LAST0 = KS + ks_words * wb;  // (resc)
-  char* LAST1 = LAST0 + bc * n * wb;
-  char* D2H = diag ? KS + ks_words * wb + (resc ? 2 * bc * n * wb : 0) : nullptr;
+  if (int rc = cws.get(w)) return rc;
+  char* T[4] = {};
+  for (size_t i = 0; i < nt; ++i) T[i] = w.at(rnt::MR_T, i);
+  char *D0 = w.at(rnt::MR_D, 0), *D1 = w.at(rnt::MR_D, 1), *D2 = w.at(rnt::MR_D, 2);
+  char *KS = w.at(rnt::MR_KS), *LAST0 = w.at(rnt::MR_LAST, 0), *LAST1 = w.at(rnt::MR_LAST, 1), *D2H = w.at(rnt::MR_D2H);
   const uint64_t full_ls = limb_stride(c0);
   const GadgetKey key(key_a, key_b);
   for (size_t p0 = 0; p0 < B; p0 += bc) {
@@ -2667,8 +2662,7 @@ int ct_rotate_body(const rnt_ctx* ctx, size_t B, void* out0, void* out1, const v
   const size_t words = L * B * n;
   const uint64_t ls = (uint64_t)B * n, two_n = 2 * (uint64_t)n;
   const uint64_t g = rotation_exponent(kk, two_n);
-  // ws: SIG0 | SIG1 | [TMP when an input is NTT-domain] | key-switch chunk space
-  const size_t bc = ks_chunk(k.t, L, B);
+  const size_t bc = ks_chunk(k.t, L, B);  // (S alone, not the layout's total)
   // sigma(c0) needs no launch of its own on the tiled four-step key-switch:
   // its inverse column pass gathers it from c0 as it adds it (k_colt_inv's
   // addend with g^-1 mod 2N).  Only for one ciphertext by default
@@ -2679,13 +2673,12 @@ int ct_rotate_body(const rnt_ctx* ctx, size_t B, void* out0, void* out1, const v
   // workgroup's gather would race the stores of the others on the same plane
   const bool fuse0 = (k.t->rot_fuse == 2 || (k.t->rot_fuse == 1 && B == 1)) && (g & 1) && !c0_ntt &&
                      !rnt::ks_whole_ok(k.t) && rnt::col_resc_ok(k.t) && out0 != c0;
-  const size_t tmp_words = c0_ntt || c1_ntt ? words : 0;
+  // sigma(c0) | sigma(c1) (the batch) | a block for an NTT-domain input | the chunk's gadget scratch
+  rnt::WsLayout w = ws_layout(k.t).bytes(words * wb).bytes(words * wb).bytes(c0_ntt || c1_ntt ? words * wb : 0)
+                        .sub(gadget_ws(k.t, L, L)).chunk(bc);
   CallWs ws(ctx);
-  if (int rc = ws.get((2 * words + tmp_words + gadget_ws_words(k.t, L, L, bc)) * wb)) return rc;
-  char* sig0 = (char*)ws.p;
-  char* sig1 = sig0 + words * wb;
-  char* tmp = sig1 + words * wb;
-  char* KS = tmp + tmp_words * wb;
+  if (int rc = ws.get(w)) return rc;
+  char *sig0 = w.at(0), *sig1 = w.at(1), *tmp = w.at(2), *KS = w.at(3);
   // sigma(c0), sigma(c1) in coefficient domain (engine.rs:417-419; poly.rs:494-504
   // converts an NTT-domain input first)
   for (int i = fuse0 ? 1 : 0; i < 2; ++i) {
@@ -2756,17 +2749,6 @@ int hoist_chunk(const rnt::Launch& kc, char* D, char* ACC, const void* c1, uint6
   return RNT_OK;
 }
 
-// Consecutive blocks of `unit` bytes carved from a workspace (none: nullptr).
-struct Carver {
-  char* p;
-  size_t unit;
-  char* take(size_t blocks = 1) {
-    char* r = blocks ? p : nullptr;
-    p += blocks * unit;
-    return r;
-  }
-};
-
 // The polys of a chunk stay where they are in the full batch (*x, limb stride
 // full_ls) or, with more than one chunk (X non-null), are gathered into X at
 // the chunk's own limb stride.
@@ -2835,16 +2817,15 @@ int hoisted_baby_finish(const rnt::Launch& k, uint64_t ls, char* A0, char* A1, c
 // The whole-plane rings (ks_whole_ok: no U0/U1 for the terms to share): the
 // composition itself -- every term's rotation through the whole-plane
 // key-switch, its product with the plaintext taken in the NTT domain and
-// summed there, one inverse of each sum.
+// summed there, one inverse of each sum.  w: dm | Z0 Z1 | R0 R1 over the batch.
 int ct_linear_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
-                       const int32_t* steps, size_t n_terms, const char* dm, const rnt_buf* keys_a,
-                       const rnt_buf* keys_b, void* ws) {
+                       const int32_t* steps, size_t n_terms, const rnt_buf* keys_a, const rnt_buf* keys_b,
+                       const rnt::WsLayout& w) {
   rnt::Launch k = launch_for(c0);
-  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
-  const size_t pw = L * B * n * wb;
+  const size_t L = k.L, B = c0->n_polys;
   const uint64_t ls = limb_stride(c0);
-  char* Z[2] = {(char*)ws, (char*)ws + pw};
-  char* R[2] = {(char*)ws + 2 * pw, (char*)ws + 3 * pw};
+  const char* dm = w.at(0);
+  char *Z[2] = {w.at(1, 0), w.at(1, 1)}, *R[2] = {w.at(2, 0), w.at(2, 1)};
   const rnt_buf* src[2] = {c0, c1};
   for (size_t t = 0; t < n_terms; ++t) {
     if (steps[t] != 0) {
@@ -2868,26 +2849,22 @@ int ct_linear_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rn
   return RNT_OK;
 }
 
-// The four-step key-switch: chunks outside, terms inside.  Per chunk the
-// workspace holds (chunk planes of L bc N words) X0 X1 (the chunk gathered,
-// more than one chunk only) | SIG1 | SEED | NT0 NT1 Z0 Z1 (a step-0 term only)
-// | S U0 U1.  Every nonzero term is a lin_term with the plaintext row; the
-// step-0 terms' products are summed in the NTT domain, inverted and added by
-// the chunk's two inverse column passes (lin_finish).
+// The four-step key-switch: chunks outside, terms inside, on rnt::lin_fused_ws.
+// Every nonzero term is a lin_term with the plaintext row; the step-0 terms'
+// products are summed in the NTT domain, inverted and added by the chunk's two
+// inverse column passes (lin_finish).
 int ct_linear_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
-                    const int32_t* steps, size_t n_terms, const char* dm, const rnt_buf* keys_a,
-                    const rnt_buf* keys_b, char* ws, size_t bc, bool any_zero, bool any_rot) {
+                    const int32_t* steps, size_t n_terms, const rnt_buf* keys_a, const rnt_buf* keys_b,
+                    const rnt::WsLayout& w, bool any_zero, bool any_rot) {
   rnt::Launch k = launch_for(c0);
-  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
+  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys, bc = w.bc;
   const uint64_t full_ls = limb_stride(c0), two_n = 2 * (uint64_t)n;
   const bool multi = bc < B;
-  Carver cv{ws, L * bc * n * wb};
-  char* X[2] = {cv.take(multi), cv.take(multi)};
-  char* SIG1 = cv.take();
-  char* SEED = cv.take();
-  char* NT[2] = {cv.take(any_zero), cv.take(any_zero)};
-  char* Z[2] = {cv.take(any_zero), cv.take(any_zero)};
-  char* KS = cv.p;
+  const char* dm = w.at(rnt::LF_DM);
+  char* X[2] = {w.at(rnt::LF_X, 0), w.at(rnt::LF_X, 1)};
+  char *SIG1 = w.at(rnt::LF_SIG1), *SEED = w.at(rnt::LF_SEED), *KS = w.at(rnt::LF_KS);
+  char* NT[2] = {w.at(rnt::LF_RA, 0), w.at(rnt::LF_RA, 1)};
+  char* Z[2] = {w.at(rnt::LF_RB, 0), w.at(rnt::LF_RB, 1)};
   char* const tmp[2] = {SEED, SIG1};
   const rnt_buf* src[2] = {c0, c1};
   rnt_buf* out[2] = {out0, out1};
@@ -2965,28 +2942,25 @@ extern "C" int rnt_ct_linear(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, co
   }
   if (int rc = set_device(c0->ctx)) return rc;
   rnt::Launch k = launch_for(c0);
-  const size_t n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
+  const size_t n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys, dm_bytes = L * n_terms * n * wb;
   const bool composed = rnt::ks_whole_ok(k.t);
-  const size_t bc = composed ? B : ks_chunk(k.t, L, B);
-  const size_t planes = composed ? 4 : (bc < B ? 2 : 0) + 2 + (any_zero ? 4 : 0);
-  const size_t dm_bytes = L * n_terms * n * wb;
-  const size_t need = dm_bytes + planes * L * bc * n * wb + gadget_ws_words(k.t, L, L, bc) * wb;
+  const size_t bc = composed ? B : ks_chunk(k.t, L, B);  // (S alone, not the layout's total)
+  rnt::WsLayout w = composed ? ws_layout(k.t).bytes(dm_bytes).blocks(L, 2).blocks(L, 2)
+                             : rnt::lin_fused_ws(n, wb, L, dm_bytes, false, bc < B, any_zero, any_zero, 0);
   CallWs ws(out0);
-  if (int rc = ws.get(std::max<size_t>(need, 16))) return rc;
+  if (int rc = ws.get(w.chunk(bc), 16)) return rc;
   // the plaintexts in Montgomery form (m^ 2^w mod q), once per call: a
   // Montgomery product with them is then the canonical product, and the
   // key-switch sums keep their single factor 2^-w for the inverse to fold
-  char* dm = (char*)ws.p;
   rnt::Launch kd = k;
   kd.B = n_terms;
-  LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kd, 1, dm, diag->data, nullptr, 0, false),
+  LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kd, 1, w.at(0), diag->data, nullptr, 0, false),  // dm leads
          "plaintexts to Montgomery form");
   int rc;
   if (composed)
-    rc = ct_linear_composed(out0, out1, c0, c1, steps, n_terms, dm, keys_a, keys_b, dm + dm_bytes);
+    rc = ct_linear_composed(out0, out1, c0, c1, steps, n_terms, keys_a, keys_b, w);
   else
-    rc = ct_linear_fused(out0, out1, c0, c1, steps, n_terms, dm, keys_a, keys_b, dm + dm_bytes, bc, any_zero,
-                         any_rot);
+    rc = ct_linear_fused(out0, out1, c0, c1, steps, n_terms, keys_a, keys_b, w, any_zero, any_rot);
   if (rc) return rc;
   out0->in_ntt = out1->in_ntt = 0;
   return RNT_OK;
@@ -3045,21 +3019,18 @@ extern "C" int rnt_ct_rotate_hoisted(rnt_buf* out0, rnt_buf* out1, const rnt_buf
   const uint64_t full_ls = limb_stride(c0), out_ls = limb_stride(out0), two_n = 2 * (uint64_t)n;
   const rnt_buf* src[2] = {c0, c1};
   rnt_buf* out[2] = {out0, out1};
-  // per ciphertext of a chunk: the digits (L^2 planes of N words), the
-  // accumulator pairs of one k_hoist_mac group, the automorphism's staging
-  // block and the gathered c0 (more than one chunk only), within the
-  // key-switch workspace cap, one ciphertext being the floor
+  // the digits D | one k_hoist_mac group's accumulator pairs ACC | the automorphism's staging TMP | the gathered
+  // c0 (more than one chunk only; the chunk counts it regardless: not the layout's total where one holds the batch)
   const size_t tg = std::min<size_t>(nz, rnt::kHoistT);
-  const size_t bc = nz ? chunk_polys(k.t, L * L + (2 * tg + 2) * L, B) : B;
+  auto lay = [&](bool multi) { return ws_layout(k.t).blocks(L, L).blocks(L, 2 * tg).blocks(L).blocks(L, multi); };
+  const size_t bc = nz ? chunk_polys(k.t, lay(true).planes, B) : B;
   const bool multi = bc < B;
-  const size_t pw = L * bc * n * wb;
+  rnt::WsLayout w = lay(multi).chunk(bc);
   CallWs ws(out0);
   if (nz)
-    if (int rc = ws.get(L * pw + (2 * tg + 1 + (multi ? 1 : 0)) * pw)) return rc;
-  char* D = (char*)ws.p;
-  char* ACC = D + L * pw;
-  char* TMP = ACC + 2 * tg * pw;
-  char* X0 = TMP + pw;
+    if (int rc = ws.get(w)) return rc;
+  char *D = nullptr, *ACC = nullptr, *TMP = nullptr, *X0 = nullptr;
+  if (nz) D = w.at(0), ACC = w.at(1), TMP = w.at(2), X0 = w.at(3);
   for (size_t t = 0; t < n_steps; ++t) {
     if (steps[t] != 0) continue;
     for (int o = 0; o < 2; ++o)
@@ -3117,6 +3088,8 @@ struct HybridPlan {
   // the key context's limb map (a level context with a gap; else the identity)
   size_t level = UINT32_MAX, gap = 0;
   rnt::HybridConsts hc{};
+  // its hybrid scratch (rnt::hybrid_ws) with `pairs` accumulator pairs
+  rnt::WsLayout ws(size_t pairs = 1) const { return rnt::hybrid_ws(C->t->n, C->t->wide ? 8 : 4, LE, beta, pairs); }
 };
 
 // The polys between two steps of a key set: a view keeps the full key's beta.
@@ -3244,25 +3217,13 @@ rnt::Launch hybrid_launch(const HybridPlan& pl, size_t c) {
   return k;
 }
 
-// Planes of N words one poly of a chunk needs: the raised digits D
-// ((Lv + K) beta) and the two accumulators over the key basis.
-size_t hybrid_planes(const HybridPlan& pl) { return pl.LE * pl.beta + 2 * pl.LE; }
-
-// Polys per chunk within the key-switch workspace cap (`extra` further planes
-// per poly are the caller's), one poly being the floor.
-size_t hybrid_chunk(const HybridPlan& pl, size_t B, size_t extra) {
-  return chunk_polys(pl.C->t.get(), hybrid_planes(pl) + extra, B);
-}
-
-// The key-switch workspace of a chunk of c polys, carved from one block: the
-// raised digits D ([LE][beta c][N]) | the accumulators A0 | A1 ([LE][c][N]),
-// over the key basis.  hybrid_planes() is its size in planes per poly.
+// The hybrid scratch carved at ws for c polys: D | A0 | A1 (of the first pair).
 struct HybridWs {
-  char *D, *A0, *A1;
-  HybridWs(const HybridPlan& pl, size_t c, void* ws) : D((char*)ws) {
-    const size_t pe = pl.LE * c * pl.C->t->n * word_bytes(pl.C->t.get());
-    A0 = D + pl.beta * pe;
-    A1 = A0 + pe;
+  char *D = nullptr, *A0 = nullptr, *A1 = nullptr;
+  HybridWs() = default;
+  HybridWs(const HybridPlan& pl, size_t c, void* ws, size_t pairs = 1) {
+    const rnt::WsLayout w = pl.ws(pairs).chunk(c).place(ws);
+    D = w.at(rnt::WS_D), A0 = w.at(rnt::WS_ACC, 0), A1 = w.at(rnt::WS_ACC, 1);
   }
 };
 
@@ -3454,16 +3415,15 @@ int ct_dot_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt_buf* o
   const size_t gmax = std::min<size_t>(n_terms, rnt::kDotT);
   const bool seeded = rescale && hybrid_same_transforms(pl);
   const size_t nd = seeded ? 1 : 3;  // d2 (and, un-seeded, d0 and d1) over the ciphertext limbs
-  const size_t bc = hybrid_chunk(pl, B, (nx * gmax + nd) * L);
-  const size_t chunk_words = L * bc * n;
-  // ws: X0 | X1 | [Y0 | Y1] (gmax terms each) | D2 | [D0 | D1] | the chunk's D, A0, A1
+  // X0 | X1 | [Y0 | Y1] (gmax terms each) | D2 | [D0 | D1] | the hybrid scratch
+  enum { WX, WD, WH };
+  rnt::WsLayout w = ws_layout(k.t).blocks(gmax * L, nx).blocks(L, nd).sub(pl.ws());
+  const size_t bc = fit_chunk(pl.C->t.get(), w, B);
   CallWs cws(out0);
-  if (int rc = cws.get(std::max<size_t>(((nx * gmax + nd) * chunk_words + hybrid_planes(pl) * bc * n) * wb, 16)))
-    return rc;
+  if (int rc = cws.get(w, 16)) return rc;
   char* X[4];
-  for (size_t j = 0; j < 4; ++j) X[j] = (char*)cws.p + (j % nx) * gmax * chunk_words * wb;
-  char* D2 = (char*)cws.p + nx * gmax * chunk_words * wb;
-  char* HW = D2 + nd * chunk_words * wb;
+  for (size_t j = 0; j < 4; ++j) X[j] = w.at(WX, j % nx);
+  char *D2 = w.at(WD, 0), *HW = w.at(WH);
   const uint64_t full_ls = limb_stride(x0), out_ls = limb_stride(out0);
   for (size_t p0 = 0; p0 < B; p0 += bc) {
     const size_t c = std::min(bc, B - p0);
@@ -3472,8 +3432,8 @@ int ct_dot_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt_buf* o
     const uint64_t cls = (uint64_t)c * n;
     const size_t po = p0 * n * wb;
     const HybridWs hw(pl, c, HW);
-    char* D0 = seeded ? hw.A0 : D2 + chunk_words * wb;
-    char* D1 = seeded ? hw.A1 : D0 + chunk_words * wb;
+    char* D0 = seeded ? hw.A0 : w.at(WD, 1);
+    char* D1 = seeded ? hw.A1 : w.at(WD, 2);
     for (size_t t0 = 0; t0 < n_terms; t0 += gmax) {
       const size_t g = std::min(gmax, n_terms - t0);
       rnt::Launch kg = k;
@@ -3534,14 +3494,15 @@ extern "C" int rnt_keyswitch_hybrid(rnt_buf* acc0, rnt_buf* acc1, const rnt_buf*
   if (int rc = set_device(d->ctx)) return rc;
   if (int rc = hybrid_prepare(&pl)) return rc;
   const size_t n = d->ctx->t->n, wb = word_bytes(d->ctx->t.get()), B = d->n_polys;
-  const size_t bc = hybrid_chunk(pl, B, 0);
+  rnt::WsLayout w = ws_layout(d->ctx->t.get()).sub(pl.ws());
+  const size_t bc = fit_chunk(pl.C->t.get(), w, B);
   CallWs ws(acc0);
-  if (int rc = ws.get(std::max<size_t>(hybrid_planes(pl) * bc * n * wb, 16))) return rc;
+  if (int rc = ws.get(w, 16)) return rc;
   const uint64_t ls = limb_stride(d);
   for (size_t p0 = 0; p0 < B; p0 += bc) {
     const size_t c = std::min(bc, B - p0);
     const size_t off = p0 * n * wb;
-    if (int rc = hybrid_chunk_run(pl, c, HybridWs(pl, c, ws.p), (const char*)d->data + off, ls, key_a, key_b,
+    if (int rc = hybrid_chunk_run(pl, c, HybridWs(pl, c, w.at(0)), (const char*)d->data + off, ls, key_a, key_b,
                                   (char*)acc0->data + off, (char*)acc1->data + off, ls, nullptr, nullptr, 0))
       return rc;
   }
@@ -3578,13 +3539,12 @@ extern "C" int rnt_ct_rotate_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf*
   const size_t n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
   const size_t words = pl.Lv * B * n;
   const uint64_t g = rotation_exponent(kk, 2 * (uint64_t)n);
-  const size_t bc = hybrid_chunk(pl, B, 0);
-  // ws: sigma(c0) | sigma(c1) (the batch, so the outputs may be the inputs) | the chunk's D, A0, A1
+  // sigma(c0) | sigma(c1) (the batch, so the outputs may be the inputs) | the hybrid scratch
+  rnt::WsLayout w = ws_layout(k.t).bytes(words * wb).bytes(words * wb).sub(pl.ws());
+  const size_t bc = fit_chunk(pl.C->t.get(), w, B);
   CallWs ws(out0);
-  if (int rc = ws.get(std::max<size_t>((2 * words + hybrid_planes(pl) * bc * n) * wb, 16))) return rc;
-  char* sig0 = (char*)ws.p;
-  char* sig1 = sig0 + words * wb;
-  char* HW = sig1 + words * wb;
+  if (int rc = ws.get(w, 16)) return rc;
+  char *sig0 = w.at(0), *sig1 = w.at(1), *HW = w.at(2);
   LAUNCH(k.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(k, sig0, c0->data, g), "automorphism");
   LAUNCH(k.t, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(k, sig1, c1->data, g), "automorphism");
   const uint64_t ls = limb_stride(c0);
@@ -3676,16 +3636,15 @@ static int ct_mul_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt
   const bool seeded = rescale && hybrid_same_transforms(pl);
   const size_t nt = tensor_blocks(k);
   const size_t nd = seeded ? 1 : 3;  // d2 (and, un-seeded, d0 and d1) over the ciphertext limbs
-  const size_t bc = hybrid_chunk(pl, B, (nt + nd) * L);
-  const size_t chunk_words = L * bc * n;
-  // ws: [T0..T3] | D2 | [D0 | D1] | the chunk's D, A0, A1
+  // [T0..T3] | D2 | [D0 | D1] | the hybrid scratch
+  enum { WT, WD, WH };
+  rnt::WsLayout w = ws_layout(k.t).blocks(L, nt).blocks(L, nd).sub(pl.ws());
+  const size_t bc = fit_chunk(pl.C->t.get(), w, B);
   CallWs cws(out0);
-  if (int rc = cws.get(std::max<size_t>(((nt + nd) * chunk_words + hybrid_planes(pl) * bc * n) * wb, 16))) return rc;
-  char* ws = (char*)cws.p;
-  char* T[4];
-  for (int i = 0; i < 4; ++i) T[i] = ws + i * chunk_words * wb;
-  char* D2 = ws + nt * chunk_words * wb;
-  char* HW = D2 + nd * chunk_words * wb;
+  if (int rc = cws.get(w, 16)) return rc;
+  char* T[4] = {};
+  for (size_t i = 0; i < nt; ++i) T[i] = w.at(WT, i);
+  char *D2 = w.at(WD, 0), *HW = w.at(WH);
   const uint64_t full_ls = limb_stride(c0), out_ls = limb_stride(out0);
   for (size_t p0 = 0; p0 < B; p0 += bc) {
     const size_t c = std::min(bc, B - p0);
@@ -3695,8 +3654,8 @@ static int ct_mul_hybrid_body(const char* name, bool rescale, rnt_buf* out0, rnt
     const size_t po = p0 * n * wb;
     auto off = [&](const rnt_buf* b) { return (const char*)b->data + po; };
     const HybridWs hw(pl, c, HW);
-    char* D0 = seeded ? hw.A0 : D2 + chunk_words * wb;
-    char* D1 = seeded ? hw.A1 : D0 + chunk_words * wb;
+    char* D0 = seeded ? hw.A0 : w.at(WD, 1);
+    char* D1 = seeded ? hw.A1 : w.at(WD, 2);
     if (int rc = tensor(kc, T, D0, D1, D2, cls, off(c0), off(c1), off(c0p), off(c1p), full_ls)) return rc;
     HybridAffine ha;
     if (aff) {
@@ -3809,20 +3768,16 @@ int bsgs_inner_sums(const rnt::Launch& k, const BsgsPlan& plan, char* VB, const 
 // The whole-plane rings: the composition itself on the whole batch -- every
 // baby rotation through the whole-plane key-switch and a forward transform,
 // the inner sums, one inverse per sum, every giant rotation, adds.
-// ws: RB (2 n1 blocks) | VB (2 nv) | T0 T1.
+// w, over the batch: dm | RB | VB | T0 T1 | hoisted: the digits | the accumulator blocks (ct_linear_bsgs_body).
 int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
                      const int32_t* baby, size_t n1, const int32_t* giant, size_t n2, const BsgsPlan& plan,
-                     const char* dm, const rnt_buf* bka, const rnt_buf* bkb, const rnt_buf* gka,
-                     const rnt_buf* gkb, char* ws, bool hoisted) {
+                     const rnt_buf* bka, const rnt_buf* bkb, const rnt_buf* gka, const rnt_buf* gkb,
+                     const rnt::WsLayout& w, bool hoisted) {
   rnt::Launch k = launch_for(c0);
-  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
-  const size_t pw = L * B * n * wb;
+  const size_t L = k.L, n = k.t->n, B = c0->n_polys, pw = w.pitch(1);
   const uint64_t ls = limb_stride(c0);
-  char* RB = ws;
-  char* VB = RB + 2 * n1 * pw;
-  char* T = VB + 2 * plan.nv * pw;
-  char* HD = T + 2 * pw;      // hoisted: the digits (L blocks) | 2 kHoistT accumulator blocks
-  char* HACC = HD + L * pw;
+  const char* dm = w.at(0);
+  char *RB = w.at(1), *VB = w.at(2), *T = w.at(3), *HD = w.at(4), *HACC = w.at(5);
   const rnt_buf* src[2] = {c0, c1};
   for (size_t i = 0; i < n1; ++i) {
     char* R[2] = {RB + 2 * i * pw, RB + (2 * i + 1) * pw};
@@ -3873,9 +3828,8 @@ int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_
   return RNT_OK;
 }
 
-// The four-step key-switch: chunks outside as in ct_linear_fused.  Per chunk
-// the workspace holds (chunk planes of L bc N words) X0 X1 (the chunk gathered,
-// more than one chunk only) | SIG1 | SEED | RB (2 n1) | VB (2 nv) | S U0 U1.
+// The four-step key-switch: chunks outside as in ct_linear_fused, on
+// rnt::lin_fused_ws.
 // Baby stage: every nonzero step runs the whole key-switch (sigma(c1) -> rows
 // -> lower, sigma(c0) as the addend) into its pair of RB blocks, a step-0 baby
 // is a copy; each block is then transformed forward.  Inner sums: k_bsgs_mac,
@@ -3883,22 +3837,16 @@ int ct_bsgs_composed(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_
 // (V0_j, V1_j) with the Montgomery-one plane `one`; the step-0 giants' sum is
 // the addend of the chunk's two inverse column passes (lin_finish).
 int ct_bsgs_fused(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1, const int32_t* baby,
-                  size_t n1, const int32_t* giant, size_t n2, const BsgsPlan& plan, const char* dm,
-                  const char* one, const rnt_buf* bka, const rnt_buf* bkb, const rnt_buf* gka,
-                  const rnt_buf* gkb, char* ws, size_t bc, bool hoisted) {
+                  size_t n1, const int32_t* giant, size_t n2, const BsgsPlan& plan, const rnt_buf* bka,
+                  const rnt_buf* bkb, const rnt_buf* gka, const rnt_buf* gkb, const rnt::WsLayout& w, bool hoisted) {
   rnt::Launch k = launch_for(c0);
-  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
-  const size_t pw = L * bc * n * wb;
+  const size_t L = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys, bc = w.bc, pw = w.pitch(rnt::LF_RA);
   const uint64_t full_ls = limb_stride(c0), two_n = 2 * (uint64_t)n;
   const bool multi = bc < B;
-  Carver cv{ws, pw};
-  char* X[2] = {cv.take(multi), cv.take(multi)};
-  char* SIG1 = cv.take();
-  char* SEED = cv.take();
-  char* RB = cv.take(2 * n1);
-  char* VB = cv.take(2 * plan.nv);
-  char* HACC = cv.take(hoisted ? 2 * rnt::kHoistT : 0);  // (the digits take S)
-  char* KS = cv.p;
+  const char *dm = w.at(rnt::LF_DM), *one = w.at(rnt::LF_ONE);
+  char* X[2] = {w.at(rnt::LF_X, 0), w.at(rnt::LF_X, 1)};
+  char *SIG1 = w.at(rnt::LF_SIG1), *SEED = w.at(rnt::LF_SEED), *RB = w.at(rnt::LF_RA), *VB = w.at(rnt::LF_RB);
+  char *HACC = w.at(rnt::LF_HACC), *KS = w.at(rnt::LF_KS);  // (a hoisted call's digits take S)
   char* const tmp[2] = {SEED, SIG1};
   char* Z[2] = {nullptr, nullptr};  // the step-0 giants' sum
   if (plan.any_zero)
@@ -4019,37 +3967,32 @@ static int ct_linear_bsgs_body(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, 
     return fail(RNT_ERR_OUT_OF_MEMORY, "host allocation failed");
   }
   const bool composed = rnt::ks_whole_ok(k.t);
-  // chunk planes per ciphertext: the baby blocks, the inner sums, SIG1, SEED
-  // and the gathered chunk (composed: the two rotation outputs); with the
-  // key-switch scratch they stay within the key-switch workspace cap, one
-  // ciphertext being the floor
-  // (hoisted: the accumulator pairs of one k_hoist_mac group; the digits take
-  // the key-switch scratch's S, which the whole-plane rings lack)
-  const size_t planes =
-      2 * n_baby + 2 * plan.nv + (composed ? 2 : 4) + (hoisted ? 2 * rnt::kHoistT + (composed ? L : 0) : 0);
-  const size_t bc = composed ? B : chunk_polys(k.t, planes * L + L * L + 2 * L, B);
-  const size_t dm_bytes = L * n_terms * n * wb;
-  const size_t one_bytes = composed ? 0 : L * n * wb;
-  const size_t used = planes - (!composed && bc == B ? 2 : 0);
-  const size_t need = dm_bytes + one_bytes + used * L * bc * n * wb + gadget_ws_words(k.t, L, L, bc) * wb;
+  // the whole-plane rings take the batch; else the chunk is what fits the key-switch workspace cap, counted
+  // with the two gather blocks even where one chunk holds the batch (then it is not the layout's total)
+  const size_t dm_bytes = L * n_terms * n * wb, acc = hoisted ? rnt::kHoistT : 0;
+  auto fused = [&](bool multi) { return rnt::lin_fused_ws(n, wb, L, dm_bytes, true, multi, n_baby, plan.nv, acc); };
+  const size_t bc = composed ? B : chunk_polys(k.t, fused(true).planes, B);
+  rnt::WsLayout w = fused(bc < B);
+  if (composed)  // dm | RB | VB | T0 T1 | hoisted: the digits | the accumulator blocks
+    w = ws_layout(k.t).bytes(dm_bytes).blocks(L, 2 * n_baby).blocks(L, 2 * plan.nv).blocks(L, 2).blocks(L, acc ? L : 0)
+            .blocks(L, 2 * acc);
   CallWs ws(out0);
-  if (int rc = ws.get(std::max<size_t>(need, 16))) return rc;
+  if (int rc = ws.get(w.chunk(bc), 16)) return rc;
   // the plaintexts in Montgomery form (m^ 2^w mod q), once per call: the inner
   // sums' Montgomery products are then the canonical products
-  char* dm = (char*)ws.p;
   rnt::Launch kd = k;
   kd.B = n_terms;
-  LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kd, 1, dm, diag->data, nullptr, 0, false),
+  LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kd, 1, w.at(0), diag->data, nullptr, 0, false),  // dm leads
          "plaintexts to Montgomery form");
   int rc;
   if (composed) {
-    rc = ct_bsgs_composed(out0, out1, c0, c1, baby_steps, n_baby, giant_steps, n_giant, plan, dm, baby_keys_a,
-                          baby_keys_b, giant_keys_a, giant_keys_b, dm + dm_bytes, hoisted);
+    rc = ct_bsgs_composed(out0, out1, c0, c1, baby_steps, n_baby, giant_steps, n_giant, plan, baby_keys_a,
+                          baby_keys_b, giant_keys_a, giant_keys_b, w, hoisted);
   } else {
-    char* one = dm + dm_bytes;
-    if (plan.any_rot) LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_mont_one(k, one), "Montgomery one");
-    rc = ct_bsgs_fused(out0, out1, c0, c1, baby_steps, n_baby, giant_steps, n_giant, plan, dm, one, baby_keys_a,
-                       baby_keys_b, giant_keys_a, giant_keys_b, one + one_bytes, bc, hoisted);
+    if (plan.any_rot)
+      LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_mont_one(k, w.at(rnt::LF_ONE)), "Montgomery one");
+    rc = ct_bsgs_fused(out0, out1, c0, c1, baby_steps, n_baby, giant_steps, n_giant, plan, baby_keys_a,
+                       baby_keys_b, giant_keys_a, giant_keys_b, w, hoisted);
   }
   if (rc) return rc;
   out0->in_ntt = out1->in_ntt = 0;
@@ -4132,42 +4075,16 @@ bool tail_fused(const rnt::Tables* tc, size_t Lv, size_t bc) {
   return Lv * bc * tc->n * word_bytes(tc) < kMdAutoBytes;
 }
 
-// The chunk of a hoisted call on B ciphertexts within the key-switch workspace
-// cap.  Per ciphertext: D (LE beta planes), the accumulator pairs of one
-// k_hoist_mac group of tg steps (2 tg LE), the caller's c_planes over C and,
-// where the tail is not k_moddown_auto, its two staging blocks (tmp_planes =
-// 2 Lv).  Two passes: the tail is chosen for the chunk that fits without the
-// staging, and an un-fused tail then shrinks the chunk to make room for it.
-struct HoistSize {
-  size_t bc;
-  bool fused;
-  size_t tmp_planes;
-};
-HoistSize hoist_size(const HybridPlan& pl, size_t B, size_t tg, size_t c_planes) {
-  const size_t acc_planes = 2 * (tg - 1) * pl.LE;  // (hybrid_planes() holds one pair)
-  HoistSize h{hybrid_chunk(pl, B, acc_planes + c_planes), true, 0};
-  h.fused = tail_fused(pl.C->t.get(), pl.Lv, h.bc);
-  if (!h.fused) {
-    h.tmp_planes = 2 * pl.Lv;
-    h.bc = hybrid_chunk(pl, B, acc_planes + c_planes + h.tmp_planes);
-  }
-  return h;
+// The layout of a hoisted call, chunked to fit the cap.  lay(tmp) declares it with `tmp` staging blocks for the tail.
+// The tail is chosen for the chunk that fits without staging; an un-fused tail then shrinks the chunk to make room.
+template <class Lay>
+rnt::WsLayout hoist_layout(const HybridPlan& pl, size_t B, Lay&& lay, bool* fused) {
+  const rnt::Tables* tc = pl.C->t.get();
+  rnt::WsLayout w = lay(0);
+  *fused = tail_fused(tc, pl.Lv, fit_chunk(tc, w, B));
+  if (!*fused) fit_chunk(tc, w = lay(2), B);
+  return w;
 }
-
-// The key-basis part of a hoisted call's workspace for chunks of bc
-// ciphertexts: D (beta blocks) | ACC (tg accumulator pairs), a block being pe
-// bytes ([LE][bc][N]).  Sized first, placed once the workspace is there.
-struct HoistWs {
-  size_t pe = 0, bytes = 0;
-  char *D = nullptr, *ACC = nullptr;
-  HoistWs() = default;
-  HoistWs(const HybridPlan& pl, size_t bc, size_t tg)
-      : pe(pl.LE * bc * pl.C->t->n * word_bytes(pl.C->t.get())), bytes((pl.beta + 2 * tg) * pe) {}
-  void place(const HybridPlan& pl, void* ws) {
-    D = (char*)ws;
-    ACC = D + pl.beta * pe;
-  }
-};
 
 // The per-step tail: dst = sigma_g(ModDown(A) (+ add)) at limb stride dst_ls,
 // A the coefficient-domain accumulator of c polys over E.  fused: one
@@ -4200,12 +4117,12 @@ int hybrid_tail(const HybridPlan& pl, size_t c, char* dst, uint64_t dst_ls, cons
 // The hoisted hybrid sums of one chunk (c polys of c1 at limb stride x1_ls):
 // one ModUp and one forward transform of D ([LE][beta c][N]) on E's tables,
 // then one k_hoist_mac launch per group of kHoistT nonzero steps into ACC
-// (2 kHoistT blocks of [LE][c][N]), both accumulators taken back to the
+// (ws.A0 on: 2 kHoistT blocks of [LE][c][N]), both accumulators taken back to the
 // coefficient domain, and finish(t, A0, A1) for every step t of the group:
 // A0 = sum_d D_d sigma_t^-1(key_b[t][d]) over E.  The caller has seen a step
 // that rotates.
 template <class Finish>
-int hybrid_hoist_chunk(const HybridPlan& pl, size_t c, const HoistWs& ws, const void* x1, uint64_t x1_ls,
+int hybrid_hoist_chunk(const HybridPlan& pl, size_t c, const HybridWs& ws, const void* x1, uint64_t x1_ls,
                        const int32_t* steps, size_t n_steps, const rnt_buf* keys_a, const rnt_buf* keys_b,
                        Finish&& finish) {
   const rnt::Tables* tc = pl.C->t.get();
@@ -4226,8 +4143,8 @@ int hybrid_hoist_chunk(const HybridPlan& pl, size_t c, const HoistWs& ws, const 
     for (; t < n_steps && nt < rnt::kHoistT; ++t) {
       if (steps[t] == 0) continue;
       idx[nt] = t;
-      a0[nt] = ws.ACC + 2 * nt * pe;
-      a1[nt] = ws.ACC + (2 * nt + 1) * pe;
+      a0[nt] = ws.A0 + 2 * nt * pe;
+      a1[nt] = ws.A0 + (2 * nt + 1) * pe;
       ka[nt] = (const char*)keys_a->data + t * key_step_polys(keys_a, pl) * n * wb;
       kb[nt] = (const char*)keys_b->data + t * key_step_polys(keys_b, pl) * n * wb;
       ++nt;
@@ -4281,18 +4198,21 @@ extern "C" int rnt_ct_rotate_hybrid_hoisted(rnt_buf* out0, rnt_buf* out1, const 
   const uint64_t full_ls = limb_stride(c0), out_ls = limb_stride(out0), two_n = 2 * (uint64_t)n;
   const rnt_buf* src[2] = {c0, c1};
   rnt_buf* out[2] = {out0, out1};
-  // ws: D | ACC | TMP, and only where a step rotates
-  HoistSize hs{B, true, 0};
-  HoistWs hw;
+  // the hybrid scratch with a k_hoist_mac group's accumulator pairs | the tail's staging, where a step rotates
+  bool fused = true;
+  size_t bc = B;
+  HybridWs hw;
+  char* TMP = nullptr;
   CallWs ws(out0);
   if (nz) {
     const size_t tg = std::min<size_t>(nz, rnt::kHoistT);
-    hs = hoist_size(pl, B, tg, 0);
-    hw = HoistWs(pl, hs.bc, tg);
-    if (int rc = ws.get(hw.bytes + hs.tmp_planes * hs.bc * n * wb)) return rc;
-    hw.place(pl, ws.p);
+    auto lay = [&](size_t tmp) { return ws_layout(k.t).sub(pl.ws(tg)).blocks(Lv, tmp); };
+    rnt::WsLayout w = hoist_layout(pl, B, lay, &fused);
+    bc = w.bc;
+    if (int rc = ws.get(w)) return rc;
+    hw = HybridWs(pl, bc, w.at(0), tg);
+    TMP = w.at(1);
   }
-  char* TMP = hw.D + hw.bytes;
   for (size_t t = 0; t < n_steps; ++t) {
     if (steps[t] != 0) continue;
     for (int o = 0; o < 2; ++o)
@@ -4301,14 +4221,14 @@ extern "C" int rnt_ct_rotate_hybrid_hoisted(rnt_buf* out0, rnt_buf* out1, const 
                                    full_ls * wb, full_ls * wb, Lv),
              "step-0 copy");
   }
-  for (size_t p0 = 0; nz && p0 < B; p0 += hs.bc) {
-    const size_t c = std::min(hs.bc, B - p0);
+  for (size_t p0 = 0; nz && p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
     const char* x0 = (const char*)c0->data + p0 * n * wb;
     auto finish = [&](size_t t, char* A0, char* A1) -> int {
       const uint64_t g = rotation_exponent(steps[t], two_n);
       const size_t off = (t * B + p0) * n * wb;
-      if (int rc = hybrid_tail(pl, c, (char*)out0->data + off, out_ls, A0, x0, full_ls, g, TMP, hs.fused)) return rc;
-      return hybrid_tail(pl, c, (char*)out1->data + off, out_ls, A1, nullptr, 0, g, TMP, hs.fused);
+      if (int rc = hybrid_tail(pl, c, (char*)out0->data + off, out_ls, A0, x0, full_ls, g, TMP, fused)) return rc;
+      return hybrid_tail(pl, c, (char*)out1->data + off, out_ls, A1, nullptr, 0, g, TMP, fused);
     };
     if (int rc = hybrid_hoist_chunk(pl, c, hw, (const char*)c1->data + p0 * n * wb, full_ls, steps, n_steps,
                                     keys_a, keys_b, finish))
@@ -4360,16 +4280,12 @@ extern "C" int rnt_ct_rotsum_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf*
   const size_t n = tc->n, wb = word_bytes(tc), Lv = k.L, B = c0->n_polys;
   const size_t z = n_steps - nz;
   const uint64_t full_ls = limb_stride(c0), two_n = 2 * (uint64_t)n;
-  // ws per ciphertext: D | A0 | A1 over E (hybrid_planes(), where a step
-  // rotates) | S over C (the c0 sum) | S1 over C (z c1, where a step is 0)
-  const size_t c_planes = (z ? 2 : 1) * Lv;
-  const size_t bc = nz ? hybrid_chunk(pl, B, c_planes) : chunk_polys(tc, c_planes, B);
-  const size_t pw = Lv * bc * n * wb;
-  const size_t pe = nz ? pl.LE * bc * n * wb : 0;
+  // the hybrid scratch (where a step rotates) | S over C (the c0 sum) | S1 over C (z c1, where a step is 0)
+  rnt::WsLayout w = ws_layout(tc).sub(nz ? pl.ws() : ws_layout(tc)).blocks(Lv).blocks(Lv, z ? 1 : 0);
+  const size_t bc = fit_chunk(tc, w, B);
   CallWs ws(out0);
-  if (int rc = ws.get((nz ? pl.beta + 2 : 0) * pe + c_planes * bc * n * wb)) return rc;
-  char* S = (char*)ws.p + (nz ? pl.beta + 2 : 0) * pe;
-  char* S1 = z ? S + pw : nullptr;
+  if (int rc = ws.get(w)) return rc;
+  char *S = w.at(1), *S1 = w.at(2);
   for (size_t p0 = 0; p0 < B; p0 += bc) {
     const size_t c = std::min(bc, B - p0);
     const uint64_t cls = (uint64_t)c * n;
@@ -4399,7 +4315,7 @@ extern "C" int rnt_ct_rotsum_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf*
       LAUNCH(tc, rnt::K_COPY, rnt::launch_copy_rows(k.s, dst1, full_ls * wb, S1, cls * wb, cls * wb, Lv), "z c1");
       continue;
     }
-    const HybridWs hw(pl, bc, ws.p);
+    const HybridWs hw(pl, bc, w.at(0));  // (at the call's pitch in every chunk)
     if (int rc = hybrid_raise(pl, c, hw.D, x1, full_ls)) return rc;
     rnt::Launch km = hybrid_launch(pl, c);
     km.Ls = pl.beta;
@@ -4491,41 +4407,29 @@ static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* o
   const size_t Lv = k.L, n = k.t->n, wb = word_bytes(k.t), B = c0->n_polys;
   const size_t n_terms = n_baby * n_giant;
   const uint64_t full_ls = limb_stride(c0), two_n = 2 * (uint64_t)n;
-  // chunk planes per ciphertext over C: the baby blocks RB (2 n_baby Lv), the
-  // inner sums VB (2 nv Lv), SIG1 | SIG0 | S0 (3 Lv) and, without
-  // k_moddown_auto, the tail's staging (2 Lv); over E: D (LE beta) and the
-  // accumulator pairs -- the baby stage's k_hoist_mac group, then the giant
-  // stage's one A0 / A1 in the same place
+  // dm, then chunk blocks over C: the baby blocks | the inner sums | SIG1 | SIG0 | S0 | the tail's staging; over E
+  // the hybrid scratch: its pairs the baby stage's k_hoist_mac group, then the giant stage's one A0 / A1 there
   const size_t tg = std::max<size_t>(std::min<size_t>(nzb, rnt::kHoistT), 1);
-  const size_t c_planes = (2 * n_baby + 2 * plan.nv + 3) * Lv;
-  HoistSize hs{B, true, 0};
-  HoistWs hw;
-  if (hyb) {
-    hs = hoist_size(pl, B, tg, c_planes);
-    hw = HoistWs(pl, hs.bc, tg);
-  } else {
-    hs.bc = std::min(B, std::max<size_t>(k.t->ks_ws_bytes / (c_planes * n * wb), 1));
-  }
-  const size_t bc = hs.bc;
-  const bool fused = hs.fused;
-  const size_t pw = Lv * bc * n * wb;
-  const size_t dm_bytes = Lv * n_terms * n * wb;
+  enum { WDM, WRB, WVB, WSIG1, WSIG0, WS0X, WTMP, WH };
+  auto lay = [&](size_t tmp) {
+    return ws_layout(k.t).bytes(Lv * n_terms * n * wb).blocks(Lv, 2 * n_baby).blocks(Lv, 2 * plan.nv).blocks(Lv)
+        .blocks(Lv).blocks(Lv).blocks(Lv, tmp).sub(hyb ? pl.ws(tg) : ws_layout(k.t));
+  };
+  bool fused = true;
+  rnt::WsLayout w = hyb ? hoist_layout(pl, B, lay, &fused) : lay(0);
+  if (!hyb) fit_chunk(k.t, w, B);
+  const size_t bc = w.bc, pw = w.pitch(WRB);
   CallWs ws(out0);
-  if (int rc = ws.get(dm_bytes + (c_planes + hs.tmp_planes) * bc * n * wb + hw.bytes)) return rc;
+  if (int rc = ws.get(w)) return rc;
   // the plaintexts in Montgomery form (m^ 2^w mod q), once per call: the inner
   // sums' Montgomery products are then the canonical products
-  char* dm = (char*)ws.p;
+  char *dm = w.at(WDM), *TMP = w.at(WTMP);
   rnt::Launch kdm = k;
   kdm.B = n_terms;
   LAUNCH(k.t, rnt::K_ELEMENTWISE, rnt::launch_bcast_mul(kdm, 1, dm, diag->data, nullptr, 0, false),
          "plaintexts to Montgomery form");
-  char* RB = dm + dm_bytes;
-  char* VB = RB + 2 * n_baby * pw;
-  char* SIG1 = VB + 2 * plan.nv * pw;
-  char* SIG0 = SIG1 + pw;
-  char* S0X = SIG0 + pw;
-  char* TMP = S0X + pw;
-  hw.place(pl, TMP + hs.tmp_planes * bc * n * wb);
+  char *RB = w.at(WRB), *VB = w.at(WVB), *SIG1 = w.at(WSIG1), *SIG0 = w.at(WSIG0), *S0X = w.at(WS0X);
+  const HybridWs hw = hyb ? HybridWs(pl, bc, w.at(WH), tg) : HybridWs();
   rnt_buf* out[2] = {out0, out1};
   for (size_t p0 = 0; p0 < B; p0 += bc) {
     const size_t c = std::min(bc, B - p0);
@@ -4562,8 +4466,7 @@ static int ct_linear_bsgs_hybrid_body(const char* name, bool rescale, rnt_buf* o
     // giant stage: sigma(V1_j) -> ModUp -> forward -> products summed into ONE
     // A0, A1 over E; sigma(V0_j) summed over C into S0, ModDown's addend
     char* S0 = plan.any_zero ? VB + 2 * plan.zslot * pw : S0X;
-    char* A0 = hw.ACC;
-    char* A1 = hw.ACC + hw.pe;
+    char *A0 = hw.A0, *A1 = hw.A1;
     bool first = true;
     for (size_t j = 0; j < n_giant; ++j) {
       if (giant_steps[j] == 0) continue;
@@ -4719,13 +4622,12 @@ int ct_plain_mac_body(const char* name, bool rescale, rnt_buf* out0, rnt_buf* ou
   const size_t n = k.t->n, wb = word_bytes(k.t);
   const size_t gmax = std::min<size_t>(n_terms, rnt::kPlainT);
   const size_t ns = rescale ? 2 : 0;  // s0, s1 in workspace
-  const size_t bc = chunk_polys(k.t, (2 * gmax + ns) * L, B);
-  const size_t chunk_words = L * bc * n;
-  // ws: X (x0's and x1's gmax terms) | S (s0 | s1, the rescaling call alone)
+  // X (x0's and x1's gmax terms) | S (s0 | s1, the rescaling call alone)
+  rnt::WsLayout w = ws_layout(k.t).blocks(2 * gmax * L).blocks(ns * L, ns ? 1 : 0);
+  const size_t bc = fit_chunk(k.t, w, B);
   CallWs cws(out0);
-  if (int rc = cws.get(std::max<size_t>((2 * gmax + ns) * chunk_words * wb, 16))) return rc;
-  char* X = (char*)cws.p;
-  char* S = X + 2 * gmax * chunk_words * wb;
+  if (int rc = cws.get(w, 16)) return rc;
+  char *X = w.at(0), *S = w.at(1);
   const bool four_step = !use_mf(k) && !rnt::whole_ok(k.t, 0);
   const uint64_t full_ls = limb_stride(x0), out_ls = limb_stride(out0), m_ls = limb_stride(m);
   const uint64_t b_ls = bias ? limb_stride(bias) : 0;
@@ -4942,17 +4844,18 @@ int lincomb_impl(const char* name, bool rescale, rnt_buf* out0, rnt_buf* out1, c
   if (int rc = lincomb_stage(k.t->device, words * wb, &slot)) return rc;
   if (wb == 4) lincomb_pack<uint32_t>((uint32_t*)slot->p, x0->ctx, n_in, n_out, weights, bias);
   else lincomb_pack<uint64_t>((uint64_t*)slot->p, x0->ctx, n_in, n_out, weights, bias);
+  // the weights | their Shoup companions | the bias, as packed
+  const size_t nw = Lv * n_out * n_in * wb;
+  rnt::WsLayout w = ws_layout(k.t).bytes(nw).bytes(nw).bytes(bias ? Lv * n_out * wb : 0);
   CallWs cws(out0);
-  if (int rc = cws.get(std::max<size_t>(words * wb, 16))) return rc;
-  HIP_TRY(hipMemcpyAsync(cws.p, slot->p, words * wb, hipMemcpyHostToDevice, k.s), "hipMemcpyAsync(lincomb weights)");
+  if (int rc = cws.get(w, 16)) return rc;
+  HIP_TRY(hipMemcpyAsync(w.at(0), slot->p, words * wb, hipMemcpyHostToDevice, k.s), "hipMemcpyAsync(lincomb weights)");
   HIP_TRY(hipEventRecord(slot->ev, k.s), "hipEventRecord(lincomb weights)");
   slot->stream = k.s;
   slot->busy = true;
-  const char* w = (const char*)cws.p;
-  const size_t nw = Lv * n_out * n_in * wb;
   LAUNCH(k.t, rnt::K_LINCOMB,
          rnt::launch_lincomb(k, out0->data, out1->data, limb_stride(out0), x0->data, x1->data, limb_stride(x0), n_in,
-                             n_out, w, w + nw, bias ? w + 2 * nw : nullptr, rescale),
+                             n_out, w.at(0), w.at(1), w.at(2), rescale),
          "lincomb");
   out0->in_ntt = out1->in_ntt = 0;
   return RNT_OK;
