@@ -93,7 +93,8 @@ int rnt_device_count(int* n);
  * "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
  * "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown",
  * "moddown_auto", "moddown_rescale", "lincomb", "dot_tensor", "mod_raise",
- * "mul_monomial", "moddown_rescale_affine", "rotsum_mac", "rotsum_c0",
+ * "mul_monomial", "moddown_rescale_affine", "dh_bsgs_mac", "dh_bsgs_fold",
+ * "rotsum_mac", "rotsum_c0",
  * "automorph_ntt", "plain_mac"), the launch
  * count and summed device milliseconds since enabling. */
 int rnt_profile_enable(const rnt_ctx* ctx, int enable);
@@ -548,7 +549,8 @@ int rnt_ct_mul_relin_hybrid(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, con
  * rnt_ct_mul_relin_rescale_hybrid, rnt_ct_linear_bsgs_hybrid_rescale,
  * rnt_ct_dot_relin_hybrid, rnt_ct_dot_relin_rescale_hybrid), of
  * rnt_ct_rotsum_hybrid (the key set of a rotate-and-sum) and of
- * rnt_ct_mul_relin_rescale_affine_hybrid, which shares the multiply's body, and the
+ * rnt_ct_mul_relin_rescale_affine_hybrid, which shares the multiply's body, and of
+ * rnt_ct_linear_bsgs_hybrid_dh and its _rescale form (both key sets), and the
  * call is then, word for word, the same call with the restricted key on a
  * root context over the view's moduli.  Both halves (and both sets of a BSGS
  * call) must be views on the SAME level-context handle; a view at level == L
@@ -752,6 +754,65 @@ int rnt_ct_linear_bsgs_hybrid_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_bu
                                       const int32_t* giant_steps, size_t n_giant, const rnt_buf* diag,
                                       const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
                                       const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b, size_t alpha);
+/* ---- the double-hoisted baby-step giant-step transform on hybrid keys
+ * (DESIGN.md "Double-hoisted hybrid BSGS"; Bossuat et al. 2021) ---------------
+ * rnt_ct_linear_bsgs_hybrid with the baby rotations never taken down from
+ * Q u P.  Notation and key sets as that call's: C, E, P = prod p_k, beta,
+ * ModUp_d, ModDown, sigma_k; baby keys in the HOISTING form, giant keys
+ * ordinary, so one pair of key sets serves both calls.  diagE[j n_baby + i] is
+ * the encoded integer polynomial of that call's diag reduced mod every modulus
+ * of E, in the NTT domain, on a context whose moduli equal q_0..q_{Lv-1},
+ * p_0..p_{K-1} BY VALUE (the keys' root E, or any context over those moduli).
+ * With D_d = ModUp_d(c1), all products negacyclic over E:
+ *   b_i != 0: T0_i = P c0 + sum_d D_d sigma_{b_i}^-1(key_b[i][d])   (P c0: [P]_{q_j} c0
+ *             T1_i =        sum_d D_d sigma_{b_i}^-1(key_a[i][d])    on q_j, 0 on p_k)
+ *             Rt_i = (sigma_{b_i}(T0_i), sigma_{b_i}(T1_i))   over E: no ModDown, sigma exact
+ *   b_i == 0: Rt_i = (P c0, P c1)                             over E, no key read
+ *   Vt_j = sum_i diagE[j n_baby + i] Rt_i                     both components, over E
+ *   Z = { j : g_j = 0 }, NZ = the others;  W_j = ModDown(Vt1_j) over C for j in NZ
+ *   A0 = sum_{j in Z} Vt0_j + sum_{j in NZ} (sigma_{g_j}(Vt0_j)
+ *                                + sum_d ModUp_d(sigma_{g_j}(W_j)) giant_key_b[j][d])
+ *   A1 = sum_{j in Z} Vt1_j + sum_{j in NZ} sum_d ModUp_d(sigma_{g_j}(W_j)) giant_key_a[j][d]
+ *   out0 = ModDown(A0), out1 = ModDown(A1)      canonical, coefficient domain, over C
+ * There is no special case: with every step 0 the result is ModDown(P x) = x,
+ * the call equals sum diag c word for word and no key buffer is read (they may
+ * be NULL; E is then the plaintexts' context).  NOT the words of
+ * rnt_ct_linear_bsgs_hybrid -- the ModDowns are grouped differently -- but the
+ * same decryption; the baby ModDown roundings are no longer multiplied by the
+ * plaintexts.  ModDowns per chunk: |NZ| + 2 instead of 2 nz_baby + 2; the price
+ * is inner sums and plaintexts over Lv + K limbs instead of Lv.
+ * rnt_ct_linear_bsgs_hybrid_dh_rescale is that result followed by
+ * rnt_ct_rescale, word for word (outputs as rnt_ct_linear_bsgs_hybrid_rescale's).
+ * Rules and statuses are rnt_ct_linear_bsgs_hybrid's (aliasing: out0 == c0 and
+ * out1 == c1 allowed; key level views in the key positions; a stage's key
+ * buffers NULL when all its steps are 0), with these for the plaintexts: a
+ * context whose moduli are not E's at this level by value, or of another degree
+ * or device -> RNT_ERR_BASIS_MISMATCH; another word width -> RNT_ERR_UNSUPPORTED;
+ * a poly count other than n_baby n_giant -> RNT_ERR_CHANNEL_COUNT (fields:
+ * n_baby n_giant, got); coefficient domain -> RNT_ERR_DOMAIN_MISMATCH; an
+ * output that shares its storage with the plaintexts, a key set or the other
+ * component's input (a wrapped buffer included) -> RNT_ERR_BAD_ARGUMENT.  A
+ * refused call leaves its outputs untouched.  ORDER: the call runs on the
+ * ciphertext context's stream; where the plaintexts live on another root
+ * context (its own stream), the call first orders itself after everything
+ * queued on that stream so far, as it does for the key basis and as
+ * rnt_mod_raise does for its input, so plaintexts uploaded or transformed just
+ * before the call need no rnt_sync.  (Not inside a capture: a recorded call
+ * reads plaintexts that are ready.)  The first call of an (E, Lv,
+ * alpha) triple builds the constants and cannot be recorded; later calls are
+ * recordable.  Profile names: "dh_bsgs_mac" (the inner sums over E, 4 giants
+ * and 16 babies a launch), "dh_bsgs_fold" (the first components into A0 / A1,
+ * 4 giants a launch). */
+int rnt_ct_linear_bsgs_hybrid_dh(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                 const int32_t* baby_steps, size_t n_baby,
+                                 const int32_t* giant_steps, size_t n_giant, const rnt_buf* diagE,
+                                 const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
+                                 const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b, size_t alpha);
+int rnt_ct_linear_bsgs_hybrid_dh_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                         const int32_t* baby_steps, size_t n_baby,
+                                         const int32_t* giant_steps, size_t n_giant, const rnt_buf* diagE,
+                                         const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
+                                         const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b, size_t alpha);
 /* ---- scalar linear combinations of ciphertexts (DESIGN.md "Scalar linear
  * combinations and polynomial evaluation") --------------------------------
  * The scalar path of a circuit: ciphertext x constant, ciphertext + constant

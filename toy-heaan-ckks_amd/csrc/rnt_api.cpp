@@ -100,7 +100,7 @@ const char* const kKernelNames[rnt::K_COUNT] = {
     "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd", "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul",
     "bsgs_mac", "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto",
     "moddown_rescale", "lincomb", "dot_tensor", "mod_raise", "mul_monomial",
-    "moddown_rescale_affine", "rotsum_mac", "rotsum_c0", "automorph_ntt", "plain_mac"};
+    "moddown_rescale_affine", "dh_bsgs_mac", "dh_bsgs_fold", "rotsum_mac", "rotsum_c0", "automorph_ntt", "plain_mac"};
 
 // A profiling call failed: clear the runtime's slot, keep the first failure
 // in the profiler, and stop profiling (rnt_profile_read reports it).
@@ -4526,6 +4526,224 @@ extern "C" int rnt_ct_linear_bsgs_hybrid_rescale(rnt_buf* out0, rnt_buf* out1, c
   return ct_linear_bsgs_hybrid_body("rnt_ct_linear_bsgs_hybrid_rescale", true, out0, out1, c0, c1, baby_steps, n_baby,
                                     giant_steps, n_giant, diag, baby_keys_a, baby_keys_b, giant_keys_a, giant_keys_b,
                                     alpha);
+}
+
+// rnt_ct_linear_bsgs_hybrid_dh (rescale false) and its _rescale form: the
+// double-hoisted transform.  The baby key products T_i stay over E in the NTT
+// domain; k_dh_bsgs_mac reads them through sigma_{b_i}'s permutation, adds the
+// P c0 seed and forms the inner sums Vt_j over E against the plaintexts over
+// E; k_dh_bsgs_fold starts A0 / A1 from the first components; each rotating
+// giant takes ModDown(Vt1_j) through the automorphism, ModUp and its key into
+// the same A0 / A1; two ModDowns (with the rescale in them where asked) close
+// the call.  No special case: with every step 0 the accumulators hold P x on
+// the q-limbs and 0 on the special ones, and ModDown returns x.
+static int ct_linear_bsgs_hybrid_dh_body(const char* name, bool rescale, rnt_buf* out0, rnt_buf* out1,
+                                         const rnt_buf* c0, const rnt_buf* c1, const int32_t* baby_steps,
+                                         size_t n_baby, const int32_t* giant_steps, size_t n_giant,
+                                         const rnt_buf* diagE, const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
+                                         const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b, size_t alpha) {
+  const rnt_buf* all[4] = {out0, out1, c0, c1};
+  for (const rnt_buf* b : all)
+    if (int rc = check_buf(b, name)) return rc;
+  if (int rc = check_buf(diagE, name)) return rc;
+  if (n_baby == 0 || n_giant == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: no steps", name);
+  if (!baby_steps || !giant_steps) return fail(RNT_ERR_BAD_ARGUMENT, "%s: null steps", name);
+  if (alpha == 0) return fail(RNT_ERR_BAD_ARGUMENT, "%s: alpha must be at least 1", name);
+  if (rescale) {
+    if (int rc = check_same(c0, c1, name)) return rc;
+  } else {
+    for (int i = 1; i < 4; ++i)
+      if (int rc = check_same(all[0], all[i], name)) return rc;
+  }
+  HybridPlan plb, plg;
+  size_t nzb = 0, nzg = 0;
+  bool have_b = false, have_g = false;
+  if (int rc = hybrid_set_check(name, c0->ctx, baby_steps, n_baby, baby_keys_a, baby_keys_b, alpha, &plb, &nzb,
+                                &have_b))
+    return rc;
+  if (int rc = hybrid_set_check(name, c0->ctx, giant_steps, n_giant, giant_keys_a, giant_keys_b, alpha, &plg, &nzg,
+                                &have_g))
+    return rc;
+  if (have_b && have_g && plb.E != plg.E)
+    return fail(RNT_ERR_BASIS_MISMATCH, "%s: the baby and giant keys belong to different key bases", name);
+  // E: the keys' basis; without any key the plaintexts' own (every step is 0, and P is still E's)
+  const rnt_ctx* C = c0->ctx;
+  const rnt_ctx* D = diagE->ctx;
+  const size_t Lv = C->L;
+  HybridPlan pl = have_b ? plb : plg;
+  if (!have_b && !have_g) {
+    pl.C = C, pl.E = D, pl.Lv = Lv, pl.LE = D->L;
+    pl.K = D->L > Lv ? D->L - Lv : 0;
+    pl.alpha = std::min(alpha, Lv);
+    pl.beta = (Lv + alpha - 1) / alpha;
+  }
+  bool same = D->L == pl.LE && D->L > Lv && D->t->log_n == C->t->log_n && D->t->device == C->t->device;
+  for (size_t t = 0; same && t < pl.LE; ++t)
+    same = D->modulus(t) == (t < Lv ? C->modulus(t) : pl.E->modulus(t));
+  if (!same)
+    return fail(RNT_ERR_BASIS_MISMATCH,
+                "%s: the plaintexts' basis does not hold the ciphertext's moduli followed by the special primes", name);
+  if (D->t->wide != C->t->wide)
+    return fail_fields(RNT_ERR_UNSUPPORTED, 0, 0, "%s: plaintext and ciphertext bases have different device word widths",
+                       name);
+  const size_t n_terms = n_baby * n_giant;
+  if (n_baby > SIZE_MAX / n_giant || diagE->n_polys != n_terms)
+    return fail_fields(RNT_ERR_CHANNEL_COUNT, n_terms, diagE->n_polys, "%s: %zu plaintexts for %zu x %zu steps", name,
+                       diagE->n_polys, n_giant, n_baby);
+  if (!diagE->in_ntt) return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the plaintexts must be in the NTT domain", name);
+  if (c0->in_ntt || c1->in_ntt)
+    return fail(RNT_ERR_DOMAIN_MISMATCH, "%s: the ciphertext must be in coefficient domain", name);
+  if (rescale)
+    if (int rc = rescaled_outputs_check(name, out0, out1, c0, c0->n_polys)) return rc;
+  const rnt_buf* ins[7] = {c0, c1, diagE, baby_keys_a, baby_keys_b, giant_keys_a, giant_keys_b};
+  if (out0 == out1 || out0->data == out1->data) return fail(RNT_ERR_BAD_ARGUMENT, "%s: out0 aliases out1", name);
+  for (int i = 0; i < 7; ++i) {
+    if (!ins[i]) continue;
+    if ((i != 0 && (out0 == ins[i] || out0->data == ins[i]->data)) ||
+        (i != 1 && (out1 == ins[i] || out1->data == ins[i]->data)))
+      return fail(RNT_ERR_BAD_ARGUMENT, "%s: an output aliases an input other than its own component", name);
+  }
+  if (int rc = set_device(C)) return rc;
+  if (int rc = hybrid_prepare(&pl)) return rc;
+  const rnt::Launch k = launch_for(c0);
+  const rnt::Tables* tc = k.t;
+  if (D->t.get() != tc && D->t->stream != tc->stream && g_capture == nullptr) {
+    // the plaintexts may still be in the making (an upload, their transform) on their own basis' stream
+    hipEvent_t ev = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate(plaintext order)");
+    hipError_t e = hipEventRecord(ev, D->t->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(tc->stream, ev, 0);
+    cleanup(hipEventDestroy(ev), "hipEventDestroy(plaintext order)");
+    HIP_TRY(e, "hipStreamWaitEvent(plaintext order)");
+  }
+  const size_t n = tc->n, wb = word_bytes(tc), B = c0->n_polys, LE = pl.LE;
+  const uint64_t full_ls = limb_stride(c0), two_n = 2 * (uint64_t)n;
+  // chunk blocks: c0^ c1^ over C | W = ModDown(Vt1_j) | its automorphism | over E the baby products T0_i T1_i | the
+  // inner sums of one giant group Vt0_j Vt1_j | the hybrid scratch (the digits, A0 A1)
+  const size_t jg = std::min<size_t>(n_giant, rnt::kDhJt);
+  enum { WCH, WW, WSIG, WT, WV, WH };
+  rnt::WsLayout w = ws_layout(tc).blocks(Lv, 2).blocks(Lv, nzg ? 1 : 0).blocks(Lv, nzg ? 1 : 0).blocks(LE, 2 * nzb)
+                        .blocks(LE, 2 * jg).sub(pl.ws());
+  const size_t bc = fit_chunk(tc, w, B);
+  CallWs ws(out0);
+  if (int rc = ws.get(w)) return rc;
+  char *CH0 = w.at(WCH, 0), *CH1 = w.at(WCH, 1), *Wd = w.at(WW), *SIG = w.at(WSIG);
+  const HybridWs hw(pl, bc, w.at(WH));  // (at the call's pitch in every chunk)
+  std::vector<const void*> t0, t1;
+  std::vector<uint64_t> gb;
+  try {
+    t0.assign(n_baby, nullptr), t1.assign(n_baby, nullptr), gb.assign(n_baby, 1);
+  } catch (...) {
+    return fail(RNT_ERR_OUT_OF_MEMORY, "host allocation failed");
+  }
+  for (size_t i = 0, ti = 0; i < n_baby; ++i) {
+    if (baby_steps[i] == 0) continue;
+    t0[i] = w.at(WT, 2 * ti), t1[i] = w.at(WT, 2 * ti + 1);
+    gb[i] = rotation_exponent(baby_steps[i], two_n);
+    ++ti;
+  }
+  const uint64_t m_ls = limb_stride(diagE), m_row = (uint64_t)n_baby * n;
+  for (size_t p0 = 0; p0 < B; p0 += bc) {
+    const size_t c = std::min(bc, B - p0);
+    rnt::Launch kc = k;
+    kc.B = c;
+    const rnt::Launch ke = hybrid_launch(pl, c);
+    rnt::Launch kq = ke;  // the ciphertext's limbs on the key basis' transforms
+    kq.L = Lv;
+    const uint64_t cls = (uint64_t)c * n;
+    const char* x[2] = {(const char*)c0->data + p0 * n * wb, (const char*)c1->data + p0 * n * wb};
+    char* CH[2] = {CH0, CH1};
+    for (int o = 0; o < 2; ++o) {
+      if (int rc = copy_rows(kc, CH[o], cls, x[o], full_ls, cls, Lv)) return rc;
+      if (int rc = fwd_raw(kq, CH[o], cls, tc)) return rc;
+    }
+    // baby stage: T_i = sum_d D_d sigma_i^-1(key[i][d]) over E, kHoistT steps a launch; nothing comes down
+    if (nzb) {
+      if (int rc = hybrid_raise(pl, c, hw.D, x[1], full_ls)) return rc;
+      rnt::Launch km = ke;
+      km.Ls = pl.beta;
+      for (size_t i = 0; i < n_baby;) {
+        void* a0[rnt::kHoistT] = {};
+        void* a1[rnt::kHoistT] = {};
+        const void* ka[rnt::kHoistT] = {};
+        const void* kb[rnt::kHoistT] = {};
+        uint32_t nt = 0;
+        for (; i < n_baby && nt < rnt::kHoistT; ++i) {
+          if (baby_steps[i] == 0) continue;
+          a0[nt] = const_cast<void*>(t0[i]);
+          a1[nt] = const_cast<void*>(t1[i]);
+          ka[nt] = (const char*)baby_keys_a->data + i * key_step_polys(baby_keys_a, pl) * n * wb;
+          kb[nt] = (const char*)baby_keys_b->data + i * key_step_polys(baby_keys_b, pl) * n * wb;
+          ++nt;
+        }
+        if (nt == 0) break;
+        LAUNCH_ON(tc, ke.s, rnt::K_HOIST_MAC,
+                  rnt::launch_hoist_mac(km, a0, a1, nt, hw.D, ka, kb, limb_stride(baby_keys_a)),
+                  "hoisted hybrid key products");
+      }
+    }
+    // giant groups: inner sums over E, the fold into A0 / A1, then each rotating giant's key products
+    for (size_t j0 = 0; j0 < n_giant; j0 += jg) {
+      const uint32_t nj = (uint32_t)std::min(jg, n_giant - j0);
+      void* v0[rnt::kDhJt] = {};
+      void* v1[rnt::kDhJt] = {};
+      uint64_t gf[rnt::kDhJt] = {};
+      for (uint32_t jj = 0; jj < nj; ++jj) {
+        v0[jj] = w.at(WV, 2 * jj), v1[jj] = w.at(WV, 2 * jj + 1);
+        gf[jj] = giant_steps[j0 + jj] == 0 ? 0 : rotation_exponent(giant_steps[j0 + jj], two_n);
+      }
+      for (size_t b0 = 0; b0 < n_baby; b0 += rnt::kDhBt) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(rnt::kDhBt, n_baby - b0);
+        const char* m = (const char*)diagE->data + (j0 * n_baby + b0) * n * wb;
+        LAUNCH_ON(tc, ke.s, rnt::K_DH_BSGS_MAC,
+                  rnt::launch_dh_bsgs_mac(ke, v0, v1, nj, t0.data() + b0, t1.data() + b0, gb.data() + b0, nb, CH0, CH1,
+                                          m, m_ls, m_row, b0 != 0, pl.hc),
+                  "double-hoisted inner sums");
+      }
+      LAUNCH_ON(tc, ke.s, rnt::K_DH_BSGS_FOLD, rnt::launch_dh_bsgs_fold(ke, hw.A0, hw.A1, v0, v1, gf, nj, j0 != 0),
+                "double-hoisted fold");
+      for (uint32_t jj = 0; jj < nj; ++jj) {
+        if (gf[jj] == 0) continue;
+        const size_t j = j0 + jj;
+        if (int rc = inv_raw(ke, v1[jj], cls, tc)) return rc;
+        LAUNCH_ON(tc, ke.s, rnt::K_MODDOWN, rnt::launch_moddown(ke, Wd, cls, v1[jj], cls, nullptr, 0, pl.hc),
+                  "ModDown");
+        LAUNCH(tc, rnt::K_AUTOMORPHISM, rnt::launch_automorphism(kc, SIG, Wd, gf[jj]), "automorphism");
+        if (int rc = hybrid_raise(pl, c, hw.D, SIG, cls)) return rc;
+        if (int rc = hybrid_products(pl, c, hw.D, hw.A0, hw.A1,
+                                     (const char*)giant_keys_a->data + j * key_step_polys(giant_keys_a, pl) * n * wb,
+                                     (const char*)giant_keys_b->data + j * key_step_polys(giant_keys_b, pl) * n * wb,
+                                     limb_stride(giant_keys_a), HybridMac::accumulate))
+          return rc;
+      }
+    }
+    if (int rc = hybrid_lower(pl, c, hw.A0, hw.A1, (char*)out0->data + p0 * n * wb, (char*)out1->data + p0 * n * wb,
+                              limb_stride(out0), nullptr, nullptr, 0, rescale))
+      return rc;
+  }
+  out0->in_ntt = out1->in_ntt = 0;
+  return RNT_OK;
+}
+
+extern "C" int rnt_ct_linear_bsgs_hybrid_dh(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                            const int32_t* baby_steps, size_t n_baby, const int32_t* giant_steps,
+                                            size_t n_giant, const rnt_buf* diagE, const rnt_buf* baby_keys_a,
+                                            const rnt_buf* baby_keys_b, const rnt_buf* giant_keys_a,
+                                            const rnt_buf* giant_keys_b, size_t alpha) {
+  return ct_linear_bsgs_hybrid_dh_body("rnt_ct_linear_bsgs_hybrid_dh", false, out0, out1, c0, c1, baby_steps, n_baby,
+                                       giant_steps, n_giant, diagE, baby_keys_a, baby_keys_b, giant_keys_a,
+                                       giant_keys_b, alpha);
+}
+
+extern "C" int rnt_ct_linear_bsgs_hybrid_dh_rescale(rnt_buf* out0, rnt_buf* out1, const rnt_buf* c0, const rnt_buf* c1,
+                                                    const int32_t* baby_steps, size_t n_baby,
+                                                    const int32_t* giant_steps, size_t n_giant, const rnt_buf* diagE,
+                                                    const rnt_buf* baby_keys_a, const rnt_buf* baby_keys_b,
+                                                    const rnt_buf* giant_keys_a, const rnt_buf* giant_keys_b,
+                                                    size_t alpha) {
+  return ct_linear_bsgs_hybrid_dh_body("rnt_ct_linear_bsgs_hybrid_dh_rescale", true, out0, out1, c0, c1, baby_steps,
+                                       n_baby, giant_steps, n_giant, diagE, baby_keys_a, baby_keys_b, giant_keys_a,
+                                       giant_keys_b, alpha);
 }
 
 extern "C" int rnt_copy_polys(rnt_buf* dst, size_t dst_first, const rnt_buf* src, size_t src_first,

@@ -185,7 +185,7 @@ enum KernelId {
   K_SFFT, K_SAMPLE, K_COPY, K_PLANE_FUSED, K_MF_NTT_FWD, K_MF_NTT_INV, K_WHOLE_FWD, K_WHOLE_INV, K_WHOLE_MUL,
   K_KS_WHOLE, K_TENSOR_WHOLE, K_MF_TENSOR, K_MF_MUL, K_BSGS_MAC, K_HOIST_DIGITS, K_HOIST_MAC, K_MODUP, K_MODDOWN,
   K_MODDOWN_AUTO, K_MODDOWN_RESCALE, K_LINCOMB, K_DOT_TENSOR, K_MOD_RAISE, K_MUL_MONOMIAL,
-  K_MODDOWN_RESCALE_AFFINE, K_ROTSUM_MAC, K_ROTSUM_C0, K_AUTOMORPH_NTT, K_PLAIN_MAC, K_COUNT
+  K_MODDOWN_RESCALE_AFFINE, K_DH_BSGS_MAC, K_DH_BSGS_FOLD, K_ROTSUM_MAC, K_ROTSUM_C0, K_AUTOMORPH_NTT, K_PLAIN_MAC, K_COUNT
 };
 
 struct Prof {
@@ -549,6 +549,27 @@ hipError_t launch_mul_monomial(const Launch& k, void* out, const void* in, uint6
 hipError_t launch_hoist_mac_seed(const Launch& k, void* acc0, void* acc1, const void* d, const void* key_a,
                                  const void* key_b, uint64_t key_ls, const void* seed_a, const void* seed_b,
                                  uint64_t seed_ls, const HybridConsts& hc);
+// The double-hoisted transform (rnt_ct_linear_bsgs_hybrid_dh).  k as the hybrid
+// launchers': the key basis' tables and limb map, k.L = Lv + K, k.B the chunk's
+// polys.  launch_dh_bsgs_mac (k_dh_bsgs_mac), nj <= kDhJt giants and nb <= kDhBt
+// babies in one launch: out0[jj] (+)= sum_b m[jj][b] (.) sigma_{g[b]}(T0_b + P c0^),
+// out1[jj] with T1_b, every block [k.L][k.B][N] in the NTT domain, canonical.
+// t0[b] / t1[b]: baby b's hoisted key products over E (launch_hoist_mac's), or
+// both nullptr for a step of 0 -- then the term is (P c0^, P c1^) at the lane's
+// own position and g[b] is not read.  c0h / c1h: the transformed ciphertext,
+// [hc.Lv][k.B][N]; m: plane (jj = 0, b = 0) of the plaintexts over E in plain
+// NTT-domain form, dense in working limbs at limb stride m_ls, giant stride
+// m_row, baby stride N; accum: added to what the outputs hold.  The outputs
+// alias no input.  launch_dh_bsgs_fold (k_dh_bsgs_fold): A0 (+)= sum over the
+// nj giants of v0[jj] (g[jj] == 0) or sigma_{g[jj]}(v0[jj]); A1 (+)= the v1[jj]
+// with g[jj] == 0; without accum the launch initialises A0 and A1.
+constexpr uint32_t kDhJt = 4;
+constexpr uint32_t kDhBt = 16;
+hipError_t launch_dh_bsgs_mac(const Launch& k, void* const* out0, void* const* out1, uint32_t nj, const void* const* t0,
+                              const void* const* t1, const uint64_t* g, uint32_t nb, const void* c0h, const void* c1h,
+                              const void* m, uint64_t m_ls, uint64_t m_row, bool accum, const HybridConsts& hc);
+hipError_t launch_dh_bsgs_fold(const Launch& k, void* A0, void* A1, const void* const* v0, const void* const* v1,
+                               const uint64_t* g, uint32_t nj, bool accum);
 // launch_rescale with limb strides: k.B polys of k.L input limbs at in_ls, the
 // k.L - 1 output limbs at out_ls (a chunk of a batch on either side).
 hipError_t launch_rescale_strided(const Launch& k, void* out, uint64_t out_ls, const void* in, uint64_t in_ls);

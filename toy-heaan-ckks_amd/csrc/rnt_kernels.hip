@@ -563,6 +563,206 @@ k_rotsum_c0(W* out, const W* __restrict__ x, RotsumC0Args a, TabPtrs<W> tp, uint
   out[(uint64_t)l * limb_words + i] = s;
 }
 
+// A lane's vector of sigma_g(x) in the NTT domain, x one plane: the V source
+// positions src[] of V consecutive positions lie in ONE aligned vector (the map
+// is block-structured), permuted inside.  VEC: that vector is loaded whole and
+// the words picked in registers (selects on the low bits, no indexed register
+// file); else V = 1 and it is the word itself.
+template <class W, bool VEC, int V>
+__device__ __forceinline__ void ld_gather_vec(W (&o)[V], const W* plane, const uint32_t (&src)[V]) {
+  if constexpr (VEC) {
+    W w[V];
+    ld_vec<W, VEC, V>(w, plane + (src[0] & ~(uint32_t)(V - 1)));
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const uint32_t e = src[v] & (uint32_t)(V - 1);
+      W r = w[0];
+#pragma unroll
+      for (int u = 1; u < V; ++u) r = e == (uint32_t)u ? w[u] : r;
+      o[v] = r;
+    }
+  } else {
+    o[0] = plane[src[0]];
+  }
+}
+
+// The inner sums of the double-hoisted transform (rnt_ct_linear_bsgs_hybrid_dh)
+// in the NTT domain over E, both components of nj <= DH_JT giants and nb <=
+// DH_BT babies in one launch:
+//   out0[jj] (+)= sum_b m[jj][b] (.) sigma_{g_b}(T0_b + P c0^),  out1[jj] with T1_b
+// T0_b / T1_b ([L][B][N], canonical) are the hoisted key products of baby b
+// BEFORE any ModDown, read through the NTT-domain permutation of sigma_{g_b}
+// (ntt_automorph_src: aligned vectors onto aligned vectors), so the rotated
+// blocks are never written.  P c0^ enters on the limbs j < Lv alone, from the
+// transformed ciphertext (c0h, c1h: [Lv][B][N]) through the same permutation:
+// mont_mul(c, P 2^w) = [P]_{q_j} c.  A baby with t0[b] == nullptr is a step of
+// 0: (P c0^, P c1^) at the lane's own position, nothing on the special limbs.
+// m points at plane (jj = 0, b = 0) of the plaintexts over E in their PLAIN
+// NTT-domain form (limb stride m_ls, giant stride m_row, baby stride N, one
+// plane for every poly of the batch); the Montgomery products x m 2^-w are
+// summed canonically and every sum is multiplied ONCE by 2^w mod q in the
+// epilogue (k_plain_mac's rule), so the plaintexts take no pass of their own.
+// `accum` (uniform): added to what the outputs hold (the baby groups after the
+// first).  Grid as k_hoist_mac; a lane owns one vector position of one limb
+// and 2 DH_JT sums.
+constexpr int DH_JT = (int)kDhJt;
+constexpr int DH_BT = (int)kDhBt;
+
+template <class W>
+struct DhMacArgs {
+  const W* t0[DH_BT];
+  const W* t1[DH_BT];
+  uint32_t g[DH_BT];
+  W* out0[DH_JT];
+  W* out1[DH_JT];
+};
+template <class W, bool VEC>
+__global__ void __launch_bounds__(256)
+k_dh_bsgs_mac(DhMacArgs<W> a, const W* __restrict__ c0h, const W* __restrict__ c1h, const W* __restrict__ m,
+              const W* __restrict__ Pw, TabPtrs<W> tp, uint32_t log_n, uint64_t limb_words, uint64_t m_ls,
+              uint64_t m_row, uint32_t nb, uint32_t nj, uint32_t Lv, uint32_t accum, LimbMap lm) {
+  constexpr int V = VEC ? 16 / (int)sizeof(W) : 1;
+  const uint32_t j = blockIdx.y;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= limb_words) return;
+  const LimbConst<W> lc = tp.lc[root_limb(j, lm)];
+  const uint64_t N = 1ull << log_n;
+  const uint32_t p0 = (uint32_t)(i & (N - 1));  // V divides N: one plane
+  const uint64_t o = (uint64_t)j * limb_words + i;
+  const uint64_t plane = o - p0;
+  const bool ql = j < Lv;  // (uniform)
+  const W pw = ql ? Pw[j] : (W)0;
+  const W* mp = m + (uint64_t)j * m_ls + p0;
+  W s0[DH_JT][V], s1[DH_JT][V];
+#pragma unroll
+  for (int jj = 0; jj < DH_JT; ++jj)
+#pragma unroll
+    for (int v = 0; v < V; ++v) s0[jj][v] = s1[jj][v] = (W)0;
+  for (uint32_t b = 0; b < nb; ++b) {  // (uniform)
+    W x0[V], x1[V];
+    if (a.t0[b] == nullptr) {  // (uniform) a step of 0
+      if (!ql) continue;
+      W u0[V], u1[V];
+      ld_vec<W, VEC, V>(u0, c0h + o);
+      ld_vec<W, VEC, V>(u1, c1h + o);
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        x0[v] = mont_mul<W>(u0[v], pw, lc.q, lc.qinv);
+        x1[v] = mont_mul<W>(u1[v], pw, lc.q, lc.qinv);
+      }
+    } else {
+      const uint32_t g = a.g[b];
+      uint32_t src[V];
+#pragma unroll
+      for (int v = 0; v < V; ++v) src[v] = ntt_automorph_src(p0 + (uint32_t)v, g, log_n);
+      ld_gather_vec<W, VEC, V>(x0, a.t0[b] + plane, src);
+      ld_gather_vec<W, VEC, V>(x1, a.t1[b] + plane, src);
+      if (ql) {
+        W u0[V];
+        ld_gather_vec<W, VEC, V>(u0, c0h + plane, src);
+#pragma unroll
+        for (int v = 0; v < V; ++v) x0[v] = add_mod<W>(x0[v], mont_mul<W>(u0[v], pw, lc.q, lc.qinv), lc.q);
+      }
+    }
+    const W* mb = mp + (uint64_t)b * N;
+#pragma unroll
+    for (int jj = 0; jj < DH_JT; ++jj) {
+      if ((uint32_t)jj < nj) {  // (uniform)
+        W mv[V];
+        ld_vec<W, VEC, V>(mv, mb + (uint64_t)jj * m_row);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          s0[jj][v] = add_mod<W>(s0[jj][v], mont_mul<W>(x0[v], mv[v], lc.q, lc.qinv), lc.q);
+          s1[jj][v] = add_mod<W>(s1[jj][v], mont_mul<W>(x1[v], mv[v], lc.q, lc.qinv), lc.q);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int jj = 0; jj < DH_JT; ++jj) {
+    if ((uint32_t)jj < nj) {  // (uniform)
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        s0[jj][v] = shoup_mul<W>(s0[jj][v], lc.rmod, lc.rmod_p, lc.q);
+        s1[jj][v] = shoup_mul<W>(s1[jj][v], lc.rmod, lc.rmod_p, lc.q);
+      }
+      if (accum) {  // (uniform)
+        W q0[V], q1[V];
+        ld_vec<W, VEC, V>(q0, a.out0[jj] + o);
+        ld_vec<W, VEC, V>(q1, a.out1[jj] + o);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          s0[jj][v] = add_mod<W>(q0[v], s0[jj][v], lc.q);
+          s1[jj][v] = add_mod<W>(q1[v], s1[jj][v], lc.q);
+        }
+      }
+      st_vec<W, VEC, V>(a.out0[jj] + o, s0[jj]);
+      st_vec<W, VEC, V>(a.out1[jj] + o, s1[jj]);
+    }
+  }
+}
+
+// The fold of the inner sums into the giant accumulators of the double-hoisted
+// transform, over E in the NTT domain:
+//   A0 (+)= sum_{jj: g = 0} v0[jj] + sum_{jj: g != 0} sigma_g(v0[jj]),  A1 (+)= sum_{jj: g = 0} v1[jj]
+// for nj <= DH_JT giants (g[jj] == 0: a giant step of 0), sigma_g the gather
+// above.  The second components of the rotating giants are not read: they go
+// through ModDown and the giant key instead, whose products k_hoist_mac_acc
+// then adds to A0 / A1.  ACC: added to what A0 / A1 hold (the giant groups
+// after the first); else the launch initialises both.  Every operand is a
+// block of the call's own workspace, 16-byte aligned with whole vectors in a
+// plane, so the kernel has the 16-byte form alone (the launcher refuses
+// anything else).
+template <class W>
+struct DhFoldArgs {
+  const W* v0[DH_JT];
+  const W* v1[DH_JT];
+  uint32_t g[DH_JT];
+};
+template <class W, bool ACC>
+__global__ void __launch_bounds__(256)
+k_dh_bsgs_fold(W* A0, W* A1, DhFoldArgs<W> a, TabPtrs<W> tp, uint32_t log_n, uint64_t limb_words, uint32_t nj,
+               LimbMap lm) {
+  constexpr bool VEC = true;
+  constexpr int V = 16 / (int)sizeof(W);
+  const uint32_t j = blockIdx.y;
+  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= limb_words) return;
+  const W q = tp.lc[root_limb(j, lm)].q;
+  const uint64_t N = 1ull << log_n;
+  const uint32_t p0 = (uint32_t)(i & (N - 1));  // V divides N: one plane
+  const uint64_t o = (uint64_t)j * limb_words + i;
+  const uint64_t plane = o - p0;
+  W s0[V], s1[V];
+  if constexpr (ACC) {
+    ld_vec<W, VEC, V>(s0, A0 + o);
+    ld_vec<W, VEC, V>(s1, A1 + o);
+  } else {
+#pragma unroll
+    for (int v = 0; v < V; ++v) s0[v] = s1[v] = (W)0;
+  }
+  for (uint32_t jj = 0; jj < nj; ++jj) {  // (uniform)
+    const uint32_t g = a.g[jj];
+    W x[V];
+    if (g == 0) {  // (uniform)
+      W y[V];
+      ld_vec<W, VEC, V>(x, a.v0[jj] + o);
+      ld_vec<W, VEC, V>(y, a.v1[jj] + o);
+#pragma unroll
+      for (int v = 0; v < V; ++v) s1[v] = add_mod<W>(s1[v], y[v], q);
+    } else {
+      uint32_t src[V];
+#pragma unroll
+      for (int v = 0; v < V; ++v) src[v] = ntt_automorph_src(p0 + (uint32_t)v, g, log_n);
+      ld_gather_vec<W, VEC, V>(x, a.v0[jj] + plane, src);
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) s0[v] = add_mod<W>(s0[v], x[v], q);
+  }
+  st_vec<W, VEC, V>(A0 + o, s0);
+  st_vec<W, VEC, V>(A1 + o, s1);
+}
+
 
 // ModUp of the hybrid key-switch: digit d = blockIdx.y owns the cnt <= alpha
 // source limbs from d alpha on.  A thread reads its vector of each of them
@@ -1669,6 +1869,78 @@ hipError_t launch_rotsum_c0(const Launch& k, void* out, const void* x, uint64_t 
     with_bool(accum, [&](auto ACC) {
       hipLaunchKernelGGL((k_rotsum_c0<W, decltype(ACC)::value>), dim3((unsigned)bx, (unsigned)k.L), dim3(256), 0, k.s,
                          (W*)out, (const W*)x, a, tab_ptrs<W>(k.t), k.t->log_n, limb_words, x_ls, nt, z);
+    });
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_dh_bsgs_mac(const Launch& k, void* const* out0, void* const* out1, uint32_t nj, const void* const* t0,
+                              const void* const* t1, const uint64_t* g, uint32_t nb, const void* c0h, const void* c1h,
+                              const void* m, uint64_t m_ls, uint64_t m_row, bool accum, const HybridConsts& hc) {
+  return by_word(k, [&](auto w) -> hipError_t {
+    using W = decltype(w);
+    const uint64_t N = 1ull << k.t->log_n;
+    const uint64_t limb_words = (uint64_t)k.B * N;
+    if (nj == 0 || nj > (uint32_t)DH_JT || nb == 0 || nb > (uint32_t)DH_BT || hc.Lv == 0 ||
+        k.L != (size_t)hc.Lv + hc.K || !limb_map_ok(k) || !c0h || !c1h || !m || !hc.Pw || m_row < (uint64_t)nb * N ||
+        m_ls < (nj - 1) * m_row + (uint64_t)nb * N)
+      return hipErrorInvalidValue;
+    if (limb_words == 0) return hipSuccess;
+    DhMacArgs<W> a{};
+    uintptr_t align = ptr_bits(c0h, c1h, m);
+    for (uint32_t b = 0; b < nb; ++b) {
+      if ((t0[b] == nullptr) != (t1[b] == nullptr)) return hipErrorInvalidValue;
+      if (t0[b] && (g[b] & 1) == 0) return hipErrorInvalidValue;
+      a.t0[b] = (const W*)t0[b];
+      a.t1[b] = (const W*)t1[b];
+      a.g[b] = (uint32_t)(g[b] & (2 * N - 1));
+      align |= ptr_bits(t0[b], t1[b]);
+    }
+    for (uint32_t jj = 0; jj < nj; ++jj) {
+      if (!out0[jj] || !out1[jj]) return hipErrorInvalidValue;
+      a.out0[jj] = (W*)out0[jj];
+      a.out1[jj] = (W*)out1[jj];
+      align |= ptr_bits(out0[jj], out1[jj]);
+    }
+    // 16-byte accesses: whole vectors within a plane, every plane and block 16-byte aligned
+    const bool vec = vec_ok<W>(N, {m_ls, m_row}, align);
+    const uint64_t bx = blocks_x<W>(limb_words, vec);
+    if (!grid_ok(bx, k.L)) return hipErrorInvalidConfiguration;
+    const dim3 grid((unsigned)bx, (unsigned)k.L);
+    with_bool(vec, [&](auto VEC) {
+      hipLaunchKernelGGL((k_dh_bsgs_mac<W, decltype(VEC)::value>), grid, dim3(256), 0, k.s, a, (const W*)c0h,
+                         (const W*)c1h, (const W*)m, (const W*)hc.Pw, tab_ptrs<W>(k.t), k.t->log_n, limb_words, m_ls,
+                         m_row, nb, nj, hc.Lv, accum ? 1u : 0u, limb_map(k));
+    });
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_dh_bsgs_fold(const Launch& k, void* A0, void* A1, const void* const* v0, const void* const* v1,
+                               const uint64_t* g, uint32_t nj, bool accum) {
+  return by_word(k, [&](auto w) -> hipError_t {
+    using W = decltype(w);
+    const uint64_t N = 1ull << k.t->log_n;
+    const uint64_t limb_words = (uint64_t)k.B * N;
+    if (nj == 0 || nj > (uint32_t)DH_JT || !limb_map_ok(k) || !A0 || !A1) return hipErrorInvalidValue;
+    if (limb_words == 0 || k.L == 0) return hipSuccess;
+    DhFoldArgs<W> a{};
+    uintptr_t align = ptr_bits(A0, A1);
+    for (uint32_t jj = 0; jj < nj; ++jj) {
+      if (!v0[jj] || !v1[jj] || (g[jj] != 0 && (g[jj] & 1) == 0)) return hipErrorInvalidValue;
+      a.v0[jj] = (const W*)v0[jj];
+      a.v1[jj] = (const W*)v1[jj];
+      a.g[jj] = (uint32_t)(g[jj] & (2 * N - 1));
+      align |= ptr_bits(v0[jj], v1[jj]);
+    }
+    // workspace blocks alone: 16-byte accesses or nothing
+    if (!vec_ok<W>(N, {}, align)) return hipErrorInvalidValue;
+    const uint64_t bx = blocks_x<W>(limb_words, true);
+    if (!grid_ok(bx, k.L)) return hipErrorInvalidConfiguration;
+    const dim3 grid((unsigned)bx, (unsigned)k.L);
+    with_bool(accum, [&](auto ACC) {
+      hipLaunchKernelGGL((k_dh_bsgs_fold<W, decltype(ACC)::value>), grid, dim3(256), 0, k.s, (W*)A0, (W*)A1, a,
+                         tab_ptrs<W>(k.t), k.t->log_n, limb_words, nj, limb_map(k));
     });
     return hipGetLastError();
   });

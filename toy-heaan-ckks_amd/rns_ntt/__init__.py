@@ -54,6 +54,8 @@ __all__ = [
     "evalmod_plan",
     "EvalModPlan",
     "linear_transform_bsgs_hybrid_rescale",
+    "linear_bsgs_hybrid_dh",
+    "hybrid_level_moduli",
     "dot_ciphertexts_hybrid",
     "conjugate_hybrid",
     "mul_i",
@@ -1386,6 +1388,63 @@ def linear_transform_bsgs_hybrid_rescale(ct: Ciphertext, diag: RnsPoly, baby_key
                                                    diag.handle, h(baby_keyset.a), h(baby_keyset.b),
                                                    h(giant_keyset.a), h(giant_keyset.b), baby_keyset.alpha))
     return Ciphertext(out0, out1, ct.logp - bits_dropped, ct.logq - bits_dropped)
+
+
+def hybrid_level_moduli(ext_basis: RnsBasis, n_special: int, level: int) -> list:
+    """The moduli ``q_0..q_{level-1}, p_0..p_{K-1}`` of a hybrid key basis at a
+    level: what the plaintexts of :func:`linear_bsgs_hybrid_dh` are encoded
+    over.  A level basis (``hybrid_level``) holds key views alone, so below the
+    top level the plaintexts live on a root basis over these moduli; at the top
+    level ``ext_basis`` itself serves."""
+    mods = ext_basis.moduli()
+    K, level = int(n_special), int(level)
+    if not 0 < K < len(mods) or not 0 < level <= len(mods) - K:
+        raise ValueError(f"hybrid_level_moduli: level {level} with {K} special primes of {len(mods)} moduli")
+    return mods[:level] + mods[len(mods) - K:]
+
+
+def linear_bsgs_hybrid_dh(ct: Ciphertext, diagE: RnsPoly, baby_keyset: RnsHybridKeySet,
+                          giant_keyset: RnsHybridKeySet, rescale: bool = False, out: Optional[Ciphertext] = None,
+                          out_basis: Optional[RnsBasis] = None) -> Ciphertext:
+    """The double-hoisted form of :func:`linear_transform_bsgs_hybrid`
+    (rnt_ct_linear_bsgs_hybrid_dh): the baby rotations stay over ``Q u P`` in
+    the NTT domain, the inner sums are formed there against ``diagE`` -- the
+    same plaintexts encoded over the key basis at the ciphertext's level
+    (:func:`hybrid_level_moduli`), NTT domain -- and only one component per
+    rotating giant and the two final sums are divided by P.  The SAME key sets
+    as :func:`linear_transform_bsgs_hybrid` (baby keys in hoisting form, giant
+    keys ordinary); the same decryption with less ModDown error, not its
+    words.  ``rescale``: followed by rescale_ciphertext, word for word, as one
+    op (``out_basis`` as in :func:`mul_ciphertexts_hybrid_rescale`); without it
+    ``out`` may be ``ct``."""
+    name = "linear_bsgs_hybrid_dh"
+    _require_hybrid_set(baby_keyset, True, f"{name} (baby keys)")
+    _require_hybrid_set(giant_keyset, False, f"{name} (giant keys)")
+    if baby_keyset.alpha != giant_keyset.alpha:
+        raise ValueError(f"{name}: the two key sets were generated for different alpha")
+    baby_keyset = _at_ct_level(baby_keyset, ct.c0.basis)
+    giant_keyset = _at_ct_level(giant_keyset, ct.c0.basis)
+    logp, logq = ct.logp, ct.logq
+    if rescale:
+        bits_dropped = ct.c0.basis.moduli()[-1].bit_length()
+        logp, logq = logp - bits_dropped, logq - bits_dropped
+        if out is None:
+            new_basis = out_basis if out_basis is not None else ct.c0.basis.drop_last(1)
+            out = Ciphertext(ct.c0._like(new_basis), ct.c0._like(new_basis), logp, logq)
+    elif out is None:
+        out = Ciphertext(ct.c0._like(), ct.c0._like(), logp, logq)
+    baby = (ctypes.c_int32 * len(baby_keyset.steps))(*baby_keyset.steps)
+    giant = (ctypes.c_int32 * len(giant_keyset.steps))(*giant_keyset.steps)
+
+    def h(p):
+        return p.handle if p is not None else None
+
+    fn = load().rnt_ct_linear_bsgs_hybrid_dh_rescale if rescale else load().rnt_ct_linear_bsgs_hybrid_dh
+    check(fn(out.c0.handle, out.c1.handle, ct.c0.handle, ct.c1.handle, baby, len(baby_keyset.steps), giant,
+             len(giant_keyset.steps), diagE.handle, h(baby_keyset.a), h(baby_keyset.b), h(giant_keyset.a),
+             h(giant_keyset.b), baby_keyset.alpha))
+    out.logp, out.logq = logp, logq
+    return out
 
 
 def ct_lincomb(ct: Ciphertext, n_in: int, weights, bias=None, rescale: bool = True,

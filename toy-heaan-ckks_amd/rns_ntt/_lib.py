@@ -167,6 +167,10 @@ SIGNATURES = {
                                                        c_int64, c_int64]),
     "rnt_ct_linear_bsgs_hybrid_rescale": (c_int, [_P, _P, _P, _P, POINTER(c_int32), c_size_t, POINTER(c_int32),
                                                   c_size_t, _P, _P, _P, _P, _P, c_size_t]),
+    "rnt_ct_linear_bsgs_hybrid_dh": (c_int, [_P, _P, _P, _P, POINTER(c_int32), c_size_t, POINTER(c_int32), c_size_t,
+                                             _P, _P, _P, _P, _P, c_size_t]),
+    "rnt_ct_linear_bsgs_hybrid_dh_rescale": (c_int, [_P, _P, _P, _P, POINTER(c_int32), c_size_t, POINTER(c_int32),
+                                                     c_size_t, _P, _P, _P, _P, _P, c_size_t]),
     "rnt_ct_rotsum_hybrid": (c_int, [_P, _P, _P, _P, POINTER(c_int32), c_size_t, _P, _P, c_size_t]),
     "rnt_copy_polys": (c_int, [_P, c_size_t, _P, c_size_t, c_size_t]),
     "rnt_ct_rescale": (c_int, [_P, _P, _P, _P]),
@@ -189,7 +193,8 @@ PROFILE_NAMES = (
     "ks_rows", "tensor_rows", "import", "export", "crt", "sfft", "sample", "copy", "plane_fused", "mf_ntt_fwd",
     "mf_ntt_inv", "whole_fwd", "whole_inv", "whole_mul", "ks_whole", "tensor_whole", "mf_tensor", "mf_mul", "bsgs_mac",
     "hoist_digits", "hoist_mac", "modup", "moddown", "moddown_auto", "moddown_rescale", "lincomb", "dot_tensor",
-    "mod_raise", "mul_monomial", "moddown_rescale_affine", "rotsum_mac", "rotsum_c0", "automorph_ntt", "plain_mac",
+    "mod_raise", "mul_monomial", "moddown_rescale_affine", "dh_bsgs_mac", "dh_bsgs_fold", "rotsum_mac", "rotsum_c0",
+    "automorph_ntt", "plain_mac",
 )
 
 _lib = None

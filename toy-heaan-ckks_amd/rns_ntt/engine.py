@@ -25,7 +25,8 @@ import numpy as np
 
 from . import (Ciphertext, CkksEncoder, DeviceRng, Plaintext, RnsBasis, RnsGadgetKey, RnsGadgetKeySet, RnsHybridKey,
                RnsHybridKeySet, RnsPoly, bsgs_diagonal_rows, check, conjugate_hybrid, ct_lincomb, ct_plain_mac,
-               dot_ciphertexts_hybrid, linear_transform, linear_transform_bsgs, merge_real_imag, mul_i,
+               dot_ciphertexts_hybrid, hybrid_level_moduli, linear_bsgs_hybrid_dh, linear_transform,
+               linear_transform_bsgs, merge_real_imag, mul_i,
                split_real_imag_hybrid,
                linear_transform_bsgs_hoisted, linear_transform_bsgs_hybrid, linear_transform_bsgs_hybrid_rescale,
                linear_transform_hybrid, load, mul_ciphertexts_gadget, mul_ciphertexts_hybrid,
@@ -85,6 +86,7 @@ class CkksEngine:
     def __init__(self, moduli, degree: int, error_std: float = 3.2,
                  hamming_weight: Optional[int] = None, device: int = 0, special_moduli=None):
         self.ext_basis = None
+        self._dh_bases = {}  # level -> the root basis over q_0..q_{level-1}, p (dh_plain_basis)
         self.special_moduli = [int(p) for p in special_moduli] if special_moduli is not None else []
         if self.special_moduli:
             if isinstance(moduli, RnsBasis):
@@ -372,11 +374,16 @@ class CkksEngine:
         scale q itself: the rescale divides by q, not by 2^scale_bits, and
         without the factor every group would scale the whole plaintext -- the
         large ``Q0 I`` of a raised ciphertext included -- by ``2^scale_bits / q``."""
+        return self._prepare_homdft("prepare_homdft", plan, top_basis, lambda s, bases: bases[s])
+
+    def _prepare_homdft(self, name: str, plan, top_basis: RnsBasis, plain_basis) -> PreparedHomDft:
+        """The level bases of ``plan`` under ``top_basis`` and every group's
+        diagonals, group s encoded on ``plain_basis(s, bases)``."""
         mods = top_basis.moduli()
         if len(mods) - plan.depth < 1:
-            raise ValueError(f"prepare_homdft: the plan consumes {plan.depth} levels, the basis has {len(mods)} limbs")
+            raise ValueError(f"{name}: the plan consumes {plan.depth} levels, the basis has {len(mods)} limbs")
         if top_basis.degree != plan.degree:
-            raise ValueError(f"prepare_homdft: the plan is for degree {plan.degree}, the basis has {top_basis.degree}")
+            raise ValueError(f"{name}: the plan is for degree {plan.degree}, the basis has {top_basis.degree}")
         bases = [top_basis] + [top_basis.drop_last(s) for s in range(1, plan.depth + 1)]
         pts = []
         for s, g in enumerate(plan.groups):
@@ -384,7 +391,7 @@ class CkksEngine:
             enc = CkksEncoder(plan.degree, q.bit_length())
             drift = q / 2.0 ** q.bit_length()
             diags = {k: v * drift for k, v in g.diags.items()}
-            pts.append(self.encode_diagonal_rows_bsgs(diags, g.baby_steps, g.giant_steps, enc, bases[s]))
+            pts.append(self.encode_diagonal_rows_bsgs(diags, g.baby_steps, g.giant_steps, enc, plain_basis(s, bases)))
         return PreparedHomDft(plan, bases, pts)
 
     def generate_homdft_key_sets(self, sk: RnsPoly, plan, rng, alpha: int) -> list:
@@ -394,7 +401,12 @@ class CkksEngine:
                  self.generate_hybrid_rotation_key_set(sk, g.giant_steps, rng, alpha)) for g in plan.groups]
 
     @staticmethod
-    def _homdft_hybrid(ct: Ciphertext, prepared: PreparedHomDft, keysets, direction: str, name: str) -> Ciphertext:
+    def _homdft_hybrid(ct: Ciphertext, prepared: PreparedHomDft, keysets, direction: str, name: str,
+                       group_call=None) -> Ciphertext:
+        """Every group of the plan as one ``group_call`` (by default
+        ``linear_transform_bsgs_hybrid_rescale``; the double-hoisted one for
+        the ``_dh`` transforms)."""
+        group_call = group_call or CkksEngine.linear_transform_bsgs_hybrid_rescale
         plan = prepared.plan
         if plan.direction != direction:
             raise ValueError(f"{name}: the plan's direction is {plan.direction!r}")
@@ -405,7 +417,7 @@ class CkksEngine:
         for s, (pt, (bk, gk)) in enumerate(zip(prepared.plaintexts, keysets)):
             if list(bk.steps) != list(plan.groups[s].baby_steps) or list(gk.steps) != list(plan.groups[s].giant_steps):
                 raise ValueError(f"{name}: the key sets of group {s} are not for the plan's steps")
-            ct = CkksEngine.linear_transform_bsgs_hybrid_rescale(ct, pt, bk, gk, out_basis=prepared.bases[s + 1])
+            ct = group_call(ct, pt, bk, gk, out_basis=prepared.bases[s + 1])
         return ct
 
     @staticmethod
@@ -422,6 +434,76 @@ class CkksEngine:
         """SlotToCoeff, the inverse: a ciphertext whose slots hold ``(a_j + i
         a_{j+n}) / 2^logp`` becomes one that decrypts to ``a``."""
         return CkksEngine._homdft_hybrid(ct, prepared, keysets, "slot_to_coeff", "slot_to_coeff_hybrid")
+
+    # -- the double-hoisted transform (rnt_ct_linear_bsgs_hybrid_dh) --------------
+    def dh_plain_basis(self, level: Optional[int] = None) -> RnsBasis:
+        """The basis the double-hoisted transform's plaintexts are encoded on
+        for a ciphertext of ``level`` limbs: ``q_0..q_{level-1}`` followed by
+        the special primes.  At the top level it is ``ext_basis``; below it a
+        root basis over those moduli (``hybrid_level_moduli``), one object per
+        level, kept.  Such a root is a full context -- its own transform tables
+        for every limb and its own stream -- made only to hold plaintexts: a
+        level context cannot hold them (it carries key views alone).  The
+        library orders a call after the plaintexts' stream."""
+        if self.ext_basis is None:
+            raise ValueError("dh_plain_basis: the engine has no special_moduli")
+        top = self.basis.channel_count()
+        level = top if level is None else int(level)
+        if level == top:
+            return self.ext_basis
+        cache = self._dh_bases
+        if level not in cache:
+            cache[level] = RnsBasis(hybrid_level_moduli(self.ext_basis, len(self.special_moduli), level), self.degree,
+                                    device=self.ext_basis.device)
+        return cache[level]
+
+    @staticmethod
+    def linear_transform_bsgs_hybrid_dh(ct: Ciphertext, diag_plaintexts: Plaintext, baby_keyset: RnsHybridKeySet,
+                                        giant_keyset: RnsHybridKeySet) -> Ciphertext:
+        """``linear_transform_bsgs_hybrid`` double-hoisted: the same key sets,
+        the plaintexts encoded on ``dh_plain_basis(level of ct)``
+        (``encode_diagonal_rows_bsgs(..., basis=that)``); logp grows by the
+        diagonals' scale."""
+        out = linear_bsgs_hybrid_dh(ct, diag_plaintexts.poly, baby_keyset, giant_keyset)
+        out.logp = ct.logp + diag_plaintexts.scale_bits
+        return out
+
+    @staticmethod
+    def linear_transform_bsgs_hybrid_dh_rescale(ct: Ciphertext, diag_plaintexts: Plaintext,
+                                                baby_keyset: RnsHybridKeySet, giant_keyset: RnsHybridKeySet,
+                                                out_basis: Optional[RnsBasis] = None) -> Ciphertext:
+        """``linear_transform_bsgs_hybrid_dh`` then ``rescale_ciphertext`` as
+        one op, word for word; logp, logq and ``out_basis`` as
+        ``linear_transform_bsgs_hybrid_rescale``."""
+        out = linear_bsgs_hybrid_dh(ct, diag_plaintexts.poly, baby_keyset, giant_keyset, rescale=True,
+                                    out_basis=out_basis)
+        out.logp += diag_plaintexts.scale_bits
+        return out
+
+    def prepare_homdft_dh(self, plan, top_basis: RnsBasis) -> PreparedHomDft:
+        """``prepare_homdft`` for the double-hoisted path: the same level bases
+        and the same diagonals, group s encoded over ``Q_l u P`` at its level
+        (``plaintexts[s]`` on ``dh_plain_basis(l)``, l = the top basis' limbs
+        less s).  ``top_basis`` holds a prefix of the engine's moduli."""
+        mods = top_basis.moduli()
+        if mods != self.basis.moduli()[: len(mods)]:
+            raise ValueError("prepare_homdft_dh: the top basis does not hold a prefix of the engine's moduli")
+        return self._prepare_homdft("prepare_homdft_dh", plan, top_basis,
+                                    lambda s, bases: self.dh_plain_basis(len(mods) - s))
+
+    @staticmethod
+    def coeff_to_slot_hybrid_dh(ct: Ciphertext, prepared: PreparedHomDft, keysets) -> Ciphertext:
+        """``coeff_to_slot_hybrid`` with every group one
+        ``linear_transform_bsgs_hybrid_dh_rescale`` call: ``prepared`` from
+        ``prepare_homdft_dh``, the SAME key sets."""
+        return CkksEngine._homdft_hybrid(ct, prepared, keysets, "coeff_to_slot", "coeff_to_slot_hybrid_dh",
+                                         CkksEngine.linear_transform_bsgs_hybrid_dh_rescale)
+
+    @staticmethod
+    def slot_to_coeff_hybrid_dh(ct: Ciphertext, prepared: PreparedHomDft, keysets) -> Ciphertext:
+        """``slot_to_coeff_hybrid`` on the double-hoisted calls."""
+        return CkksEngine._homdft_hybrid(ct, prepared, keysets, "slot_to_coeff", "slot_to_coeff_hybrid_dh",
+                                         CkksEngine.linear_transform_bsgs_hybrid_dh_rescale)
 
     # -- polynomial evaluation -------------------------------------------------
     ct_lincomb = staticmethod(ct_lincomb)

@@ -18,6 +18,12 @@ A matrix is kept as a dict from step ``k`` in ``[0, n)`` to its diagonal
 
 so nothing here is ever an n x n matrix (except ``order="natural"``, which is
 for small rings).
+
+A plan says nothing about the basis its diagonals are encoded on: the engine
+encodes them over the level's ``Q_l`` (``CkksEngine.prepare_homdft``, one
+``linear_transform_bsgs_hybrid_rescale`` per group) or over ``Q_l u P``
+(``prepare_homdft_dh``, one double-hoisted call per group) with the same key
+sets.
 """
 from __future__ import annotations
 
